@@ -2,6 +2,8 @@
 """bench.py -- encode_batch throughput of the MI355X path on BASELINE.json's configs.
 
   python bench.py --gpus 1 --steps 20 --warmup 3                      # configs[1]: GPT-2 byte-level BPE (the headline metric)
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full               # the same line with every leg below (and C3 .. o200k)
+  python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs bench_outputs   # + the last timed step's outputs (see below)
   python bench.py --config c3|c4|c5                                    # configs[2] / [3] / [4] on one GPU
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
@@ -14,10 +16,17 @@ timed region of `value` contains no collective).  The steps ROTATE over --batche
 text, > 256 MiB with their outputs) so that neither the text nor the intermediates of one step are still in the 256 MiB
 Infinity Cache when the next step reads them.
 
-Before anything is printed, a 2 % sample of the documents of EVERY timed batch is compared with the CPU oracle
-(oracle/oracle.c): a bench line only exists for bit-exact ids.
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs DIR is given, and prints
+the line: everything else below runs with --full only (tools/session.sh, the round profiles), where the objects are None
+otherwise.  With --full, before anything is printed, a 2 % sample of the documents of EVERY timed batch is compared with
+the CPU oracle (oracle/oracle.c): a --full line only exists for bit-exact ids.
 
-Rank 0 prints ONE JSON line.  Extra objects next to the contract's fields:
+  --dump-outputs DIR   the last timed step's token CSR (tok_offsets.npy, float64, every document) and the ids of a fixed,
+                       seeded sample of its documents (ids_sample.npy, in document order; sample_docs.npy,
+                       which documents; all float64, < 64 MB) -- the inputs are the same from run to run, so two builds
+                       compare output for output
+
+Rank 0 prints ONE JSON line.  Extra objects next to the contract's fields (--full):
   roofline       dominant kernel, HIP-event timed live over the same K steps; traffic from the committed PMC summary
   cpu_baseline   the reference wheel's Rayon encode_batch_fast on this box's host cores (+ 1 thread, encode_batch with
                  offsets, and the reference's 1,000-documents-per-call bench shape in `others`)
@@ -73,19 +82,62 @@ def make_corpus(config: str, n_lines: int, text_seed: int, type_seed: int, n_typ
     return synth.gen_lines(n_lines, text_seed=text_seed, type_seed=type_seed, n_types=n_types)
 
 
-class Batch:
-    """One batch resident in HBM + the 2 % oracle sample that vouches for it."""
+def sample_of(lines, rank) -> tuple[list, list]:
+    """The 2 % of a batch's documents the oracle gate compares: (indices, documents)."""
+    idx = list(range(rank % 50, len(lines), 50))
+    return idx, [lines[i] for i in idx]
 
-    def __init__(self, lines, dev, rank, keep_lines):
+
+def host_batch(config: str, n_lines: int, text_seed: int, type_seed: int, n_types: int, rank: int, keep_lines: bool):
+    """One batch's documents, packed, with its oracle sample: (buf, off, sample, lines if keep_lines)."""
+    import tokenizers_amd as ta
+    lines = make_corpus(config, n_lines, text_seed, type_seed, n_types)
+    buf, off = ta.pack_documents(lines)
+    return buf, off, sample_of(lines, rank)[1], (lines if keep_lines else None)
+
+
+def start_corpus(config: str, n_lines: int, n_batches: int, type_seed: int, n_types: int, rank: int, world: int, keep_first: bool):
+    """Start making the timed batches (seeds 100 + rank + 1000 k) in worker processes -- called before torch is imported, so the
+    forked workers never hold the device -- and return a function that waits for them: list of host_batch() tuples, in order.
+    The same documents as making them one after the other, in a fraction of the time."""
+    jobs = [(config, n_lines, 100 + rank + 1000 * k, type_seed, n_types, rank, keep_first and k == 0) for k in range(n_batches)]
+    workers = max(1, min(n_batches, 8 // max(1, world)))
+    if workers == 1:
+        return lambda: [host_batch(*j) for j in jobs]
+    import concurrent.futures
+    import multiprocessing
+    # (a caller that already holds the device -- a test process, say -- gets fresh interpreters instead of forks)
+    holds_device = "torch" in sys.modules and sys.modules["torch"].cuda.is_initialized()
+    ctx = multiprocessing.get_context("spawn" if holds_device else "fork")
+    pool = concurrent.futures.ProcessPoolExecutor(max_workers=workers, mp_context=ctx)
+    futs = [pool.submit(host_batch, *j) for j in jobs]
+
+    def wait():
+        try:
+            return [f.result() for f in futs]
+        finally:
+            pool.shutdown()
+    return wait
+
+
+class Batch:
+    """One batch resident in HBM + the 2 % oracle sample that vouches for it.  `packed` = a host_batch() tuple made elsewhere
+    (then `lines` is not needed)."""
+
+    def __init__(self, lines, dev, rank, keep_lines, packed=None):
         import torch
         import tokenizers_amd as ta
-        buf, off = ta.pack_documents(lines)
-        self.n_docs, self.n_bytes = len(lines), int(off[-1])
+        if packed is None:
+            buf, off = ta.pack_documents(lines)
+            sample = sample_of(lines, rank)[1]
+        else:
+            buf, off, sample, lines = packed
+        self.n_docs, self.n_bytes = len(off) - 1, int(off[-1])
         self.h_buf, self.h_off = buf, off                   # (the host-boundary leg rotates over the same batches)
         self.d_text = torch.from_numpy(buf).to(dev)
         self.d_off = torch.from_numpy(off).to(dev)
-        self.sample_idx = list(range(rank % 50, len(lines), 50))
-        self.sample = [lines[i] for i in self.sample_idx]
+        self.sample_idx = list(range(rank % 50, self.n_docs, 50))
+        self.sample = sample
         self.lines = lines if keep_lines else None
         self.n_tok = self.n_pretok = None
         self.checksum = None                                # of the result the parity gate vouched for (result_checksum)
@@ -105,6 +157,33 @@ def result_checksum(b) -> tuple:
     if w is None or w.numel() < n:
         w = _WEIGHTS[ids.device] = (torch.arange(n + (n >> 2), dtype=torch.int64, device=ids.device) % 1000003) + 1
     return (int(ids.sum()), int((ids * w[:ids.numel()]).sum()), int(to.sum()), int((to * w[:to.numel()]).sum()), int(b.n_tokens))
+
+
+DUMP_SEED = 20251016
+DUMP_MAX_SAMPLE_TOKENS = 6_000_000      # 48 MB of float64 ids at most, next to the token CSR (8 MB per million documents)
+
+
+def dump_outputs(out_dir: str, b) -> dict:
+    """What a caller of the timed path receives from its last step, as float64 .npy files in out_dir: the token CSR of every
+    document (tok_offsets.npy), and the ids of a fixed, seeded sample of 1 in 16 documents (sample_docs.npy: which, in order;
+    ids_sample.npy: their ids, concatenated).  The sample depends on the document count alone; a sample of more than
+    DUMP_MAX_SAMPLE_TOKENS ids is cut after the last whole document that fits.  Returns {name: shape}."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    ids = b.ids_tensor()
+    to = b.tok_offsets_tensor().cpu().numpy()
+    n_docs = to.shape[0] - 1
+    docs = np.sort(np.random.default_rng(DUMP_SEED).choice(n_docs, size=max(1, n_docs // 16), replace=False)) if n_docs else np.zeros(0, np.int64)
+    lens = to[docs + 1] - to[docs]
+    keep = int(np.searchsorted(np.cumsum(lens), DUMP_MAX_SAMPLE_TOKENS, side="right"))
+    docs, lens = docs[:keep], lens[:keep]
+    # the position of every sampled token in the ids: each document's first token + 0 .. len - 1
+    pos = np.repeat(to[docs] - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()), dtype=np.int64)
+    sel = ids[torch.from_numpy(pos).to(ids.device)].cpu().numpy().view(np.uint32) if pos.size else np.zeros(0, np.uint32)
+    out = {"tok_offsets": to.astype(np.float64), "sample_docs": docs.astype(np.float64), "ids_sample": sel.astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
 
 
 def check_against_oracle(tok, oracle_obj, batch: Batch, stream) -> int:
@@ -290,16 +369,28 @@ def main() -> None:
     ap.add_argument("--config", default="c2", choices=["c2", "c3", "c4", "c5", "o200k"],
                     help="BASELINE.json config: c2 GPT-2 BPE (the headline metric, default), c3 BERT WordPiece, "
                          "c4 Llama-3 style BPE 128k, c5 GPT-2 BPE on Zipf-length documents")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure as well: the oracle parity gate and the check of the timed outputs, the repeat "
+                         "blocks, the roofline, with-offsets, word-cache, out-of-distribution, host-boundary, single-call and CPU-baseline legs, "
+                         "the other configs (--also) and, at N > 1, the gather leg; the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR as .npy (float64): tok_offsets, sample_docs, ids_sample")
     args = ap.parse_args()
-
-    import torch
-    import torch.distributed as dist
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus != world and world == 1 and args.gpus > 1:
         raise SystemExit("launch multi-GPU runs with torch.distributed.run (one process per GPU)")
+    t0 = time.time()
+    tok_json, n_types, workload = load_config(args.config)
+    n_batches = max(1, args.batches)
+    # (the host leg, the single-call leg and the CPU baseline read the first batch's documents as strings)
+    corpus = start_corpus(args.config, args.lines, n_batches, args.type_seed, n_types, rank, world, keep_first=args.full)
+
+    import torch
+    import torch.distributed as dist
+
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the HIP path has no CPU fallback")
     torch.cuda.set_device(local_rank)
@@ -317,26 +408,21 @@ def main() -> None:
     import tokenizers_amd as ta
     from tokenizers_amd.parallel import gather_to_root
 
-    t0 = time.time()
-    tok_json, n_types, workload = load_config(args.config)
     tok = ta.Tokenizer.from_str(tok_json, device=local_rank)
-    oracle_obj = orc.Oracle(tok_json)
+    oracle_obj = orc.Oracle(tok_json) if args.full else None
     log(f"[bench] tokenizer ready in {time.time() - t0:.1f}s  sha256={synth.sha256(tok_json)[:12]} info={tok.info}")
 
     t0 = time.time()
-    n_batches = max(1, args.batches)
-    batches = []
-    for k in range(n_batches):
-        lines = make_corpus(args.config, args.lines, 100 + rank + 1000 * k, args.type_seed, n_types)
-        batches.append(Batch(lines, dev, rank, keep_lines=(k == 0)))
-        del lines
-    log(f"[bench] corpus: {n_batches} batches of {batches[0].n_docs} docs / {batches[0].n_bytes / 1e6:.1f} MB in {time.time() - t0:.1f}s")
+    batches = [Batch(None, dev, rank, keep_lines=(k == 0), packed=p) for k, p in enumerate(corpus())]
+    log(f"[bench] corpus: {n_batches} batches of {batches[0].n_docs} docs / {batches[0].n_bytes / 1e6:.1f} MB in {time.time() - t0:.1f}s more")
     stream = torch.cuda.current_stream().cuda_stream
 
-    # ---- parity gate: a 2 % sample of every timed batch against the oracle, before any timing counts ----
-    t0 = time.time()
-    n_checked = sum(check_against_oracle(tok, oracle_obj, b, stream) for b in batches)
-    log(f"[bench] parity: {n_checked} sampled documents of the timed batches equal the oracle ({time.time() - t0:.1f}s)")
+    # ---- parity gate (--full): a 2 % sample of every timed batch against the oracle, before any timing counts ----
+    n_checked = None
+    if args.full:
+        t0 = time.time()
+        n_checked = sum(check_against_oracle(tok, oracle_obj, b, stream) for b in batches)
+        log(f"[bench] parity: {n_checked} sampled documents of the timed batches equal the oracle ({time.time() - t0:.1f}s)")
 
     def encode(i):
         b = batches[i % n_batches]
@@ -364,30 +450,39 @@ def main() -> None:
     # (un-timed, in front of the contract's W warm-up steps: twenty full rotations over the batches -- some thirty milliseconds of the
     # same work -- so that clocks, the workspaces and the handle's claims statistics are where the repeat blocks find them: round 5's
     # first block ran 2.5 % behind the later ones, with three rotations round 6's still 0.6 %)
+    # (the first rotation also learns each batch's token and pre-token counts where no parity gate has: the line's token rate)
     for i in range(20 * n_batches):
-        encode(i)
+        r = encode(i)
+        if i < n_batches and batches[i].n_tok is None:
+            r.sync()
+            batches[i].n_tok, batches[i].n_pretok = r.n_tokens, r.n_pretokens
     torch.cuda.synchronize()
     elapsed = timed(encode)
-    # ---- the same measurement again, `repeat_blocks` times: K steps between the same fences, max over ranks.  The contract's block is
-    # 20 steps of about half a millisecond -- eleven milliseconds; min / median / max over five more say how much of a 2-3 % difference
-    # between two builds is the box (every rank takes part: reduce_max is a collective). ----
+    if args.dump_outputs and rank == 0:
+        t0 = time.time()
+        shapes = dump_outputs(args.dump_outputs, state["last"])
+        log(f"[bench] outputs of the last timed step in {args.dump_outputs}: {shapes} ({time.time() - t0:.1f}s)")
+    # ---- (--full) the same measurement again, `repeat_blocks` times: K steps between the same fences, max over ranks.  The contract's
+    # block is 20 steps of about half a millisecond -- eleven milliseconds; min / median / max over five more say how much of a 2-3 %
+    # difference between two builds is the box (every rank takes part: reduce_max is a collective). ----
     rep_ms = []
-    for _ in range(max(0, args.repeat_blocks)):
+    for _ in range(max(0, args.repeat_blocks) if args.full else 0):
         el, _ = timed_steps(encode, args.steps, 0, fence, reduce_max, finish_last=lambda b: b.sync())
         rep_ms.append(el / args.steps * 1e3)
     # ---- the outputs of the timed region: the LAST timed step's ids + token CSR (still in the workspace) must be the result the
     # parity gate vouched for, and so must every step of one more pass over the same K-step sequence (un-timed: the checksum runs
     # on the stream behind each encode) -- with in-batch claims a repeat's result depends on a row another workgroup publishes, so
     # "the gate passed once" is not the same statement as "the timed steps produced these ids". ----
-    last_b = batches[(args.steps - 1) % n_batches]
-    if result_checksum(state["last"]) != last_b.checksum:
-        raise SystemExit("bench: the last TIMED step's ids / token CSR differ from the result the parity gate checked for that batch")
     n_verified = 0
-    for i in range(args.steps):
-        if result_checksum(encode(i).sync()) != batches[i % n_batches].checksum:
-            raise SystemExit(f"bench: step {i} of the verification pass produced ids / token CSR that differ from the parity gate's")
-        n_verified += 1
-    log(f"[bench] timed outputs: last timed step + {n_verified} re-run steps reproduce the gate's checksums")
+    if args.full:
+        last_b = batches[(args.steps - 1) % n_batches]
+        if result_checksum(state["last"]) != last_b.checksum:
+            raise SystemExit("bench: the last TIMED step's ids / token CSR differ from the result the parity gate checked for that batch")
+        for i in range(args.steps):
+            if result_checksum(encode(i).sync()) != batches[i % n_batches].checksum:
+                raise SystemExit(f"bench: step {i} of the verification pass produced ids / token CSR that differ from the parity gate's")
+            n_verified += 1
+        log(f"[bench] timed outputs: last timed step + {n_verified} re-run steps reproduce the gate's checksums")
     # units all ranks processed in the K timed steps
     mine = np.zeros(4, dtype=np.float64)
     for i in range(args.steps):
@@ -419,7 +514,7 @@ def main() -> None:
 
     # ---- roofline leg: per-kernel HIP-event times over the same K steps (rank 0) ----
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         tok.profile(True)
         for i in range(args.steps):
             encode(i)
@@ -461,7 +556,7 @@ def main() -> None:
     # ---- with-offsets legs (rank 0, N=1): the functions the metric names -- Rust encode_batch (byte offsets + word ids) and Python's
     # encode_batch (char offsets + word ids); `value` above is encode_batch_fast ----
     with_off = None
-    if rank == 0 and world == 1 and not args.no_offsets:
+    if rank == 0 and world == 1 and args.full and not args.no_offsets:
         with_off = {}
         for mode in ("byte", "char"):
             t0 = time.time()
@@ -479,7 +574,7 @@ def main() -> None:
     # them -- the upper end of what a long-running service sees; the cold figure (cache cleared before every step: every queued word
     # is merged AND inserted) is the lower end. ----
     wcache = None
-    if rank == 0 and world == 1 and not args.no_word_cache:
+    if rank == 0 and world == 1 and args.full and not args.no_word_cache:
         tok.word_cache(True, clear=True)
         for i in range(n_batches):
             encode(i)
@@ -519,7 +614,7 @@ def main() -> None:
 
     # ---- out-of-distribution leg (rank 0, N=1): word types the vocabulary never saw -> every word runs the merge loop ----
     ood = None
-    if rank == 0 and world == 1 and not args.no_ood and args.type_seed == 0:
+    if rank == 0 and world == 1 and args.full and not args.no_ood and args.type_seed == 0:
         t0 = time.time()
         ob = Batch(make_corpus(args.config, args.lines, 100, 1, n_types), dev, rank, keep_lines=False)
         check_against_oracle(tok, oracle_obj, ob, stream)
@@ -550,7 +645,7 @@ def main() -> None:
 
     # ---- host-boundary leg (rank 0, N=1): the C-ABI call of SURVEY 8d = H2D + kernels + D2H (PCIe inclusive) ----
     host = None
-    if rank == 0 and world == 1 and not args.no_host:
+    if rank == 0 and world == 1 and args.full and not args.no_host:
         lines = batches[0].lines
         t0 = time.perf_counter()
         hb, ho = ta.pack_documents(lines)
@@ -617,7 +712,7 @@ def main() -> None:
     # tokenizer/mod.rs:1345-1348).  PCIe inclusive by construction (host buffers in, host buffers out).  With one visible GPU the list
     # names it twice: the code path runs, the figure says nothing about scaling. ----
     single_call = None
-    if rank == 0 and world == 1 and not args.no_host and not args.no_single_call:
+    if rank == 0 and world == 1 and args.full and not args.no_host and not args.no_single_call:
         try:
             if torch.cuda.device_count() < 2:
                 single_call = single_call_leg(ta, tok_json, batches[0].lines, 1, args.single_call_gpus)
@@ -630,14 +725,14 @@ def main() -> None:
 
     # ---- CPU baseline leg (rank 0, N=1 only): the reference's Rayon encode_batch on the host cores ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(tok_json, batches[0].lines, args.cpu_lines, args.config, brief=args.cpu_brief)
 
     # ---- the other BASELINE configs on this GPU (rank 0, N=1, headline config only): the same script, same flags, as child processes
     # one after the other -- so that C3 / C4 are driver-timed numbers too, not only builder-run ones ----
     others_cfg = None
     also = [c.strip() for c in args.also.split(",") if c.strip() in ("c3", "c4", "c5", "o200k")]
-    if rank == 0 and world == 1 and args.config == "c2" and also:
+    if rank == 0 and world == 1 and args.full and args.config == "c2" and also:
         others_cfg = {}
         for cfg in also:
             t0 = time.time()
@@ -666,7 +761,8 @@ def main() -> None:
             "value_out_of_distribution": ood["value"] if ood else None,
             "value_with_word_cache": wcache["value_warm"] if wcache else None,
             "parity": {"checked_documents": int(n_checked), "against": "oracle/oracle.c", "of": "every timed batch (2 % sample), ids bit-exact",
-                       "timed_outputs": f"checksums of ids + token CSR of the last timed step and of {n_verified} re-run steps equal the gated results'"},
+                       "timed_outputs": f"checksums of ids + token CSR of the last timed step and of {n_verified} re-run steps equal the gated results'"}
+                      if args.full else None,
             "config": {"workload": f"{workload}, {b0.n_docs} synthetic documents ({b0.n_bytes / 1e6:.0f} MB) per GPU per step, "
                                    f"{n_batches} distinct batches rotated, ids-only (encode_batch_fast), inputs resident in HBM",
                        "docs_per_gpu": b0.n_docs, "bytes_per_gpu": b0.n_bytes, "tokens_per_gpu": int(b0.n_tok),
@@ -678,7 +774,7 @@ def main() -> None:
         }
     # ---- gather leg: the same K steps, each ending with the collect-to-root of the final buffers over RCCL ----
     gather_obj = None
-    if (world > 1 or args.force_gather) and not args.no_gather:
+    if (args.force_gather or (world > 1 and args.full)) and not args.no_gather:
         # A collective that never completes must not cost the bench line.  A watchdog THREAD, not SIGALRM: a rank stuck inside a RCCL
         # wait sits in C++ with the GIL released, where a Python signal handler never gets to run; a thread does.  Every rank has
         # one (rank 0 prints the line first), so a hang ends the whole job instead of leaving torchrun waiting on the others.
@@ -704,9 +800,9 @@ def main() -> None:
 
 
 def other_config_leg(cfg: str, steps: int, warmup: int, n_lines: int, n_batches: int, timeout_s: int = 420) -> dict:
-    """`python bench.py --config cfg` (kernel pipeline + parity gate + roofline leg only) as a child process; the fields of its line
+    """`python bench.py --config cfg --full` (kernel pipeline + parity gate + roofline leg only) as a child process; the fields of its line
     that matter, or an error -- never an exception (the headline line must not be lost to an auxiliary leg)."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", str(steps), "--warmup", str(warmup), "--lines", str(n_lines),
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--full", "--steps", str(steps), "--warmup", str(warmup), "--lines", str(n_lines),
            "--batches", str(n_batches), "--cpu-lines", str(min(n_lines, 250_000)), "--cpu-brief", "--no-ood", "--no-host", "--no-word-cache",
            "--no-single-call", "--also", "none"] + (["--no-offsets"] if cfg == "c5" else [])
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}

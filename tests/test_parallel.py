@@ -293,3 +293,48 @@ def test_bench_timed_region_and_watchdog_over_gloo():
     assert r.returncode == 7 and "WATCHDOG" in r.stdout
     import bench
     assert bench.run_guarded(lambda: 41 + 1, 5.0, lambda: os._exit(9)) == 42
+
+
+def test_bench_corpus_workers_make_the_serial_batches():
+    """bench.start_corpus (the timed batches made in worker processes) hands back exactly what making them one after the other does:
+    the packed documents, the oracle sample, and the first batch's strings when asked for."""
+    import bench
+    import tokenizers_amd as ta
+    js, n_types, _ = bench.load_config("c2")
+    got = bench.start_corpus("c2", 3000, 3, 0, n_types, 1, 1, keep_first=True)()
+    assert len(got) == 3
+    for k, (buf, off, sample, lines) in enumerate(got):
+        exp = bench.make_corpus("c2", 3000, 100 + 1 + 1000 * k, 0, n_types)
+        b2, o2 = ta.pack_documents(exp)
+        assert np.array_equal(buf, b2) and np.array_equal(off, o2)
+        assert sample == bench.sample_of(exp, 1)[1]
+        assert lines == (exp if k == 0 else None)
+
+
+def test_bench_dump_outputs_is_a_seeded_sample_of_the_result(tmp_path):
+    """bench.dump_outputs: the whole token CSR, and the ids of a document sample that depends on the document count alone, as float64."""
+    import bench
+
+    class Result:                                       # the two views of a DeviceBatch that dump_outputs reads
+        def __init__(self, ids, to):
+            self._ids, self._to = torch.from_numpy(ids), torch.from_numpy(to)
+
+        def ids_tensor(self):
+            return self._ids
+
+        def tok_offsets_tensor(self):
+            return self._to
+    rng = np.random.default_rng(5)
+    to = np.zeros(20001, dtype=np.int64)
+    np.cumsum(rng.integers(0, 30, size=20000), out=to[1:])
+    ids = rng.integers(-2 ** 31, 2 ** 31, size=int(to[-1])).astype(np.int32)     # int32 views of u32 ids
+    shapes = bench.dump_outputs(str(tmp_path / "a"), Result(ids, to))
+    bench.dump_outputs(str(tmp_path / "b"), Result(ids[::-1].copy(), to))
+    out = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in shapes}
+    assert all(a.dtype == np.float64 and list(a.shape) == shapes[n] for n, a in out.items())
+    assert np.array_equal(out["tok_offsets"], to)
+    docs = out["sample_docs"].astype(np.int64)
+    assert len(docs) == 20000 // 16 and np.all(np.diff(docs) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "sample_docs.npy"), out["sample_docs"])
+    exp = np.concatenate([ids[to[d]:to[d + 1]].view(np.uint32) for d in docs])
+    assert np.array_equal(out["ids_sample"], exp.astype(np.float64))

@@ -19,8 +19,8 @@ TKAMD_TEST_DISTINCT_DEVICES=1 timeout 1200 python -m pytest tests/test_multi_dev
 timeout 1700 python -m pytest tests -m gpu -q -n 8 > "$O/pytest_gpu.txt" 2>&1; echo "gate rc=$?" | tee -a "$O/summary.txt"; tail -2 "$O/pytest_gpu.txt"
 for g in 1 2 4 8; do
   [ "$g" -le "$n" ] || continue
-  if [ "$g" = 1 ]; then timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_n1.json" 2> "$O/bench_n1.log"
-  else timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $g --master-addr 127.0.0.1 --master-port $((29600 + g)) bench.py --gpus $g --steps 20 --warmup 5 > "$O/bench_n$g.json" 2> "$O/bench_n$g.log"; fi
+  if [ "$g" = 1 ]; then timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/bench_n1.json" 2> "$O/bench_n1.log"
+  else timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $g --master-addr 127.0.0.1 --master-port $((29600 + g)) bench.py --gpus $g --steps 20 --warmup 5 --full > "$O/bench_n$g.json" 2> "$O/bench_n$g.log"; fi
   echo "bench --gpus $g rc=$?" | tee -a "$O/summary.txt"
   python - "$O/bench_n$g.json" <<'PY' | tee -a "$O/summary.txt"
 import json, sys

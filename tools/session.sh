@@ -17,7 +17,7 @@
 tag=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/$tag; mkdir -p "$O"
-SHORT="--no-cpu-baseline --no-ood --no-host --no-word-cache --no-single-call --also none"
+SHORT="--full --no-cpu-baseline --no-ood --no-host --no-word-cache --no-single-call --also none"
 for step in "$@"; do
   kind=${step%%:*}; rest=${step#*:}; [ "$rest" = "$step" ] && rest=""
   case $kind in
@@ -26,8 +26,8 @@ for step in "$@"; do
       else timeout 1700 python -m pytest tests -m gpu -q -n 8 > "$O/pytest_gpu.txt" 2>&1; echo "gate rc=$?"; tail -3 "$O/pytest_gpu.txt"; fi ;;
     bench)
       cfg=${rest%%:*}; extra=${rest#*:}; [ "$extra" = "$rest" ] && extra=""; cfg=${cfg:-c2}
-      if [ "$cfg" = c2 ]; then timeout 900 python bench.py $extra > "$O/c2_bench.json" 2> "$O/c2_bench.log"
-      else timeout 400 python bench.py --config $cfg --no-host --no-ood --no-word-cache --no-single-call $extra > "$O/${cfg}_bench.json" 2> "$O/${cfg}_bench.log"; fi
+      if [ "$cfg" = c2 ]; then timeout 900 python bench.py --full $extra > "$O/c2_bench.json" 2> "$O/c2_bench.log"
+      else timeout 400 python bench.py --config $cfg --full --no-host --no-ood --no-word-cache --no-single-call $extra > "$O/${cfg}_bench.json" 2> "$O/${cfg}_bench.log"; fi
       echo "bench $cfg rc=$?"; head -c 300 "$O/${cfg}_bench.json"; echo ;;
     stats)
       c=$rest
