@@ -94,6 +94,7 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
     if (!(flags & TKAMD_PAIRS) && hm.pp_single_refused) throw Unsupported("post_processor: " + hm.pp_unsupported);
     if (mixed && (flags & TKAMD_ADD_SPECIAL) && !hm.pp_pair_unsupported.empty()) throw Unsupported("add_special_tokens on a pair: " + hm.pp_pair_unsupported);
     const bool prefix_space = hm.byte_level && hm.add_prefix_space;
+    const bool metaspace = hm.pretok == PT_METASPACE;     // the "▁" front: X = the "▁" text (kernels/metaspace.hip)
     // host-side bound of the X text length: +1 per document for the virtual space; BertNormalizer can grow a
     // character (CJK spacing: 3 -> 5 bytes, NFD/lowercase expansions <= 3x) -- 3x the input covers every case
     // added-token matches of a batch: at most one per min_len bytes (the shortest pattern)
@@ -103,15 +104,18 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
     const bool have_added_tokens = at_min_len != (size_t)-1;
     const uint32_t mcap = have_added_tokens ? (uint32_t)std::min<size_t>((size_t)n_bytes / std::max<size_t>(at_min_len, 1) + 16, 0x7FFFFFF0u) : 0u;
     // (a prefix space goes in front of every piece: every document, and what follows every match)
-    const int64_t n_x = (hm.norm == NORM_BERT) ? 3 * n_bytes + 64 : n_bytes + (prefix_space ? n_docs + (int64_t)mcap : 0);
+    // (the "▁" front: a ' ' becomes three bytes, and a "▁" of three goes in front of a piece -- every document, and what follows every match)
+    const int64_t n_x = (hm.norm == NORM_BERT) ? 3 * n_bytes + 64
+                        : metaspace ? 3 * n_bytes + 3 * (n_docs + 2 * (int64_t)mcap + 1) + 64
+                        : n_bytes + (prefix_space ? n_docs + (int64_t)mcap : 0);
     if (n_x >= (int64_t)0xFFFFFF00ll) throw Invalid("batch larger than 4 GiB: split it (byte offsets are 32-bit on the device)");
     const bool bpe_path = hm.model == MODEL_BPE && !hm.char_bpe && (hm.pretok == PT_BYTELEVEL_GPT2 || hm.pretok == PT_LLAMA3 || hm.pretok == PT_BYTELEVEL_NOREGEX);
     const bool local_pretok = hm.pretok == PT_WHITESPACE || hm.pretok == PT_WHITESPACE_SPLIT || hm.pretok == PT_BERT;
     const bool word_models = (hm.model == MODEL_WORDLEVEL || hm.model == MODEL_WORDPIECE) && local_pretok;
-    const bool char_bpe = hm.model == MODEL_BPE && hm.char_bpe && local_pretok;      // BPE over characters rides the word models' pre-tokenizers
+    const bool char_bpe = hm.model == MODEL_BPE && hm.char_bpe && (local_pretok || metaspace);      // BPE over characters rides the word models' pre-tokenizers, or the "▁" front
     if (!bpe_path && !word_models && !char_bpe)
         throw Unsupported("this build covers {ByteLevel(GPT-2 regex), Llama-3 Split+ByteLevel, ByteLevel(no regex)}+BPE and "
-                          "{Whitespace,WhitespaceSplit,BertPreTokenizer}+{WordLevel,WordPiece,BPE over characters}");
+                          "{Whitespace,WhitespaceSplit,BertPreTokenizer}+{WordLevel,WordPiece,BPE over characters} and the U+2581 front+BPE over characters");
     if (prefix_space && hm.norm != NORM_NONE) throw Unsupported("ByteLevel add_prefix_space behind a normalizer");
 
     reserve_workspace(t, w, n_x, n_docs, flags, want_meta);
@@ -151,7 +155,7 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
         z.add(sc, SC_SLOTS * 8);
         // (behind BertNormalizer the mask covers the bound of the normalised text, three times the input: the words that text really has
         // are zeroed behind the normaliser, next to the slack of the text -- launch_zero_tail below)
-        if (!(len_bound && hm.norm == NORM_BERT)) z.add(w->w_docmask.p, (size_t)(W + 1) * 8);
+        if (!(len_bound && (hm.norm == NORM_BERT || metaspace))) z.add(w->w_docmask.p, (size_t)(W + 1) * 8);
         z.add(w->w_qcount.p, (size_t)QCNT_WORDS * 4);
         z.add(w->w_cstate.p, cstate_bytes);
         if (hm.pretok == PT_LLAMA3 && split_rule_fast(hm.split_rule)) {
@@ -690,12 +694,12 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
     const int64_t* x_len_dev = nullptr;
     const uint32_t* norig = nullptr;
     const uint32_t* norig_e = nullptr;
-    if (hm.norm == NORM_BERT || prefix_space) {
+    if (hm.norm == NORM_BERT || prefix_space || metaspace) {
         w->w_ntext.reserve((size_t)n_x + TKAMD_TEXT_PAD);
         w->w_ndoc_off.reserve((size_t)(n_docs + 2) * 8);
         // (the prefix-space copy leaves nothing unwritten either, but only the normaliser's path has been taken through the tests without
         // this memset: k_zero_tail behind launch_bert_normalize zeroes the slack behind the text it wrote)
-        if (hm.norm != NORM_BERT) HIP_CHECK(hipMemsetAsync(w->w_ntext.p, 0, (size_t)n_x + TKAMD_TEXT_PAD, st));
+        if (hm.norm != NORM_BERT && !metaspace) HIP_CHECK(hipMemsetAsync(w->w_ntext.p, 0, (size_t)n_x + TKAMD_TEXT_PAD, st));
         // test hook TKAMD_POISON_NTEXT (with TKAMD_TEST_HOOKS=1): the normaliser's output buffer starts every batch as 0xFF, so a kernel that
         // reads it beyond *x_len + TEXT_PAD -- bounded by the host's n_x instead of the device length -- changes a result instead of
         // meeting zeros an earlier batch or the allocator happened to leave (tests/test_parity_gpu.py runs the BertNormalizer fixtures so)
@@ -713,7 +717,7 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
             norig = w->w_norig.as<uint32_t>();
             // (behind BertNormalizer the END of a byte's original range follows from its start and the original text -- kernels/output.hip
             // norig_end: 4 bytes per normalised byte less to write and to read; the prefix-space copy keeps per-byte ends)
-            if (hm.norm != NORM_BERT) {
+            if (hm.norm != NORM_BERT && !metaspace) {
                 w->w_norig_e.reserve(((size_t)n_x + 4) * 4);
                 norig_e = w->w_norig_e.as<uint32_t>();
             }
@@ -769,7 +773,7 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
                            hm.norm == NORM_NONE ? MATCH_LEN_ORIG : 0u, d_err);
         pf.end();
     }
-    if (have_added && !prefix_space) {
+    if (have_added && !prefix_space && !metaspace) {
         scatter_masks(n_in, x_len_dev, off_mode != TKAMD_OFFSETS_NONE);
         matchmask = w->w_matchmask.as<ull>();
     }
@@ -807,6 +811,35 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
             matchmask = w->w_matchmask.as<ull>();
             piece_off = xseg;
             piece_n_dev = d_nseg;
+        }
+    } else if (metaspace) {
+        // ---- the "▁" front: the raw text's pieces (documents, and what lies between added-token matches) -> the "▁" text X + the original
+        // byte of every X byte; the matches are copied as they are and move into X coordinates like the normaliser's (kernels/metaspace.hip) ----
+        w->w_ms_dmask.reserve((size_t)(W0 + 2) * 8);
+        HIP_CHECK(hipMemsetAsync(w->w_ms_dmask.p, 0, (size_t)(W0 + 2) * 8, st));
+        launch_mark_doc_starts_n(st, d_doc_off, n_docs, n_bytes, nullptr, w->w_ms_dmask.as<ull>(), d_err);
+        const ull* pstart = w->w_ms_dmask.as<ull>();
+        if (have_added) {
+            scatter_masks(n_bytes, nullptr, false);
+            build_pieces(d_doc_off, n_bytes, nullptr);
+            pstart = w->w_boundmask.as<ull>();
+        }
+        w->w_keepmask.reserve(bn_olen_bytes(n_bytes));          // output bytes per source byte (kernels.hpp bn_olen_bytes)
+        w->w_kprefix.reserve((size_t)(W0 + 1) * 4);
+        w->w_wbase.reserve((size_t)(W0 + 1) * 4);
+        pf.begin("metaspace");
+        launch_metaspace(st, d_text, n_bytes, d_doc_off, n_docs, pstart, w->w_ms_dmask.as<ull>(), have_added ? w->w_matchmask.as<ull>() : nullptr,
+                         have_added ? w->w_spanmask.as<ull>() : nullptr, (uint32_t)hm.ms_prepend, w->w_keepmask.as<uint8_t>(), w->w_kprefix.as<uint32_t>(),
+                         w->w_bsum.as<uint32_t>(), w->w_wbase.as<uint32_t>(), d_xlen, w->w_ntext.as<uint8_t>(), (uint32_t*)norig, w->w_ndoc_off.as<int64_t>());
+        launch_zero_tail(st, w->w_ntext.as<uint8_t>(), d_xlen, TKAMD_TEXT_PAD, len_bound ? w->w_docmask.as<ull>() : nullptr, W + 1, t->n_cu * 4);
+        pf.end();
+        if (have_added) launch_translate_matches_norm(st, mlist, n_match, w->w_keepmask.as<uint8_t>(), w->w_wbase.as<uint32_t>(), n_bytes, d_xlen);
+        x_text = w->w_ntext.as<uint8_t>();
+        x_doc_off = w->w_ndoc_off.as<int64_t>();
+        x_len_dev = d_xlen;
+        if (have_added) {
+            scatter_masks(n_x, x_len_dev, off_mode != TKAMD_OFFSETS_NONE);
+            matchmask = w->w_matchmask.as<ull>();
         }
     } else if (have_added && hm.pretok == PT_LLAMA3) {
         piece_off = build_pieces(x_doc_off, n_in, x_len_dev);
@@ -861,6 +894,11 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
                              t->t_ucc1.p ? t->t_ucc1.as<uint16_t>() : nullptr, t->t_ucc2.p ? t->t_ucc2.as<uint8_t>() : nullptr,
                              w->w_l3_tiles.p ? w->w_l3_tiles.as<ull>() : nullptr, lead_done ? w->w_leadmask.as<ull>() : nullptr);
         pf.end();
+    } else if (metaspace) {
+        // every piece start (the document mask holds the match edges now) and every "▁" behind another char (or every "▁": split)
+        pf.begin("metaspace_units");
+        launch_ms_units(st, x_text, n_x, x_len_dev, w->w_docmask.as<ull>(), w->w_startmask.as<ull>(), W, hm.ms_split);
+        pf.end();
     } else if (hm.pretok == PT_BYTELEVEL_NOREGEX) {
         // ByteLevel(use_regex=false): every document is one pre-token (byte_level.rs:128-130)
         HIP_CHECK(hipMemcpyAsync(w->w_startmask.p, w->w_docmask.p, (size_t)W * 8, hipMemcpyDeviceToDevice, st));
@@ -889,6 +927,20 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
                          meta_masks ? w->w_tile_w.as<uint32_t>() : nullptr);
         pf.end();
         after_masks();
+    }
+
+    // the "▁" front over whole pieces: a word id is the index of the pre-token's PIECE in its document, not of the unit (the piece starts are
+    // the document mask's bits by now: documents + match edges)
+    const uint32_t* pt_word = nullptr;
+    if (metaspace && !hm.ms_split && want_words && !words_in) {
+        w->w_pprefix.reserve((size_t)(W + 2) * 4);
+        w->w_pt_word.reserve(((size_t)n_x + 4) * 4);
+        pf.begin("metaspace_words");
+        launch_mask_scan(st, w->w_docmask.as<ull>(), W, w->w_bsum.as<uint32_t>(), w->w_pprefix.as<uint32_t>(), sc + SC_NPIECE, len_bound ? x_len_dev : nullptr);
+        launch_ms_piece_rank(st, w->w_startmask.as<ull>(), w->w_wprefix.as<uint32_t>(), w->w_docmask.as<ull>(), w->w_pprefix.as<uint32_t>(), n_x, x_len_dev,
+                             w->w_pt_word.as<uint32_t>());
+        pf.end();
+        pt_word = w->w_pt_word.as<uint32_t>();
     }
 
     uint32_t* tmp_end = (off_mode != TKAMD_OFFSETS_NONE) ? w->w_tmp_end.as<uint32_t>() : nullptr;
@@ -969,10 +1021,19 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
         // BPE over characters: only the kernels that know its start (kernels/bpe.hip CHARS) -- the two LDS kernels, each on its own queue,
         // and the workgroup-per-pre-token kernel for everything beyond 32 bytes (or for everything, when the vocabulary's new ids are not
         // in merge order and the LDS kernels cannot run)
-        if (hm.char_bpe) {
-            mdt.thin_limit = 0u;                           // (each queue has its one kernel here)
+        // pre-tokens beyond the LDS path (> 8192 B) run from a global scratch slab: 5 words per symbol, sized for the worst case this batch
+        // can contain (the whole X text being such pre-tokens), capped at 1 GiB
+        const size_t huge_words = std::min<size_t>((size_t)6 * N + 4096, (size_t)1 << 28);
+        const bool huge_possible = N > (size_t)LONG_PT_MAX;
+        if (huge_possible) {
+            w->w_huge.reserve(huge_words * 4);
+            w->w_list_huge.reserve((N / LONG_PT_MAX + 16) * 4);
+        } else {
             w->w_huge.reserve(64);
             w->w_list_huge.reserve(64);
+        }
+        if (hm.char_bpe) {
+            mdt.thin_limit = 0u;                           // (each queue has its one kernel here)
             auto long_only = [&](const QView& q) {
                 launch_bpe_merge_long_only(st, t->n_cu * 2, mdt, x_text, q, w->w_rows.p, w->w_tmp_ids.as<uint32_t>(), tmp_end, w->w_list_huge.as<uint32_t>(), d_counters + CNT_LISTH);
             };
@@ -986,7 +1047,10 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
             pf.end();
             pf.begin("bpe_merge_long");
             long_only(plan.v[2]);
-            long_only(plan.v[3]);
+            // (the longest queue's pre-tokens beyond 8 KB -- a CJK paragraph is one unit behind the "▁" front -- go on to k_bpe_merge_huge)
+            launch_bpe_merge_long(st, t->n_cu, mdt, x_text, plan.v[3], w->w_rows.p, w->w_tmp_ids.as<uint32_t>(), tmp_end, w->w_list_huge.as<uint32_t>(),
+                                  d_counters + CNT_LISTH, w->w_huge.as<uint32_t>(), (unsigned long long)(huge_possible ? huge_words : 0),
+                                  (unsigned long long*)(sc + SC_HUGE_USED), d_err);
             pf.end();
         } else {
         pf.begin(lds32 ? "bpe_merge_lds32" : "bpe_merge_lane32");
@@ -1001,19 +1065,9 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
         launch_bpe_merge(st, grid, 64, mdt, x_text, plan.v[2], w->w_rows.p, w->w_tmp_ids.as<uint32_t>(), tmp_end);
         pf.end();
         pf.begin("bpe_merge_long");
-        // pre-tokens beyond the LDS path (> 8192 B) run from a global scratch slab: 5 words per symbol, sized for the
-        // worst case this batch can contain (the whole X text being such pre-tokens), capped at 1 GiB
-        const size_t huge_words = std::min<size_t>((size_t)6 * N + 4096, (size_t)1 << 28);
-        if (N > (size_t)LONG_PT_MAX) {
-            w->w_huge.reserve(huge_words * 4);
-            w->w_list_huge.reserve((N / LONG_PT_MAX + 16) * 4);
-        } else {
-            w->w_huge.reserve(64);
-            w->w_list_huge.reserve(64);
-        }
         launch_bpe_merge_long(st, t->n_cu, mdt, x_text, plan.v[3], w->w_rows.p,
                               w->w_tmp_ids.as<uint32_t>(), tmp_end, w->w_list_huge.as<uint32_t>(), d_counters + CNT_LISTH, w->w_huge.as<uint32_t>(),
-                              (unsigned long long)(N > (size_t)LONG_PT_MAX ? huge_words : 0), (unsigned long long*)(sc + SC_HUGE_USED), d_err);
+                              (unsigned long long)(huge_possible ? huge_words : 0), (unsigned long long*)(sc + SC_HUGE_USED), d_err);
         pf.end();
         }
         if (wc.keys) {
@@ -1078,6 +1132,7 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
     if (want_meta) {
         MetaArgs a{};
         a.word_of_doc = word_of_doc;
+        a.pt_word = pt_word;
         a.first_tok = first_tok;
         a.x_text = x_text;
         a.text = d_text;

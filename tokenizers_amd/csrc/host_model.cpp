@@ -411,9 +411,33 @@ bool parse_split_pattern(const std::string& rx, SplitRule* rule, bool* gpt2, std
     return true;
 }
 
+const char* const kMetaspace = "\xE2\x96\x81";     // U+2581, the "▁" of SentencePiece
+
 PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
-    if (!pt || pt->is_null()) throw Unsupported("pre_tokenizer: null is outside the hot path");
+    if (!pt || pt->is_null()) {
+        // the "▁" normalizers leave every piece ONE pre-token (the device cuts it into units: the model check below proves that exact)
+        if (m.norm == NORM_METASPACE) return PT_METASPACE;
+        throw Unsupported("pre_tokenizer: null is outside the hot path");
+    }
     std::string type = pt->get_str("type");
+    // (the U+2581 normalizers are the front of SentencePiece conversions: in front of any pre-tokenizer but none they are outside the path)
+    if (m.norm == NORM_METASPACE && type != "Metaspace")
+        throw Unsupported("normalizer: the U+2581 normalizers (Prepend / Replace ' ' -> U+2581) in front of pre_tokenizer '" + type +
+                          "' are outside the hot path (only with a null pre_tokenizer)");
+    if (type == "Metaspace") {
+        // pre_tokenizers/metaspace.rs:34-77 (deserialisation: split defaults to true, the legacy add_prefix_space = false means "never")
+        if (m.norm != NORM_NONE) throw Unsupported("pre_tokenizer: Metaspace behind a normalizer");
+        const std::string rep = pt->get_str("replacement");
+        if (rep != kMetaspace) throw Unsupported("pre_tokenizer: Metaspace with replacement '" + rep + "' (only U+2581 is on the path)");
+        const JsonValue* ps = pt->get("prepend_scheme");
+        std::string scheme = (ps && ps->is_string()) ? ps->str : (pt->get_bool("add_prefix_space", true) ? "always" : "never");
+        if (scheme == "always") m.ms_prepend = MS_ALWAYS;
+        else if (scheme == "first") m.ms_prepend = MS_FIRST;
+        else if (scheme == "never") m.ms_prepend = MS_NEVER;
+        else throw Invalid("tokenizer.json: Metaspace prepend_scheme '" + scheme + "'");
+        m.ms_split = pt->get_bool("split", true);
+        return PT_METASPACE;
+    }
     if (type == "ByteLevel") {
         m.byte_level = true;
         m.add_prefix_space = pt->get_bool("add_prefix_space", true);
@@ -761,6 +785,28 @@ HostModel HostModel::from_json(const char* json, size_t len) {
             m.bn_lowercase = norm->get_bool("lowercase", true);
             const JsonValue* sa = norm->get("strip_accents");
             m.bn_strip_accents = (sa && sa->is_bool()) ? sa->b : m.bn_lowercase;  // normalizers/bert.rs:124
+        } else if (t == "Sequence" || t == "Replace" || t == "Prepend") {
+            // the "▁" normalizers of SentencePiece conversions: Sequence[Prepend("▁"), Replace(" " -> "▁")] (Llama-2, Mistral) or
+            // Replace(" " -> "▁") alone (Gemma-style); anything else of these types is outside the path
+            auto is_replace = [](const JsonValue* r) {
+                if (!r || r->get_str("type") != "Replace") return false;
+                const JsonValue* pat = r->get("pattern");
+                if (!pat || !pat->is_object() || !pat->get("String")) throw Unsupported("normalizer: Replace with a Regex pattern");
+                if (pat->get_str("String") != " ") throw Unsupported("normalizer: Replace of '" + pat->get_str("String") + "' (only ' ' -> U+2581 is on the path)");
+                if (r->get_str("content") != kMetaspace) throw Unsupported("normalizer: Replace with '" + r->get_str("content") + "' (only ' ' -> U+2581 is on the path)");
+                return true;
+            };
+            auto is_prepend = [](const JsonValue* r) {
+                if (!r || r->get_str("type") != "Prepend") return false;
+                if (r->get_str("prepend") != kMetaspace) throw Unsupported("normalizer: Prepend of '" + r->get_str("prepend") + "' (only U+2581 is on the path)");
+                return true;
+            };
+            const JsonValue* seq = t == "Sequence" ? norm->get("normalizers") : nullptr;
+            if (t == "Replace" && is_replace(norm)) m.ms_prepend = MS_NEVER;
+            else if (seq && seq->is_array() && seq->arr.size() == 2 && is_prepend(seq->arr[0].get()) && is_replace(seq->arr[1].get())) m.ms_prepend = MS_PIECE;
+            else throw Unsupported("normalizer: this " + t + " is outside the hot path (only Sequence[Prepend(U+2581), Replace(' ' -> U+2581)] and "
+                                   "Replace(' ' -> U+2581) are)");
+            m.norm = NORM_METASPACE;
         } else {
             throw Unsupported("normalizer: type '" + t + "' is outside the hot path");
         }
@@ -1093,6 +1139,11 @@ HostModel HostModel::from_json(const char* json, size_t len) {
             auto ia = v.find(a), ib = v.find(b), in = v.find(a + b.substr(m.bpe_prefix.size()));
             if (ia == v.end() || ib == v.end() || in == v.end())
                 throw Invalid("tokenizer.json: merge token out of vocabulary (MergeTokenOutOfVocabulary)");
+            // the "▁" front's unit split (PT_METASPACE without split): exact only if no merge joins a char other than "▁" to a symbol that
+            // starts with "▁" -- then no pair across a cut ever merges, and every unit runs its merges on its own (bpe/word.rs:162-250)
+            if (m.pretok == PT_METASPACE && !m.ms_split && m.char_bpe && b.compare(0, 3, kMetaspace) == 0 && !(a.size() >= 3 && a.compare(a.size() - 3, 3, kMetaspace) == 0))
+                throw Unsupported("pre_tokenizer: the merge ('" + a + "', '" + b + "') joins a char other than U+2581 to a U+2581: whole-piece BPE "
+                                  "(no split at U+2581) is outside the hot path for this vocabulary");
             mm[((uint64_t)ia->second << 32) | ib->second] = {rank, in->second};
             ++rank;
         }
@@ -1120,6 +1171,21 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     } else {
         throw Unsupported("model: type '" + mtype + "' is outside the hot path");
     }
+    if (m.pretok == PT_METASPACE) {
+        if (m.model != MODEL_BPE || !m.char_bpe)
+            throw Unsupported("pre_tokenizer: the U+2581 front (Metaspace, or null behind the U+2581 normalizers) is only on the path in front of BPE over characters");
+        if (!m.bpe_prefix.empty() || !m.bpe_suffix.empty())
+            throw Unsupported("pre_tokenizer: the U+2581 front with continuing_subword_prefix / end_of_word_suffix");
+        if (!m.ms_split) {
+            // (the device cuts every piece at each U+2581 behind another char: exact by the merge check above, if the vocabulary has the U+2581
+            // symbol itself -- and not for ignore_merges, whose whole-word lookup is of the whole piece)
+            if (m.ignore_merges) throw Unsupported("pre_tokenizer: ignore_merges over whole pieces (no split at U+2581) is outside the hot path");
+            if (v.find(kMetaspace) == v.end()) throw Unsupported("pre_tokenizer: whole-piece BPE (no split at U+2581) with a vocabulary that lacks U+2581 is outside the hot path");
+        }
+    }
+    if (m.norm == NORM_METASPACE)
+        for (const AddedToken& a : m.added_tokens)
+            if (a.normalized) throw Unsupported("added token '" + a.content + "' is normalized = true behind the U+2581 normalizer (matched on the normalized text: not on the path)");
 
     // BPE over characters with an end_of_word_suffix: the vocabulary entry of a WHOLE word carries the suffix its text does not.  The
     // whole-word table (below) is keyed by text: the merge-stable shortcut's candidates are the entries minus their suffix (an entry

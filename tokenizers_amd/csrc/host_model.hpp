@@ -58,6 +58,11 @@ struct HostModel {
     // BertNormalizer options (normalizers/bert.rs:62-90)
     bool bn_clean_text = true, bn_handle_chinese = true, bn_strip_accents = true, bn_lowercase = true;
 
+    // the "▁" front (PT_METASPACE): where a piece gets its "▁" (tables.hpp MsPrepend), and whether every "▁" starts a pre-token
+    // (Metaspace split = true) or the device cuts a piece into units at every "▁" behind a char other than "▁" (proved exact at load)
+    MsPrepend ms_prepend = MS_NEVER;
+    bool ms_split = false;
+
     // model options
     bool ignore_merges = false;
     bool has_unk = false;

@@ -4,6 +4,7 @@
 //
 //   text bytes ──documents─────► doc-start bitmask (+ added-token matches, prefix space)          kernels/documents.hip
 //        │──────bert_norm──────► normalised text X (BertNormalizer)                               kernels/bert_norm.hip
+//        │──────metaspace──────► "▁" text X + its pre-token starts (SentencePiece-style BPE)        kernels/metaspace.hip
 //        │──────pretok_*───────► pre-token start (/ end) bitmask: per-lane 64-bit mask algebra    kernels/pretok_{gpt2,llama3,local}.hip
 //        │──────scan_emit──────► pt_start[P+1]   (byte offset of every pre-token = "split")       kernels/scan_emit.hip
 //        │──────lookup─────────► straight from the bitmasks: whole-word hit -> 1 token (LDS hot    kernels/lookup.hip
@@ -79,6 +80,7 @@ static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)(
 #include "kernels/pretok_llama3.hip"
 #include "kernels/pretok_local.hip"
 #include "kernels/bert_norm.hip"
+#include "kernels/metaspace.hip"
 #include "kernels/scan_emit.hip"
 #include "kernels/bpe.hip"
 #include "kernels/lookup.hip"

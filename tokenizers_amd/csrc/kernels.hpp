@@ -133,6 +133,7 @@ struct MetaArgs {
     const uint32_t* chunk_lo;         // the compaction's: chunk_lo[c] = the first document d with doc_pt[d] >= c * chunk (k_doc_first_pretok)
     uint32_t chunk;
     const uint32_t* word_of_doc;      // is_pretokenized: word id of every token of document d (its index in the sequence); else null
+    const uint32_t* pt_word;          // the "▁" front over whole pieces: the piece rank of every pre-token (word id = rank - its document's first); else null
     const int64_t* first_tok;         // is_pretokenized with trim_offsets: index of the first token of document d's sequence; else null
     int64_t n_docs;
     const int64_t* x_doc_off;         // document CSR in x space
@@ -401,6 +402,13 @@ void launch_scatter_matches(hipStream_t st, const uint32_t* list, const uint32_t
                             unsigned long long* spanmask, unsigned long long* stopmask, unsigned long long* hardmask, uint32_t* tmp_end, uint32_t* dirty);
 void launch_mask_or2(hipStream_t st, unsigned long long* dst, const unsigned long long* a, const unsigned long long* b, int64_t n_words);
 void launch_emit_boundaries(hipStream_t st, const unsigned long long* mask, const uint32_t* wprefix, int64_t n_bytes, const int64_t* len_dev, const int64_t* total, int64_t* out);
+void launch_metaspace(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* doc_off, int64_t n_docs, const unsigned long long* pstart,
+                      const unsigned long long* dstart, const unsigned long long* mmask, const unsigned long long* smask, uint32_t prepend, uint8_t* olen,
+                      uint32_t* wsum, uint32_t* bsum, uint32_t* wbase, int64_t* x_len, uint8_t* xtext, uint32_t* nos, int64_t* xdoc_off);
+void launch_ms_units(hipStream_t st, const uint8_t* xtext, int64_t n_x, const int64_t* x_len, const unsigned long long* pmask, unsigned long long* startmask,
+                     int64_t n_words, bool split);
+void launch_ms_piece_rank(hipStream_t st, const unsigned long long* startmask, const uint32_t* wprefix, const unsigned long long* pmask, const uint32_t* pprefix,
+                          int64_t n_x, const int64_t* x_len, uint32_t* pt_word);
 void launch_translate_matches_norm(hipStream_t st, uint32_t* list, const uint32_t* n_list, const uint8_t* olen, const uint32_t* wbase, int64_t n_bytes, const int64_t* x_len);
 void launch_translate_matches_prefix(hipStream_t st, uint32_t* list, const uint32_t* n_list, const unsigned long long* bmask, const uint32_t* wprefix, int64_t n_bytes,
                                      const int64_t* len_dev, const int64_t* total, const int64_t* xseg_off);

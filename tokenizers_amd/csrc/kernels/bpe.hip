@@ -685,13 +685,7 @@ __global__ __launch_bounds__(256) void k_bpe_merge_long(DevTables t, const uint8
         const uint32_t s = it.s, len = qitem_len(it.len);
         if (len == 0u) continue;                           // retired by k_long_vocab
         if (len > (uint32_t)LONG_PT_MAX) {                 // too long for LDS: hand over to k_bpe_merge_huge (by queue position)
-            if (tid == 0) {
-                if (t.cb & CB_ON) atomicOr(t.err, ERR_PRETOKEN_TOO_LONG);      // (BPE over characters: no global-scratch variant -- a "word" of more than 8 KB)
-                else list_huge[atomicAdd(n_huge, 1u)] = pos;
-            }
-            if (t.cb & CB_ON) {                            // (uniform) an empty row keeps the compaction well defined until the error is reported
-                if (tid == 0) rows[v.row_base + pos] = make_uint4(ROW_CNT_MORE << ROW_CNT_SHIFT, s, 0u, 0u);
-            }
+            if (tid == 0) list_huge[atomicAdd(n_huge, 1u)] = pos;      // (byte-level and BPE over characters alike)
             continue;
         }
         __syncthreads();

@@ -3,7 +3,7 @@
 
 // =================================================================================================
 // K_bpe_merge_huge: pre-tokens longer than LONG_PT_MAX bytes (e.g. a 1 MB run of letters).  One workgroup per
-// pre-token, the Symbol list (c, prev, next) and the cached pair ranks live in a global scratch slab, and the
+// pre-token (byte-level, or BPE over characters with k_bpe_merge_long's per-character start), the Symbol list (c, prev, next) and the cached pair ranks live in a global scratch slab, and the
 // heap of models/bpe/word.rs:163-180 becomes a two-level minimum: one (rank, pos) minimum per 64-symbol chunk,
 // reduced across the workgroup every round; a merge recomputes at most three chunk minima.  Rounds cost
 // O(len / 16384 + 64) loads per lane, so a 1 MB word finishes in seconds instead of O(len^2).
@@ -53,15 +53,61 @@ __global__ __launch_bounds__(256) void k_bpe_merge_huge(DevTables t, const uint8
         uint32_t* nxt = nid + len;
         uint32_t* prv = nxt + len;
         unsigned long long* cmin = (unsigned long long*)(prv + len + ((base_s + 5ull * len) & 1ull));   // 8-byte aligned
-        for (uint32_t i = tid; i < len; i += 256) {
-            sym[i] = t.byte_id[text[s + i]];
-            nxt[i] = (i + 1 < len) ? i + 1 : 0xFFFFFFFFu;
-            prv[i] = (i > 0) ? i - 1 : 0xFFFFFFFFu;
+        if (!(t.cb & CB_ON)) {                                       // (uniform) byte-level: a symbol per byte
+            for (uint32_t i = tid; i < len; i += 256) {
+                sym[i] = t.byte_id[text[s + i]];
+                nxt[i] = (i + 1 < len) ? i + 1 : 0xFFFFFFFFu;
+                prv[i] = (i > 0) ? i - 1 : 0xFFFFFFFFu;
+            }
+        } else {
+            // BPE over characters: k_bpe_merge_long's start (merge_word, bpe/model.rs:465-550) -- every lead byte asks for its char's entry in
+            // parallel (parked in nid[]), then ONE thread links up what stands where: an unknown char's fate (its own unk symbol, part of the
+            // previous one, its bytes' tokens, nothing) depends on the char before it
+            for (uint32_t i = tid; i < len; i += 256) {
+                const uint32_t b0 = text[s + i];
+                uint32_t own = CHAR_NONE;
+                if ((b0 & 0xC0u) != 0x80u) {
+                    const uint32_t cl = b0 < 0x80u ? 1u : b0 < 0xE0u ? 2u : b0 < 0xF0u ? 3u : 4u;
+                    uint32_t cp = b0 < 0x80u ? b0 : b0 < 0xE0u ? (b0 & 0x1Fu) : b0 < 0xF0u ? (b0 & 0x0Fu) : (b0 & 0x07u);
+                    for (uint32_t q = 1; q < cl; ++q) cp = (cp << 6) | (i + q < len ? (text[s + i + q] & 0x3Fu) : 0u);
+                    const uint32_t var = ((i != 0 && (t.cb & CB_PREFIX)) ? 1u : 0u) | ((i + cl >= len && (t.cb & CB_SUFFIX)) ? 2u : 0u);
+                    if (cp < 0x110000u) own = t.char_id[(cp << 2) | var];
+                }
+                nid[i] = own;
+                sym[i] = 0xFFFFFFFFu;                                // nothing stands here (yet)
+                nxt[i] = prv[i] = 0xFFFFFFFFu;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                bool unknown = false, prev_unk = false;
+                uint32_t last = 0xFFFFFFFFu;
+                for (uint32_t i = 0; i < len; ++i) {
+                    const uint32_t b0 = text[s + i];
+                    const bool lead = (b0 & 0xC0u) != 0x80u;
+                    if (lead) unknown = nid[i] == CHAR_NONE;
+                    uint32_t id = 0xFFFFFFFFu;
+                    if (!unknown) { if (lead) { id = nid[i]; prev_unk = false; } }
+                    else if (t.cb & CB_BYTES) { id = t.byte_id[b0]; prev_unk = false; }
+                    else if (lead) {
+                        if (t.cb & CB_UNK) {
+                            if (!(prev_unk && (t.cb & CB_FUSE))) id = t.unk_id;
+                            prev_unk = true;
+                        } else if (t.cb & CB_UNK_MISSING) atomicOr(err, ERR_UNK_OOV);
+                    }
+                    if (id != 0xFFFFFFFFu) {
+                        sym[i] = id;
+                        prv[i] = last;
+                        if (last != 0xFFFFFFFFu) nxt[last] = i;
+                        last = i;
+                    }
+                }
+            }
         }
         __syncthreads();
         for (uint32_t i = tid; i < len; i += 256) {
             uint32_t r = RANK_NONE, ni = 0;
-            if (i + 1 < len) merge_probe(t, sym[i], sym[i + 1], &r, &ni);
+            const uint32_t j = nxt[i];
+            if (sym[i] != 0xFFFFFFFFu && j != 0xFFFFFFFFu) merge_probe(t, sym[i], sym[j], &r, &ni);
             rnk[i] = r;
             nid[i] = ni;
         }
@@ -130,6 +176,6 @@ __global__ __launch_bounds__(256) void k_bpe_merge_huge(DevTables t, const uint8
             if (tid == 0) cnt_s += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
             __syncthreads();
         }
-        if (tid == 0) rows[row_base + p] = make_uint4(first_s | (ROW_CNT_MORE << ROW_CNT_SHIFT), s, cnt_s, 0u);
+        if (tid == 0) rows[row_base + p] = make_uint4((cnt_s ? first_s : 0u) | (ROW_CNT_MORE << ROW_CNT_SHIFT), s, cnt_s, 0u);
     }
 }

@@ -130,6 +130,31 @@ void launch_bert_normalize(hipStream_t st, const BnTables& bt, const uint8_t* te
     hipLaunchKernelGGL(k_bn_doc_offsets, dim3(blocks_for(n_docs + 1, 256)), dim3(256), 0, st, doc_off, n_docs, n_bytes, ol,
                        (const uint32_t*)wbase, (const int64_t*)x_len, ndoc_off);
 }
+// the "▁" front (kernels/metaspace.hip): count -> scan of the 64-byte words -> write, then the document CSR in X (the BertNormalizer's)
+void launch_metaspace(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* doc_off, int64_t n_docs, const unsigned long long* pstart,
+                      const unsigned long long* dstart, const unsigned long long* mmask, const unsigned long long* smask, uint32_t prepend, uint8_t* olen,
+                      uint32_t* wsum, uint32_t* bsum, uint32_t* wbase, int64_t* x_len, uint8_t* xtext, uint32_t* nos, int64_t* xdoc_off) {
+    const int64_t n_words = (n_bytes >> 6) + 1;
+    uint8_t* const ltot = bn_ltot_of(olen, n_bytes);
+    const BnOlen ol{olen, ltot};
+    const MsArgs a{text, n_bytes, pstart, dstart, mmask, smask, prepend};
+    hipLaunchKernelGGL(k_ms_count, dim3(blocks_for(n_bytes + 1, 256 * BN_LANE)), dim3(256), 0, st, a, olen, ltot, wsum);
+    unsigned nb = blocks_for(n_words, 256);
+    hipLaunchKernelGGL(k_u32_reduce, dim3(nb), dim3(256), 0, st, (const uint32_t*)wsum, n_words, bsum);
+    hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, st, bsum, (int64_t)nb, (const int64_t*)nullptr, (int64_t)1, x_len);
+    hipLaunchKernelGGL(k_u32_down, dim3(nb), dim3(256), 0, st, (const uint32_t*)wsum, n_words, (const uint32_t*)bsum, wbase);
+    hipLaunchKernelGGL(k_ms_write, dim3(blocks_for(n_bytes, 256 * BN_LANE)), dim3(256), 0, st, a, ol, (const uint32_t*)wbase, xtext, nos);
+    hipLaunchKernelGGL(k_bn_doc_offsets, dim3(blocks_for(n_docs + 1, 256)), dim3(256), 0, st, doc_off, n_docs, n_bytes, ol,
+                       (const uint32_t*)wbase, (const int64_t*)x_len, xdoc_off);
+}
+void launch_ms_units(hipStream_t st, const uint8_t* xtext, int64_t n_x, const int64_t* x_len, const unsigned long long* pmask, unsigned long long* startmask,
+                     int64_t n_words, bool split) {
+    hipLaunchKernelGGL(k_ms_units, dim3(blocks_for(n_words, 256)), dim3(256), 0, st, xtext, n_x, x_len, pmask, startmask, n_words, split ? 1u : 0u);
+}
+void launch_ms_piece_rank(hipStream_t st, const unsigned long long* startmask, const uint32_t* wprefix, const unsigned long long* pmask, const uint32_t* pprefix,
+                          int64_t n_x, const int64_t* x_len, uint32_t* pt_word) {
+    hipLaunchKernelGGL(k_ms_piece_rank, dim3(blocks_for((n_x >> 6) + 1, 256)), dim3(256), 0, st, startmask, wprefix, pmask, pprefix, n_x, x_len, pt_word);
+}
 void launch_long_vocab3(hipStream_t st, int grid, const DevTables& t, const uint8_t* text, const QView& v1, const QView& v2, const QView& v3, void* rows, uint32_t miss_is_unk,
                         int* err, const WordCache& wc) {
     hipLaunchKernelGGL(k_long_vocab3, dim3(3 * grid), dim3(256), 0, st, t, text, v1, v2, v3, (uint4*)rows, miss_is_unk, err, wc.claim_mask,

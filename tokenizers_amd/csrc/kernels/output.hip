@@ -480,7 +480,7 @@ __global__ __launch_bounds__(256) void k_token_meta_seq(MetaArgs a) {
         int64_t lo = 0, hi = a.n_docs;
         while (hi - lo > 1) { int64_t mid = (lo + hi) >> 1; if ((int64_t)a.doc_pt[mid] <= p) lo = mid; else hi = mid; }
         const int64_t d = lo;
-        const uint32_t word = a.word_of_doc ? a.word_of_doc[d] : (uint32_t)(p - a.doc_pt[d]);
+        const uint32_t word = a.word_of_doc ? a.word_of_doc[d] : a.pt_word ? a.pt_word[p] - a.pt_word[a.doc_pt[d]] : (uint32_t)(p - a.doc_pt[d]);
         const uint32_t xdoc = (uint32_t)a.x_doc_off[d];
         const uint32_t odoc = (uint32_t)a.doc_off[d];
         uint32_t rel = 0;
@@ -753,7 +753,7 @@ __global__ __launch_bounds__(256, MASKS ? 5 : 4) void k_token_meta(MetaArgs a) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) { run += v[q]; if (4 * tid + q < np) s_doc[4 * tid + q] = run; }
         }
-        slow = slow || s_slow != 0u || (NORIG && s_match != 0u);
+        slow = slow || s_slow != 0u || (NORIG && s_match != 0u) || a.pt_word;      // (pt_word: word ids by piece, general's way)
         if (!slow && tid < 64) {                          // set bits in front of every mask word: sixty-four words, one wavefront, no barrier of its own
             static_assert(TM_TOKCAP / 64 == 64, "a word a lane of wavefront 0");
             const uint32_t v = (uint32_t)__popcll(s_tmask[tid]);
@@ -773,7 +773,7 @@ __global__ __launch_bounds__(256, MASKS ? 5 : 4) void k_token_meta(MetaArgs a) {
             const uint32_t o = ts0.x, c = ts1.x - o, j = tt - o;
             const uint32_t s = ts0.y, e = HAS_END ? s_end[i] : ts1.y;
             const int64_t p = base + i, d = (int64_t)s_doc[i];
-            uint32_t word = a.word_of_doc ? a.word_of_doc[d] : (uint32_t)(p - (int64_t)a.doc_pt[d]);
+            uint32_t word = a.word_of_doc ? a.word_of_doc[d] : a.pt_word ? a.pt_word[p] - a.pt_word[a.doc_pt[d]] : (uint32_t)(p - (int64_t)a.doc_pt[d]);
             const uint32_t xdoc = (uint32_t)a.x_doc_off[d], odoc = (uint32_t)a.doc_off[d];
             uint32_t rel = 0u, rel_end = e - s;           // (no token ends without offsets: word ids only)
             bool snapped = c == 1u;                       // (one token: the pre-token's own edges, char boundaries both)

@@ -189,9 +189,18 @@ enum PretokKind {
     PT_WHITESPACE = 3,       // \w+|[^\w\s]+                                    whitespace.rs:20-29
     PT_WHITESPACE_SPLIT = 4, // char::is_whitespace                             whitespace.rs:35-41
     PT_BERT = 5,             // BertPreTokenizer                                bert.rs:14-17
-    PT_BYTELEVEL_NOREGEX = 6 // ByteLevel(use_regex=false): whole doc is one pre-token
+    PT_BYTELEVEL_NOREGEX = 6,// ByteLevel(use_regex=false): whole doc is one pre-token
+    PT_METASPACE = 7         // the "▁" front of SentencePiece-style BPE: Metaspace (metaspace.rs:122-146), or null behind NORM_METASPACE
 };
-enum NormKind { NORM_NONE = 0, NORM_BERT = 1 };
+// NORM_METASPACE: Sequence[Prepend("▁"), Replace(" " -> "▁")] or Replace(" " -> "▁") alone (prepend.rs:16-24, replace.rs:83)
+enum NormKind { NORM_NONE = 0, NORM_BERT = 1, NORM_METASPACE = 2 };
+// where the "▁" front puts a "▁" in front of a piece (the raw text between document edges and added-token matches)
+enum MsPrepend {
+    MS_NEVER = 0,      // Metaspace prepend_scheme "never"; Replace alone
+    MS_ALWAYS = 1,     // Metaspace "always": unless the piece starts with ' ' or "▁"
+    MS_FIRST = 2,      // Metaspace "first": the same, only for a piece at its sequence's offset 0 (a document start)
+    MS_PIECE = 3,      // the Prepend normalizer: every non-empty piece, whatever it starts with
+};
 
 // ---- the tiktoken family of Split patterns (pre_tokenizers/split.rs:76-105 with a SysRegex, tokenizer/pattern.rs:63-83) -------
 // Every member is the alternation
