@@ -163,6 +163,13 @@ def test_one_call_over_a_device_list(monkeypatch):
     M.test_sharded_call_equals_the_unsharded_call("p2p", 2)
     M.test_sharded_pairs_truncation_fixed_padding_and_words("bert_wordpiece_4000_specials")
     M.test_an_error_in_one_shard_fails_the_call_and_the_handle_survives()
+    # every result array in the peer-copy collect: the nine-array pair call on three devices, the SentencePiece-style front, and the
+    # cuts that leave a shard without documents (under AddressSanitizer, tools/simt_check.sh, a root buffer too few is a report)
+    M.check_matrix_case(monkeypatch, "bert_wordpiece_4000_specials", 3, "p2p", "pairs")
+    M.check_matrix_case(monkeypatch, "spm_bpe_llama2", 3, "p2p", "mixed")
+    zero = ("long alone", "long first", "long between", "long last")
+    assert M.check_cuts(monkeypatch, "bert-batchlongest", 5, True, "p2p", kinds=("singles",), only=zero) == 4
+    assert M.check_cuts(monkeypatch, "spm_llama2-fixed", 3, True, "host", kinds=("words",), only=zero) >= 3
 
 
 def test_decode_batch_matches_golden():

@@ -121,7 +121,7 @@ struct tkamd_tokenizer {
     std::mutex group_mu;                 // one sharded call at a time (it already uses every device)
     std::atomic<int> collect{0};         // TKAMD_COLLECT_*
     std::string collect_note;            // why the handle left TKAMD_COLLECT_ROOT_RCCL for the peer copies (written under group_mu)
-    DevBuf g_root[8];                    // COLLECT_ROOT_*: the whole result on devices[0] before its one D2H (indexed like the descriptors of the call)
+    std::vector<std::unique_ptr<DevBuf>> g_root;   // COLLECT_ROOT_*: the whole result on devices[0] before its one D2H, one buffer per descriptor of the call (grown to the call's list: encode_host_sharded)
     std::vector<void*> rccl_comms;       // ncclComm_t per device of the handle (COLLECT_ROOT_RCCL, made at first use)
     int64_t shard_min_bytes = 1 << 20;   // a batch of less than this per device is not worth the threads: it runs on devices[0] (TKAMD_SHARD_MIN_KB, read at load)
     std::vector<double> shard_ms;        // last sharded call: wall milliseconds every device's thread was busy (H2D + kernels + collect)

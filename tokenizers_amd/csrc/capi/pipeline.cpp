@@ -400,6 +400,12 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
         fa.pad_on = pa.pad_on; fa.pad_fixed = pa.pad_fixed; fa.pad_length = pa.pad_length; fa.pad_multiple = pa.pad_multiple;
         size_t T2 = (size_t)n_x + 4 + (size_t)(n_pairs + 1) * n_special_max;
         if (overflow) {
+            // (a sharded call with BatchLongest padding: the CSR below pads to the BATCH's longest encoding, not to this shard's)
+            // (the value itself is not needed here: batch_longest wrote it back to the device target the kernels below read)
+            if (hm.pad_on && !hm.pad_fixed && w->pad_exchange) {
+                (void)batch_longest(pa.target, &rerun);
+                if (rerun) { pf.end(); return; }
+            }
             launch_final_offsets(st, fa);
             int64_t total = 0;
             HIP_CHECK(hipMemcpyAsync(&total, fa.n_tok2, 8, hipMemcpyDeviceToHost, st));
@@ -532,7 +538,13 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
         // capacity of the padded arrays: known up front for Fixed; BatchLongest needs the batch maximum (one 4-byte read-back)
         size_t T2 = (size_t)n_x + 4 + (size_t)(e_n + 1) * n_add;
         if (overflow) {
-            // overlapping windows: the token total is whatever the new CSR says (read back once it is built)
+            // overlapping windows: the token total is whatever the new CSR says (read back once it is built).  A sharded call with
+            // BatchLongest padding first takes the batch's longest encoding from the other shards, like the branch below.  (Its value is
+            // not needed here: batch_longest wrote it back to the device target the kernels below read.)
+            if (hm.pad_on && !hm.pad_fixed && w->pad_exchange) {
+                (void)batch_longest(fa.target, &rerun);
+                if (rerun) { pf.end(); return; }
+            }
             launch_final_offsets(st, fa);
             int64_t total = 0;
             HIP_CHECK(hipMemcpyAsync(&total, fa.n_tok2, 8, hipMemcpyDeviceToHost, st));

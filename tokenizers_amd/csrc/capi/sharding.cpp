@@ -120,6 +120,12 @@ static int encode_host_sharded(tkamd_tokenizer* t, const uint8_t* text, const in
     };
     auto count_of = [&](const Shard& x, const ShardDesc& d) { return (d.per_token ? x.n_tok : x.n_enc) + d.extra; };
     auto base_of = [&](const Shard& x, const ShardDesc& d) { return d.per_token ? x.tok_base : x.enc_base; };
+    // COLLECT_ROOT_*: the root buffer of descriptor q.  The coordinator grows the handle's list to the call's descriptors before any
+    // shard gets here; a descriptor without a buffer is an error of this file and fails the call instead of writing past the list.
+    auto root_of = [&](size_t q) -> DevBuf& {
+        if (q >= t->g_root.size()) throw Invalid("internal: a sharded call describes more result arrays than the root has buffers for");
+        return *t->g_root[q];
+    };
 
     auto worker = [&](int r) {
         Shard& x = sh[(size_t)r];
@@ -179,11 +185,16 @@ static int encode_host_sharded(tkamd_tokenizer* t, const uint8_t* text, const in
                     for (Shard& y : sh) { y.tok_base = tb; y.enc_base = eb; tb += y.n_tok; eb += y.n_enc; }
                     total_tok = tb;
                     if ((uint64_t)tb >= ((uint64_t)1 << 40)) throw Invalid("more than 2^40 tokens in one batch");
+                    // (the collect walks the shards' lists side by side, descriptor q of every shard into array q of the result)
+                    for (const std::vector<ShardDesc>& dl : desc)
+                        if (dl.size() != desc[0].size()) throw Invalid("internal: the shards of one call describe different sets of result arrays");
+                    if (collect != TKAMD_COLLECT_HOST)
+                        while (t->g_root.size() < desc[0].size()) t->g_root.emplace_back(new DevBuf());
                     for (size_t q = 0; q < desc[0].size(); ++q) {
                         const ShardDesc& d = desc[0][q];
                         const size_t elems = (size_t)(d.per_token ? tb : eb) + (size_t)d.extra;
                         *d.dst = pinned_get(elems * d.esz + 64);
-                        if (collect != TKAMD_COLLECT_HOST) t->g_root[q].reserve(elems * d.esz + 64);
+                        if (collect != TKAMD_COLLECT_HOST) root_of(q).reserve(elems * d.esz + 64);
                     }
                     return TKAMD_OK;
                 });
@@ -201,6 +212,7 @@ static int encode_host_sharded(tkamd_tokenizer* t, const uint8_t* text, const in
                 if (x.tok_base) launch_add_i64(x.s, (int64_t*)x.res.d_tok_offsets, x.n_enc + 1, x.tok_base);      // the shard's CSR continues the batch's
                 if (x.res.d_enc_docs && x.g0) launch_add_u32(x.s, (uint32_t*)x.res.d_enc_docs, x.n_enc, (uint32_t)(mixed ? x.i0 : x.g0 / unit));   // ... and its documents the batch's
                 const std::vector<ShardDesc>& dl = desc[(size_t)r];
+                if (collect != TKAMD_COLLECT_HOST && !dl.empty()) (void)root_of(dl.size() - 1);      // (checked here: nothing below may throw inside an open RCCL group)
                 if (collect == TKAMD_COLLECT_HOST) {
                     for (const ShardDesc& d : dl) {
                         const int64_t n = count_of(x, d);
@@ -210,7 +222,7 @@ static int encode_host_sharded(tkamd_tokenizer* t, const uint8_t* text, const in
                     for (size_t q = 0; q < dl.size(); ++q) {
                         const ShardDesc& d = dl[q];
                         const int64_t n = count_of(x, d);
-                        if (n > 0) HIP_CHECK(hipMemcpyPeerAsync((uint8_t*)t->g_root[q].p + (size_t)base_of(x, d) * d.esz, t->device, d.src, tr->device, (size_t)n * d.esz, x.s));
+                        if (n > 0) HIP_CHECK(hipMemcpyPeerAsync((uint8_t*)root_of(q).p + (size_t)base_of(x, d) * d.esz, t->device, d.src, tr->device, (size_t)n * d.esz, x.s));
                     }
                     HIP_CHECK(hipEventRecord(x.ev, x.s));
                 } else {
@@ -231,7 +243,7 @@ static int encode_host_sharded(tkamd_tokenizer* t, const uint8_t* text, const in
                             for (size_t q = 0; q < dl.size(); ++q) {
                                 const ShardDesc& d = desc[(size_t)p][q];
                                 const int64_t n = count_of(sh[(size_t)p], d);
-                                if (n > 0) note(api.Recv((uint8_t*)t->g_root[q].p + (size_t)base_of(sh[(size_t)p], d) * d.esz, (size_t)n * d.esz, 1, p, t->rccl_comms[0], x.s), "ncclRecv");
+                                if (n > 0) note(api.Recv((uint8_t*)root_of(q).p + (size_t)base_of(sh[(size_t)p], d) * d.esz, (size_t)n * d.esz, 1, p, t->rccl_comms[0], x.s), "ncclRecv");
                             }
                     note(api.GroupEnd(), "ncclGroupEnd");
                     if (first_bad) throw HipError(std::string(what) + " failed: " + (api.GetErrorString ? api.GetErrorString(first_bad) : "?"));
@@ -255,7 +267,7 @@ static int encode_host_sharded(tkamd_tokenizer* t, const uint8_t* text, const in
                     for (size_t q = 0; q < desc[0].size(); ++q) {
                         const ShardDesc& d = desc[0][q];
                         const size_t elems = (size_t)(d.per_token ? total_tok : eb) + (size_t)d.extra;
-                        if (elems) HIP_CHECK(hipMemcpyAsync(d.dst->p, t->g_root[q].p, elems * d.esz, hipMemcpyDeviceToHost, x.s));
+                        if (elems) HIP_CHECK(hipMemcpyAsync(d.dst->p, root_of(q).p, elems * d.esz, hipMemcpyDeviceToHost, x.s));
                     }
                     return TKAMD_OK;
                 });
