@@ -99,7 +99,6 @@ struct tkamd_tokenizer {
     // of the step (the claims' worst case).  Inside a batch every lookup workgroup gives the claims up by itself once
     // it has seen that (kernels/lookup.hip CLAIM_ADAPT_MIN); across batches, a batch that ran with the claims and found fewer than a
     // quarter of its candidates shared pauses them for the next claims_pause_len batches of the handle; then they are tried again.
-    std::atomic<int> q16_fat_hint{1};    // the last batch that ran with the claims left a fat <= 16-byte queue (or none has run yet): see run_pipeline's merge launches
     std::atomic<int> claims_pause{0};
     // A tokenizer with added tokens runs a batch as if its text held none (one detection pass per pattern set instead of match / resolve /
     // scatter / piece launches that find nothing in natural text); a batch that did hold one is run again with the matching passes and
@@ -128,7 +127,6 @@ struct tkamd_tokenizer {
     std::vector<int64_t> shard_bytes;
 };
 
-constexpr uint32_t MERGE_THIN_LIMIT = 393216;   // <= 16-byte queue entries up to which the 32-symbol merge launch takes them along (two rounds of its 768 lanes x 256 CUs)
 constexpr size_t PHASE_WGS = 1 << 17;           // workgroups the phase table has rows for (per kernel)
 constexpr size_t MAX_HOST_WORKSPACES = 4;       // concurrent host-entry calls per handle; further callers wait for a free one
 

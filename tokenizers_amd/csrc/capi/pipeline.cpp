@@ -1021,15 +1021,14 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
         const bool lds16 = t->dt.newid_affine && !test_hook("TKAMD_FORCE_LANE_MERGE");      // keys in LDS
         const bool lds32 = lds16;
         // With the claims on both queues hold the distinct words only, and a launch of the LDS kernels lasts as long as its longest word's
-        // chain of dependent merge probes whatever it holds: the 32-symbol kernel takes both queues in one launch.  Thin or not is only
-        // known on the device: while the handle has not seen a thin <= 16-byte queue (its first batch, or text that repeats nothing) BOTH
-        // kernels are launched and pick the queue's owner from its fill themselves (thin_limit; an extra ~4 us launch); once a batch came
-        // back thin the next ones launch the 32-symbol kernel alone, until a fat one is seen again.  (Test hook TKAMD_MERGE_TWO: always two
-        // launches, each with its own queue.)
+        // chain of dependent merge probes whatever it holds: ONE launch takes both queues, the 16-symbol and the 32-symbol body side by
+        // side in one grid (k_bpe_merge_lds_pair: it splits its workgroups between the queues by their fills, thin or fat, on the device).
+        // (Test hooks.  TKAMD_MERGE_TWO: two launches, each kernel with its own queue.  TKAMD_MERGE_PAIR=0: the one launch is the 32-symbol
+        // kernel with the <= 16-byte queue behind its own, what ran before the pair kernel -- the A/B of the two in one process.)
         const bool can_one = wc.claims && lds16 && lds32 && !test_hook("TKAMD_MERGE_TWO");
-        const bool both = can_one && t->q16_fat_hint.load() != 0;
-        const bool one = can_one && !both;
-        if (both) mdt.thin_limit = MERGE_THIN_LIMIT;
+        const char* const pair_hook = test_hook("TKAMD_MERGE_PAIR");
+        const bool pair = can_one && !(pair_hook && pair_hook[0] == '0');
+        const bool one = can_one && !pair;
         // BPE over characters: only the kernels that know its start (kernels/bpe.hip CHARS) -- the two LDS kernels, each on its own queue,
         // and the workgroup-per-pre-token kernel for everything beyond 32 bytes (or for everything, when the vocabulary's new ids are not
         // in merge order and the LDS kernels cannot run)
@@ -1045,7 +1044,6 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
             w->w_list_huge.reserve(64);
         }
         if (hm.char_bpe) {
-            mdt.thin_limit = 0u;                           // (each queue has its one kernel here)
             auto long_only = [&](const QView& q) {
                 launch_bpe_merge_long_only(st, t->n_cu * 2, mdt, x_text, q, w->w_rows.p, w->w_tmp_ids.as<uint32_t>(), tmp_end, w->w_list_huge.as<uint32_t>(), d_counters + CNT_LISTH);
             };
@@ -1065,10 +1063,16 @@ void run_pipeline(tkamd_tokenizer* t, Workspace* w, const uint8_t* d_text, const
                                   (unsigned long long*)(sc + SC_HUGE_USED), d_err);
             pf.end();
         } else {
-        pf.begin(lds32 ? "bpe_merge_lds32" : "bpe_merge_lane32");
-        launch_bpe_merge(st, lds32 ? t->n_cu : grid, lds32 ? 6 : 2, mdt, x_text, plan.v[1], w->w_rows.p, w->w_tmp_ids.as<uint32_t>(), tmp_end, (one || both) ? &plan.v[0] : nullptr);
-        pf.end();
-        if (!one) {
+        if (pair) {
+            pf.begin("bpe_merge_lds_pair");
+            launch_bpe_merge_pair(st, t->n_cu, mdt, x_text, plan.v[0], plan.v[1], w->w_rows.p, w->w_tmp_ids.as<uint32_t>(), tmp_end);
+            pf.end();
+        } else {
+            pf.begin(lds32 ? "bpe_merge_lds32" : "bpe_merge_lane32");
+            launch_bpe_merge(st, lds32 ? t->n_cu : grid, lds32 ? 6 : 2, mdt, x_text, plan.v[1], w->w_rows.p, w->w_tmp_ids.as<uint32_t>(), tmp_end, one ? &plan.v[0] : nullptr);
+            pf.end();
+        }
+        if (!can_one) {
             pf.begin(lds16 ? "bpe_merge_lds" : "bpe_merge_lane");
             launch_bpe_merge(st, lds16 ? t->n_cu : grid, lds16 ? 5 : 1, mdt, x_text, plan.v[0], w->w_rows.p, w->w_tmp_ids.as<uint32_t>(), tmp_end);
             pf.end();
@@ -1260,7 +1264,6 @@ int read_scalars(tkamd_tokenizer* t, Workspace* w, hipStream_t st, int64_t* n_to
         // Fewer than one in four shared: the round trips cost more than the merges they save (tkamd_tokenizer::claims_pause)
         const uint64_t cands = w->last_counters[CNT_CLAIM_CANDS], shared = w->last_counters[CNT_CLAIM_SHARED];
         if (cands >= 32768 && shared * 4 < cands) t->claims_pause = t->claims_pause_len;
-        t->q16_fat_hint = w->last_counters[CNT_CLAIM_CANDS] - w->last_counters[CNT_CLAIM_SHARED] >= MERGE_THIN_LIMIT ? 1 : 0;   // (survivors: an upper bound of the queue's fill)
     }
     if (n_tok) *n_tok = host[w->last_ntok_slot];
     if (n_pretok) *n_pretok = host[SC_NPRETOK];

@@ -20,7 +20,6 @@ struct DevTables {
     uint32_t cb;                      // CB_* flags of that model (0: byte-level BPE, or another model)
     int* err;                         // (per call, in the host's copy) the batch's error bits: the char start reports ERR_UNK_OOV
     uint32_t* probes;                 // (per call, profiling runs only, else null) counter of merge-table probes, (k - 1) + 2 m per word
-    uint32_t thin_limit;              // != 0 (per call, in the host's copy): the LDS merge kernels pick the owner of the <= 16-byte queue by its fill (bpe.hip)
     // in-batch claims: set (per call, in the host's copy) when the model kernels publish the claimants' rows themselves (bpe.hip):
     // the rows of the claimed slots, the slot mask, and -- only when offsets are requested -- where the claimant's first byte goes
     void* pub_rows;
@@ -344,6 +343,10 @@ void launch_lookup(hipStream_t st, int grid, const DevTables& t, const uint8_t* 
 // also (group 6 only): a second queue for the same launch
 void launch_bpe_merge(hipStream_t st, int grid, int group, const DevTables& t, const uint8_t* text, const QView& v, void* rows,
                       uint32_t* tmp_ids, uint32_t* tmp_end, const QView* also = nullptr);
+// both LDS merge queues in one launch, side by side (k_bpe_merge_lds_pair; its grid is what is resident on n_cu CUs)
+void launch_bpe_merge_pair(hipStream_t st, int n_cu, const DevTables& t, const uint8_t* text, const QView& v16, const QView& v32, void* rows,
+                           uint32_t* tmp_ids, uint32_t* tmp_end);
+int pair_merge_occupancy();       // workgroups of k_bpe_merge_lds_pair resident per CU (after prepare_long_kernel)
 // the normaliser's count arrays share one buffer: n_bytes + 64 per-byte counts (written for the lanes that are not plain only), then
 // one byte per 16-byte lane (bert_norm_core.hpp BnOlen); bn_olen_bytes(n) is what the buffer must hold
 inline size_t bn_olen_bytes(int64_t n_bytes) { return (((size_t)n_bytes + 64 + 15) & ~(size_t)15) + ((size_t)n_bytes >> 4) + 64; }

@@ -371,85 +371,50 @@ template __global__ void k_bpe_merge_lane<32>(DevTables, const uint8_t*, QView, 
 // (one per unknown char, or one per run of them: fuse_unk), the <0xXX> tokens of its bytes (byte_fallback), or nothing at all (no
 // unk_token: the char is dropped) -- BPE::merge_word, bpe/model.rs:465-550.  Symbols still sit at the byte position they start at, so
 // the merge loop, the token-boundary mask and the row format are the byte-level ones.
-template <int S, int NT, bool DISP_LDS, bool SYM_REGS, bool CHARS = false>
-__global__ __launch_bounds__(NT) void k_bpe_merge_lds(DevTables t, const uint8_t* __restrict__ text, QView v, QView v2, uint4* __restrict__ rows,
-                                                      uint32_t* __restrict__ tmp_ids, uint32_t* __restrict__ tmp_end) {
-    __shared__ uint32_t s_qpre[NSQ + 1];
-    __shared__ uint32_t s_qpre2[S == 32 ? NSQ + 1 : 1];    // (only the 32-symbol kernel takes a second queue: two 704-lane workgroups of the 16-symbol one fill a CU's LDS to the last KB)
-    __shared__ uint32_t s_probes;                          // t.probes (profiling runs): merge-table probes of this workgroup's words, SURVEY 8d's model
-    if (threadIdx.x == 0) s_probes = 0u;
+// One UNIT of the LDS merge: `take` consecutive items from `base` of the item order (the entries of v, then -- TWO_Q -- those of v2), one per
+// lane, from the queue entry to the published row.  NT lanes run it (all of them meet the barriers of the counting sort); the first NL
+// of them hold a word each, the key column of lane l being lds_words[slot * NL + l] (NL < NT: the 32-symbol role of k_bpe_merge_lds_pair,
+// whose key area is the 16-symbol role's).  Shared by k_bpe_merge_lds and k_bpe_merge_lds_pair.
+template <int S, int NT, int NL, bool SYM_REGS, bool CHARS, bool TWO_Q>
+__device__ __forceinline__ void bpe_merge_lds_unit(const DevTables& t, const uint8_t* __restrict__ text, const QView& v, const uint32_t* s_qpre, const uint32_t n_first,
+                                                   const QView& v2, const uint32_t* s_qpre2, const uint32_t n_items, const uint32_t base, const uint32_t take,
+                                                   uint32_t* lds_words, const uint16_t* const disp, uint32_t* s_probes, uint4* __restrict__ rows,
+                                                   uint32_t* __restrict__ tmp_ids, uint32_t* __restrict__ tmp_end) {
+    static_assert(NL <= NT && NL % 64 == 0 && 4 * NT <= S * NL, "whole wavefronts hold the words; the sort's items fit the key area");
     constexpr uint32_t PB = (S == 16) ? 4 : 5;
-    HIP_DYNAMIC_SHARED(__attribute__((aligned(16))) uint32_t, lds_words)
-    uint32_t* s_key = lds_words;                              // [S][NT]
-    uint32_t* s_sym = s_key + S * NT;                         // [S][NT], absent when the symbols stay in registers
-    uint32_t* s_byte_id = s_sym + (SYM_REGS ? 0 : S * NT);    // [256]
-    uint32_t* s_hist = s_byte_id + 256;                       // [S + 1] (+ padding to 64)
-    uint16_t* s_disp = (uint16_t*)(s_hist + 64);              // [DISP_LDS_MAX]
-    uint4* s_sort = (uint4*)s_key;                            // [NT], aliases the key area between items
+    uint32_t* const s_key = lds_words;                              // [S][NL]
+    uint32_t* const s_sym = s_key + S * NL;                         // [S][NL], absent when the symbols stay in registers
+    uint32_t* const s_byte_id = s_sym + (SYM_REGS ? 0 : S * NL);    // [256]
+    uint32_t* const s_hist = s_byte_id + 256;                       // [S + 2]: a bin per length 0..S and the invalid lanes' (+ padding to 64)
+    uint4* const s_sort = (uint4*)s_key;                            // [NT], aliases the key area between items
     const uint32_t tid = threadIdx.x;
-    // Which kernel takes the <= 16-byte class is decided HERE, from the queue's fill, when the host asks for it (t.thin_limit != 0: both
-    // kernels are launched).  Thin -- the in-batch claims left the distinct words only -- it rides along in the 32-symbol launch (one
-    // launch lasts as long as its longest word's chain of merges whatever it holds, and this kernel returns at once); fat -- text that
-    // repeats nothing -- it stays with this kernel's twice as many lanes per CU (13 M short words: 0.85 ms against 1.51).  Both kernels
-    // read the same counters, so exactly one of them takes the queue.
-    const uint32_t n_first = qview_prefix(v, s_qpre);
-    if (S == 16 && t.thin_limit && n_first < t.thin_limit) return;
-    for (uint32_t i = tid; i < 256; i += NT) s_byte_id[i] = t.byte_id[i];
-    // (DISP_LDS is the launcher's choice: only for a displacement table that fits.  A pointer that is the LDS copy or the table in memory
-    // by a RUN-TIME test is a flat pointer: its loads count on both memory counters and return in no order, so the compiler waits for
-    // everything in flight behind every one of them -- up to round 5 each of a word's up to 31 first probes, and both probes of every
-    // merge, was a round trip of its own: s_waitcnt vmcnt(0) lgkmcnt(0) around each in the ISA)
-    constexpr bool disp_in_lds = DISP_LDS;
-    if (disp_in_lds) {
-        // sixteen bytes a load (eight displacements): with thin queues the kernel is as long as its prologue plus one word's chain of
-        // merges, and 2-byte loads made the prologue twenty dependent round trips per lane
-        static_assert((DISP_LDS_MAX * 2) % 16 == 0, "whole 16-byte words");
-        const uint32_t n16 = (t.merge_bmask + 8u) >> 3;                             // (the table is a power of two of entries; the upload is padded)
-        for (uint32_t i = tid; i < n16; i += NT) ((uint4*)s_disp)[i] = ((const uint4*)t.merge_disp)[i];
+    const uint32_t item = base + tid;
+    bool valid = tid < take && item < n_items;
+    uint32_t s = 0, len = 0, qidx = 0, claim = 0;         // qidx: the result row (named by the position in the work queue); claim: QLEN_CLAIM of the entry
+    if (valid) {
+        if (!TWO_Q || item < n_first) { const uint32_t qp = qview_pos(s_qpre, v.sq_cap, item); const QItem it = v.q[qp]; s = it.s; len = qitem_len(it.len); claim = it.len & QLEN_CLAIM; qidx = v.row_base + qp; }
+        else { const uint32_t qp = qview_pos(s_qpre2, v2.sq_cap, item - n_first); const QItem it = v2.q[qp]; s = it.s; len = qitem_len(it.len); claim = it.len & QLEN_CLAIM; qidx = v2.row_base + qp; }
     }
-    __syncthreads();
-    const uint16_t* const disp = disp_in_lds ? (const uint16_t*)s_disp : t.merge_disp;
-    const uint32_t nid_base = t.newid_base;
-    uint32_t n_second = (S == 32 && v2.q) ? qview_prefix(v2, s_qpre2) : 0u;
-    if (t.thin_limit && n_second >= t.thin_limit) n_second = 0u;   // (fat: the 16-symbol kernel's)
-    const uint32_t n_items = n_first + n_second;
-    // a short queue (the in-batch claims leave the distinct words only) is spread over the whole grid, a few wavefronts of every
-    // workgroup busy, instead of filling the first workgroups and leaving most CUs idle
-    const uint32_t take = min((uint32_t)NT, ((n_items + gridDim.x - 1u) / gridDim.x + 63u) & ~63u);
-    const uint32_t stride = gridDim.x * take;
-    // Rounds alternate their direction over the workgroups: the queue of the LONGER class comes first in the item order, so it is the
-    // first workgroups whose round 0 is as long as a 32-symbol word's chain of merges -- a second round on top of that made them the
-    // launch's critical path (two rounds at C2: 296 k words on 196 k lanes); reversed, round 1 goes to the workgroups whose round 0 was short.
-    uint32_t round = 0u;
-    for (uint32_t base0 = 0u; base0 < n_items; base0 += stride, ++round) {
-        const uint32_t base = base0 + ((round & 1u) ? (gridDim.x - 1u - blockIdx.x) : blockIdx.x) * take;
-        if (base >= n_items) { if (base0 + stride >= n_items) break; continue; }         // (workgroup-uniform)
-        const uint32_t item = base + tid;
-        bool valid = tid < take && item < n_items;
-        uint32_t s = 0, len = 0, qidx = 0, claim = 0;         // qidx: the result row (named by the position in the work queue); claim: QLEN_CLAIM of the entry
-        if (valid) {
-            if (item < n_first) { const uint32_t qp = qview_pos(s_qpre, v.sq_cap, item); const QItem it = v.q[qp]; s = it.s; len = qitem_len(it.len); claim = it.len & QLEN_CLAIM; qidx = v.row_base + qp; }
-            else { const uint32_t qp = qview_pos(s_qpre2, v2.sq_cap, item - n_first); const QItem it = v2.q[qp]; s = it.s; len = qitem_len(it.len); claim = it.len & QLEN_CLAIM; qidx = v2.row_base + qp; }
-        }
-        valid = valid && len != 0u;                           // length 0: retired by k_long_vocab
-        // counting sort of the workgroup's items by length: a wavefront loops until its slowest lane is done
-        {
-            __syncthreads();                                  // previous item's key/sym area is dead
-            if (tid <= S) s_hist[tid] = 0;
-            __syncthreads();
-            const uint32_t bin = valid ? len : (uint32_t)S;
-            const uint32_t within = atomicAdd(&s_hist[bin], 1u);
-            __syncthreads();
-            uint32_t before = 0;
-            for (uint32_t b = 0; b < bin; ++b) before += s_hist[b];
-            s_sort[before + within] = make_uint4(claim, s, len, valid ? qidx + 1u : 0u);
-            __syncthreads();
-            const uint4 it = s_sort[tid];
-            __syncthreads();                                  // everyone has read its item before keys overwrite the area
-            claim = it.x; s = it.y; len = it.z; valid = it.w != 0u;
-            qidx = it.w - 1u;
-        }
-        uint32_t* my_key = s_key + tid;                       // slot i at my_key[i * NT]
+    valid = valid && len != 0u;                           // length 0: retired by k_long_vocab
+    // counting sort of the workgroup's items by length: a wavefront loops until its slowest lane is done
+    {
+        __syncthreads();                                  // previous item's key/sym area is dead
+        if (tid <= S + 1) s_hist[tid] = 0;
+        __syncthreads();
+        const uint32_t bin = valid ? len : (uint32_t)S + 1u;  // (a bin of their own behind every word: with NL < NT the words must fill the first lanes)
+        const uint32_t within = atomicAdd(&s_hist[bin], 1u);
+        __syncthreads();
+        uint32_t before = 0;
+        for (uint32_t b = 0; b < bin; ++b) before += s_hist[b];
+        s_sort[before + within] = make_uint4(claim, s, len, valid ? qidx + 1u : 0u);
+        __syncthreads();
+        const uint4 it = s_sort[tid];
+        __syncthreads();                                  // everyone has read its item before keys overwrite the area
+        claim = it.x; s = it.y; len = it.z; valid = it.w != 0u;
+        qidx = it.w - 1u;
+    }
+    if (NL == NT || tid < NL) {                                 // (whole wavefronts; past the sort no valid item sits beyond lane `take` <= NL)
+        uint32_t* my_key = s_key + tid;                       // slot i at my_key[i * NL]
         uint32_t* my_sym = s_sym + tid;
         // SYM_REGS: symbols stay in registers (a dynamic index is a select chain -- the ALU has the headroom) and only
         // the keys take LDS, which is what bounds the number of pre-tokens in flight per CU.  The selects are written
@@ -457,7 +422,7 @@ __global__ __launch_bounds__(NT) void k_bpe_merge_lds(DevTables t, const uint8_t
         uint32_t ids[S];
 #define TKAMD_SYM_AT(dst, pos)                                                                 \
         do {                                                                                   \
-            if (!SYM_REGS) (dst) = my_sym[(pos) * NT];                                         \
+            if (!SYM_REGS) (dst) = my_sym[(pos) * NL];                                         \
             else {                                                                             \
                 (dst) = ids[0];                                                                \
                 _Pragma("unroll") for (int q_ = 1; q_ < S; ++q_) (dst) = ((pos) == (uint32_t)q_) ? ids[q_] : (dst); \
@@ -477,7 +442,7 @@ __global__ __launch_bounds__(NT) void k_bpe_merge_lds(DevTables t, const uint8_t
 #pragma unroll
                 for (int i = 0; i < S; ++i) {
                     ids[i] = s_byte_id[TKAMD_BYTE_AT(i)];
-                    if (!SYM_REGS) my_sym[i * NT] = ids[i];
+                    if (!SYM_REGS) my_sym[i * NL] = ids[i];
                 }
                 // The first probes, one per pair of neighbours: EIGHT at a time, unconditionally (a lane whose word ends earlier probes the
                 // pair of whatever its padding bytes map to and drops the answer) -- the eight loads are in flight together, where a probe
@@ -501,11 +466,11 @@ __global__ __launch_bounds__(NT) void k_bpe_merge_lds(DevTables t, const uint8_t
 #pragma unroll
                         for (int q = 0; q < PG; ++q) {
                             const int i = g + q;
-                            my_key[i * NT] = ((uint32_t)(i + 1) < len && rk[q] != RANK_NONE) ? ((rk[q] << PB) | (uint32_t)i) : 0xFFFFFFFFu;
+                            my_key[i * NL] = ((uint32_t)(i + 1) < len && rk[q] != RANK_NONE) ? ((rk[q] << PB) | (uint32_t)i) : 0xFFFFFFFFu;
                         }
                     } else {
 #pragma unroll
-                        for (int q = 0; q < PG; ++q) my_key[(g + q) * NT] = 0xFFFFFFFFu;
+                        for (int q = 0; q < PG; ++q) my_key[(g + q) * NL] = 0xFFFFFFFFu;
                     }
                 }
                 alive0 = (len >= 32) ? 0xFFFFFFFFu : ((1u << len) - 1u);
@@ -556,7 +521,7 @@ __global__ __launch_bounds__(NT) void k_bpe_merge_lds(DevTables t, const uint8_t
                         merge_probe_d(t, disp, ids[i], right, &r, &nd);
                         if (r != RANK_NONE) k = (r << PB) | (uint32_t)i;
                     }
-                    my_key[i * NT] = k;
+                    my_key[i * NL] = k;
                 }
             }
 #undef TKAMD_BYTE_AT
@@ -567,11 +532,11 @@ __global__ __launch_bounds__(NT) void k_bpe_merge_lds(DevTables t, const uint8_t
             if (active) {
                 uint32_t best = 0xFFFFFFFFu;
 #pragma unroll
-                for (int i = 0; i < S - 1; ++i) best = min(best, my_key[i * NT]);
+                for (int i = 0; i < S - 1; ++i) best = min(best, my_key[i * NL]);
                 if (best == 0xFFFFFFFFu) active = false;
                 else {
                     const uint32_t i = best & (uint32_t)(S - 1);
-                    const uint32_t nid = (best >> PB) + nid_base;
+                    const uint32_t nid = (best >> PB) + t.newid_base;
                     uint32_t above = alive & ~((2u << i) - 1u);           // live positions right of i (the pair's right symbol is the first)
                     const uint32_t j = (uint32_t)__ffs(above) - 1u;
                     above &= above - 1u;
@@ -586,12 +551,12 @@ __global__ __launch_bounds__(NT) void k_bpe_merge_lds(DevTables t, const uint8_t
                     if (SYM_REGS) {
 #pragma unroll
                         for (int q = 0; q < S; ++q) ids[q] = (i == (uint32_t)q) ? nid : ids[q];
-                    } else my_sym[i * NT] = nid;
+                    } else my_sym[i * NL] = nid;
                     uint32_t r1, r2;
                     merge_probe2_d(t, disp, sl, nid, nid, sr, &r1, &r2);
-                    my_key[j * NT] = 0xFFFFFFFFu;
-                    my_key[i * NT] = (has_k && r2 != RANK_NONE) ? ((r2 << PB) | i) : 0xFFFFFFFFu;
-                    if (has_h) my_key[h * NT] = (r1 != RANK_NONE) ? ((r1 << PB) | h) : 0xFFFFFFFFu;
+                    my_key[j * NL] = 0xFFFFFFFFu;
+                    my_key[i * NL] = (has_k && r2 != RANK_NONE) ? ((r2 << PB) | i) : 0xFFFFFFFFu;
+                    if (has_h) my_key[h * NL] = (r1 != RANK_NONE) ? ((r1 << PB) | h) : 0xFFFFFFFFu;
                     if (!has_k && !has_h) active = false;                 // one symbol left
                 }
             }
@@ -633,15 +598,118 @@ __global__ __launch_bounds__(NT) void k_bpe_merge_lds(DevTables t, const uint8_t
             if (tmp_end && c && !carry) tmp_end[s + c - 1] = len;
             { const uint4 row_ = make_row(c, s, r[0], r[1], r[2], r[3]); rows[qidx] = row_; TKAMD_PUBLISH_ROW(t, text, s, len | claim, row_); }
             // (k - 1) + 2 m probes for a word of k symbols and m merges: every initial pair once, two new pairs per merge
-            if (t.probes) { const uint32_t k0 = (uint32_t)__popc(alive0); if (k0) atomicAdd(&s_probes, (k0 - 1u) + 2u * (k0 - c)); }
+            if (t.probes) { const uint32_t k0 = (uint32_t)__popc(alive0); if (k0) atomicAdd(s_probes, (k0 - 1u) + 2u * (k0 - c)); }
         }
+    }
+}
+#undef TKAMD_SYM_AT
+// the tables every unit reads, into the workgroup's LDS behind the key area: the byte alphabet and -- DISP_LDS -- the merge displacements
+template <int S, int NT, int NL, bool DISP_LDS, bool SYM_REGS>
+__device__ __forceinline__ const uint16_t* bpe_merge_lds_tables(const DevTables& t, uint32_t* lds_words) {
+    uint32_t* const s_byte_id = lds_words + (SYM_REGS ? 1 : 2) * S * NL;
+    uint16_t* const s_disp = (uint16_t*)(s_byte_id + 256 + 64);       // [DISP_LDS_MAX]
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < 256; i += NT) s_byte_id[i] = t.byte_id[i];
+    // (DISP_LDS is the launcher's choice: only for a displacement table that fits.  A pointer that is the LDS copy or the table in memory
+    // by a RUN-TIME test is a flat pointer: its loads count on both memory counters and return in no order, so the compiler waits for
+    // everything in flight behind every one of them -- up to round 5 each of a word's up to 31 first probes, and both probes of every
+    // merge, was a round trip of its own: s_waitcnt vmcnt(0) lgkmcnt(0) around each in the ISA)
+    if (DISP_LDS) {
+        // sixteen bytes a load (eight displacements): with thin queues the kernel is as long as its prologue plus one word's chain of
+        // merges, and 2-byte loads made the prologue twenty dependent round trips per lane
+        static_assert((DISP_LDS_MAX * 2) % 16 == 0, "whole 16-byte words");
+        const uint32_t n16 = (t.merge_bmask + 8u) >> 3;                             // (the table is a power of two of entries; the upload is padded)
+        for (uint32_t i = tid; i < n16; i += NT) ((uint4*)s_disp)[i] = ((const uint4*)t.merge_disp)[i];
+    }
+    __syncthreads();
+    return DISP_LDS ? (const uint16_t*)s_disp : t.merge_disp;
+}
+template <int S, int NT, bool DISP_LDS, bool SYM_REGS, bool CHARS = false>
+__global__ __launch_bounds__(NT) void k_bpe_merge_lds(DevTables t, const uint8_t* __restrict__ text, QView v, QView v2, uint4* __restrict__ rows,
+                                                      uint32_t* __restrict__ tmp_ids, uint32_t* __restrict__ tmp_end) {
+    __shared__ uint32_t s_qpre[NSQ + 1];
+    __shared__ uint32_t s_qpre2[S == 32 ? NSQ + 1 : 1];    // (only the 32-symbol kernel takes a second queue: two 704-lane workgroups of the 16-symbol one fill a CU's LDS to the last KB)
+    __shared__ uint32_t s_probes;                          // t.probes (profiling runs): merge-table probes of this workgroup's words, SURVEY 8d's model
+    if (threadIdx.x == 0) s_probes = 0u;
+    HIP_DYNAMIC_SHARED(__attribute__((aligned(16))) uint32_t, lds_words)
+    const uint32_t n_first = qview_prefix(v, s_qpre);
+    const uint16_t* const disp = bpe_merge_lds_tables<S, NT, NT, DISP_LDS, SYM_REGS>(t, lds_words);
+    const uint32_t n_second = (S == 32 && v2.q) ? qview_prefix(v2, s_qpre2) : 0u;
+    const uint32_t n_items = n_first + n_second;
+    // a short queue (the in-batch claims leave the distinct words only) is spread over the whole grid, a few wavefronts of every
+    // workgroup busy, instead of filling the first workgroups and leaving most CUs idle
+    const uint32_t take = min((uint32_t)NT, ((n_items + gridDim.x - 1u) / gridDim.x + 63u) & ~63u);
+    const uint32_t stride = gridDim.x * take;
+    // Rounds alternate their direction over the workgroups: the queue of the LONGER class comes first in the item order, so it is the
+    // first workgroups whose round 0 is as long as a 32-symbol word's chain of merges -- a second round on top of that made them the
+    // launch's critical path (two rounds at C2: 296 k words on 196 k lanes); reversed, round 1 goes to the workgroups whose round 0 was short.
+    uint32_t round = 0u;
+    for (uint32_t base0 = 0u; base0 < n_items; base0 += stride, ++round) {
+        const uint32_t base = base0 + ((round & 1u) ? (gridDim.x - 1u - blockIdx.x) : blockIdx.x) * take;
+        if (base >= n_items) { if (base0 + stride >= n_items) break; continue; }         // (workgroup-uniform)
+        bpe_merge_lds_unit<S, NT, NT, SYM_REGS, CHARS, S == 32>(t, text, v, s_qpre, n_first, v2, s_qpre2, n_items, base, take, lds_words, disp, &s_probes, rows, tmp_ids, tmp_end);
     }
     if (t.probes) {                                        // (uniform)
         __syncthreads();
         if (threadIdx.x == 0 && s_probes) atomicAdd(t.probes, s_probes);
     }
 }
-#undef TKAMD_SYM_AT
+// =================================================================================================
+// K_bpe_merge_lds_pair: BOTH queues of the LDS merge in one launch, SIDE BY SIDE -- what runs when the in-batch claims are on.
+// k_bpe_merge_lds<32, ..> with the <= 16-byte queue behind its own gives every short word (93 % of them at C2) the 32-symbol price --
+// select chains over 32 registers, a minimum over 31 keys -- and, 768 lanes a CU, takes two rounds for C2's 285 k distinct words.  Here
+// a workgroup is 640 lanes, two to a CU (the 16-symbol kernel's shape), and runs units of either ROLE:
+//   short: the 16-symbol unit over 640 words of v16;
+//   long:  the 32-symbol unit over 320 words of v32 -- 320 x 32 keys are the same 40 KB as 640 x 16, the upper five wavefronts only
+//          meet the barriers.  Five wavefronts a SIMD leave 96 registers: without the second queue's code the role takes 94 (96 with
+//          the displacements in memory) where k_bpe_merge_lds<32, ..> takes 104, no scratch, its first probes still eight at a time
+//          (tests/test_isa_merge_pair.py holds all of that).  Tried and dropped: first probes four at a time (the same 94), and
+//          amdgpu_waves_per_eu(5, 5), under which the instantiation that reads the displacements from memory probes one at a time.
+// Nobody but the device knows the fills, so every workgroup derives the same plan from them: the fewest ROUNDS of the grid that hold
+// both queues at full units; when that is one round, its slots are split between the roles in proportion to what each needs and each
+// queue is spread evenly over its slots (a thin queue keeps a few wavefronts of every one of its workgroups busy, as in k_bpe_merge_lds).  Units are
+// numbered long role first and dealt to the workgroups round by round, the rounds alternating their direction: a second round goes
+// first to the workgroups whose first unit was a short one.  No workgroup waits for another.
+// =================================================================================================
+constexpr int PAIR_NT = 640, PAIR_NL32 = 320, PAIR_WG_PER_CU = 2;
+static_assert(16 * PAIR_NT == 32 * PAIR_NL32, "one key area serves both roles");
+template <bool DISP_LDS>
+__global__ __launch_bounds__(PAIR_NT) void k_bpe_merge_lds_pair(DevTables t, const uint8_t* __restrict__ text, QView v16, QView v32, uint4* __restrict__ rows,
+                                                                                      uint32_t* __restrict__ tmp_ids, uint32_t* __restrict__ tmp_end) {
+    __shared__ uint32_t s_qpre16[NSQ + 1];
+    __shared__ uint32_t s_qpre32[NSQ + 1];
+    __shared__ uint32_t s_probes;
+    if (threadIdx.x == 0) s_probes = 0u;
+    HIP_DYNAMIC_SHARED(__attribute__((aligned(16))) uint32_t, lds_words)
+    const uint32_t n16 = qview_prefix(v16, s_qpre16), n32 = qview_prefix(v32, s_qpre32);
+    if (!(n16 | n32)) return;                              // (uniform: nothing queued, nothing counted)
+    const uint16_t* const disp = bpe_merge_lds_tables<16, PAIR_NT, PAIR_NT, DISP_LDS, true>(t, lds_words);
+    const uint32_t grid = gridDim.x;
+    const uint32_t need_l = (n32 + PAIR_NL32 - 1u) / PAIR_NL32, need_s = (n16 + PAIR_NT - 1u) / PAIR_NT, need = need_l + need_s;   // full units
+    const uint32_t rounds = (need + grid - 1u) / grid;
+    const uint32_t slots = rounds * grid, spare = slots - need;                                         // (spare < grid: the product below stays in 32 bits)
+    const uint32_t slots_l = need_l + (spare * need_l + need - 1u) / need, slots_s = slots - slots_l;   // (slots_s >= need_s: the spare ones are split, never more)
+    // (more than one round: full units, so that only the workgroups the overflow is dealt to -- the last ones, whose first unit was a
+    // short one -- run a second unit at all; every workgroup running two half-filled units measured slower than k_bpe_merge_lds<32, ..>'s
+    // two rounds on out-of-distribution text, 0.686 against 0.645 ms a step)
+    const bool spread = rounds == 1u;
+    const uint32_t take_l = (n32 && spread) ? min((uint32_t)PAIR_NL32, ((n32 + slots_l - 1u) / slots_l + 63u) & ~63u) : (uint32_t)PAIR_NL32;
+    const uint32_t take_s = (n16 && spread) ? min((uint32_t)PAIR_NT, ((n16 + slots_s - 1u) / slots_s + 63u) & ~63u) : (uint32_t)PAIR_NT;
+    const uint32_t units_l = (n32 + take_l - 1u) / take_l, units = units_l + (n16 + take_s - 1u) / take_s;                       // (<= slots_l, <= slots)
+    for (uint32_t round = 0u; round < rounds; ++round) {
+        const uint32_t u = round * grid + ((round & 1u) ? (grid - 1u - blockIdx.x) : blockIdx.x);                               // (workgroup-uniform)
+        if (u < units_l)
+            bpe_merge_lds_unit<32, PAIR_NT, PAIR_NL32, true, false, false>(t, text, v32, s_qpre32, n32, v32, s_qpre32, n32, u * take_l, take_l, lds_words, disp, &s_probes, rows, tmp_ids, tmp_end);
+        else if (u < units)
+            bpe_merge_lds_unit<16, PAIR_NT, PAIR_NT, true, false, false>(t, text, v16, s_qpre16, n16, v16, s_qpre16, n16, (u - units_l) * take_s, take_s, lds_words, disp, &s_probes, rows, tmp_ids, tmp_end);
+    }
+    if (t.probes) {                                        // (uniform)
+        __syncthreads();
+        if (threadIdx.x == 0 && s_probes) atomicAdd(t.probes, s_probes);
+    }
+}
+template __global__ void k_bpe_merge_lds_pair<true>(DevTables, const uint8_t*, QView, QView, uint4*, uint32_t*, uint32_t*);
+template __global__ void k_bpe_merge_lds_pair<false>(DevTables, const uint8_t*, QView, QView, uint4*, uint32_t*, uint32_t*);
 constexpr int lds_merge_bytes(int S, int NT, bool disp_lds, bool sym_regs) { return ((sym_regs ? 1 : 2) * S * NT + 256 + 64) * 4 + (disp_lds ? DISP_LDS_MAX * 2 : 0); }
 template <int S, int NT, bool DISP_LDS, bool SYM_REGS>
 static int prepare_lds_merge() {
@@ -655,6 +723,30 @@ static void launch_lds_merge(hipStream_t st, int grid, const DevTables& t, const
         hipLaunchKernelGGL((k_bpe_merge_lds<S, NT, DISP_LDS, SYM_REGS, true>), dim3(grid), dim3(NT), lds_merge_bytes(S, NT, DISP_LDS, SYM_REGS), st, t, text, v, v2, rows, tmp_ids, tmp_end);
     else
         hipLaunchKernelGGL((k_bpe_merge_lds<S, NT, DISP_LDS, SYM_REGS, false>), dim3(grid), dim3(NT), lds_merge_bytes(S, NT, DISP_LDS, SYM_REGS), st, t, text, v, v2, rows, tmp_ids, tmp_end);
+}
+
+static int pair_merge_wg_per_cu = PAIR_WG_PER_CU;          // (prepare_pair_merge: what the runtime says is resident)
+static int prepare_pair_merge() {
+    const int lds = lds_merge_bytes(16, PAIR_NT, true, true);
+    int rc = (int)hipFuncSetAttribute((const void*)k_bpe_merge_lds_pair<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (rc == 0) rc = (int)hipFuncSetAttribute((const void*)k_bpe_merge_lds_pair<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_merge_bytes(16, PAIR_NT, false, true));
+    // what is resident: the smaller of the two instantiations' answers, and never more than the two workgroups a CU the kernel is laid
+    // out for (tkamd_profile_counters hands the figure out: tests/test_merge_pair_gpu.py asserts the two)
+    int n = 0, n_mem = 0;
+    if (rc == 0) rc = (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_bpe_merge_lds_pair<true>, PAIR_NT, (size_t)lds);
+    if (rc == 0) rc = (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_mem, (const void*)k_bpe_merge_lds_pair<false>, PAIR_NT, (size_t)lds_merge_bytes(16, PAIR_NT, false, true));
+    if (rc == 0 && (n < 1 || n_mem < 1)) rc = (int)hipErrorInvalidValue;        // (not even one workgroup fits)
+    if (rc == 0) pair_merge_wg_per_cu = std::min(std::min(n, n_mem), PAIR_WG_PER_CU);
+    return rc;
+}
+int pair_merge_occupancy() { return pair_merge_wg_per_cu; }
+// grid: the resident capacity (the kernel deals its units to whatever grid it is given)
+static void launch_lds_merge_pair(hipStream_t st, int n_cu, const DevTables& t, const uint8_t* text, const QView& v16, const QView& v32, uint4* rows, uint32_t* tmp_ids, uint32_t* tmp_end) {
+    const int grid = n_cu * pair_merge_wg_per_cu;
+    if (t.merge_bmask < (uint32_t)DISP_LDS_MAX)
+        hipLaunchKernelGGL(k_bpe_merge_lds_pair<true>, dim3(grid), dim3(PAIR_NT), lds_merge_bytes(16, PAIR_NT, true, true), st, t, text, v16, v32, rows, tmp_ids, tmp_end);
+    else
+        hipLaunchKernelGGL(k_bpe_merge_lds_pair<false>, dim3(grid), dim3(PAIR_NT), lds_merge_bytes(16, PAIR_NT, false, true), st, t, text, v16, v32, rows, tmp_ids, tmp_end);
 }
 
 // =================================================================================================
