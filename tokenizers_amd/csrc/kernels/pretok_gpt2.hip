@@ -49,20 +49,26 @@ __device__ __forceinline__ uint32_t utf8_at(const uint8_t* sb, int k, uint32_t* 
 }
 
 // =================================================================================================
-// K_pretok_gpt2_seq: the GPT-2 start predicate, bit-parallel PER LANE.  A lane owns 48 bytes and looks at a 64-byte
-// window around them (8 bytes back, 8 ahead), loaded as four 16-byte loads.  Each byte indexes a small LDS table
-// whose entries are one-hot flags spaced 8 bits apart (letter, digit, space-class, U+0020 | continuation,
-// apostrophe, multi-byte lead), so ONE shift-or per byte deposits a flag into up to four masks at once and eight
-// bytes later the finished groups move into 64-bit per-lane masks.  The regex then is the same mask algebra as
-// a ballot formulation's (shifts by one to three bytes; the halo absorbs the edge effects), but on the vector ALU,
-// one window per lane.  Non-ASCII code points and apostrophes are handled in two short loops over the set bits
-// of their masks (class lookup / literal check from memory).  ~13 instructions per byte instead of ~80 for the
-// lane-per-byte kernel of round 1.  The predicate: SURVEY Appendix A.1.
+// K_pretok_gpt2_seq: the GPT-2 start predicate, bit-parallel PER LANE, one lane per 64-bit word of the start mask.  A lane
+// loads its own 64 bytes (four 16-byte loads) and classifies each of them exactly once: a byte indexes a small LDS table
+// whose entries are one-hot flags spaced 8 bits apart (letter, digit, space-class, U+0020 | continuation, apostrophe,
+// multi-byte lead), so ONE shift-or per byte deposits a flag into up to four masks at once and eight bytes later the
+// finished groups move into 64-bit per-lane masks.  Multi-byte code points are resolved next (a short loop over their lead
+// bits; what a code point puts on the next word is the lane's spill).  Then the neighbours: the regex looks at most four
+// bytes ahead and three back, so a lane needs 8 bits of each mask of the word on either side -- one 64-bit word from the
+// lane below (with its spill), one 32-bit word from the lane above.  Inside a wavefront they come by __shfl_up / __shfl_down,
+// between the wavefronts of the workgroup through six words of LDS and one barrier, and at the two ends of the workgroup
+// lanes 0 and 1 of the first wavefront classify the 8 bytes beyond it themselves (both in one pass of the same code): no
+// workgroup waits for another.  The regex then is mask algebra on the vector ALU (pretok_gpt2_core.hpp gpt2_word_starts)
+// and every lane stores its word.  The predicate: SURVEY Appendix A.1.
+// (Until this form a lane decided the 48 bytes in the middle of a 64-byte window: every fourth byte was classified twice,
+// the loads were 8-byte aligned, four lanes' results were shuffled into three words.)
 // =================================================================================================
 // SQ_LUT_COPIES: replicas of the per-lane kernels' 2 KB flag tables.  ONE since round 5: lanes that read the same entry are a broadcast,
 // the same entry of two replicas is a bank conflict (four replicas: k_pretok_gpt2_seq 0.0521 -> 0.0495 ms, profiles/r5a_ab_c2.txt)
 constexpr int SQ_MAIN = 48, SQ_HALO = 8, SQ_LUT_COPIES = 1;
 struct __attribute__((packed, aligned(8))) SqChunk { uint32_t a, b, c, d; };
+constexpr int G2_WORDS_PER_BLOCK = 256;      // k_pretok_gpt2_seq: one lane per mask word
 
 // LEAD: the lead-byte mask of the same text rides along (char offsets over a text the pre-tokenizer reads as it came -- no normalizer, no
 // prefix space: k_leadmask's pass over the same 120 MB, 0.025 ms, is not launched then).
@@ -73,6 +79,8 @@ __global__ __launch_bounds__(256) void k_pretok_gpt2_seq(const uint8_t* __restri
                                                          const uint16_t* __restrict__ uc1, const uint8_t* __restrict__ uc2,
                                                          unsigned long long* __restrict__ startmask, unsigned long long* __restrict__ leadmask) {
     __shared__ Gpt2Flags lut[COPIES * 256];
+    __shared__ unsigned long long sh_up[4];      // [v]: what the last lane of wavefront v - 1 hands up ([0]: the word in front of the workgroup)
+    __shared__ uint32_t sh_down[4];              // [v]: what the first lane of wavefront v + 1 hands down ([3]: the word behind the workgroup)
     {
         const Gpt2Flags f = gpt2_byte_flags(threadIdx.x);    // 256 threads: one table entry each
 #pragma unroll
@@ -81,23 +89,37 @@ __global__ __launch_bounds__(256) void k_pretok_gpt2_seq(const uint8_t* __restri
     __syncthreads();
     const int64_t n_bytes = len_dev ? *len_dev : n_bytes_host;
     const int64_t n_words_host = (n_bytes_host >> 6) + 1;
-    const int64_t Lg = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    // loads, flag deposit and the regex as mask algebra: pretok_gpt2_core.hpp (the very function the CPU test runs)
-    uint64_t ld = 0;
-    const unsigned long long out = gpt2_lane_starts(text, n_bytes, n_words_host, (const uint64_t*)docmask,
-                                                    lut + (threadIdx.x & (COPIES - 1)) * 256, Lg, uc1, uc2, LEAD ? &ld : nullptr);
-    // four lanes' 48-bit results are three 64-bit mask words
-    const unsigned long long nxt = __shfl_down(out, 1, 64);
-    const int q = (int)(threadIdx.x & 3);
-    if (q < 3) {
-        const int64_t word = 3 * (Lg >> 2) + q;
-        if (word < n_words_host) startmask[word] = (out >> (16 * q)) | (nxt << (SQ_MAIN - 16 * q));
+    const int64_t w = (int64_t)blockIdx.x * G2_WORDS_PER_BLOCK + threadIdx.x;
+    const Gpt2Flags* my_lut = lut + (threadIdx.x & (COPIES - 1)) * 256;
+    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+    // the word's own 64 bytes (a word past the text: all zero, no load)
+    Gpt2Window m;
+    const Gpt2Spill spill = gpt2_word_classify(text, n_bytes, (const uint64_t*)docmask, my_lut, w, uc1, uc2, m);
+    const unsigned long long up = gpt2_pack_up(m, spill);
+    const uint32_t down = gpt2_pack_down(m);
+    unsigned long long from_below = __shfl_up(up, 1, 64);
+    uint32_t from_above = __shfl_down(down, 1, 64);
+    if (lane == 63 && wave < 3) sh_up[wave + 1] = up;
+    if (lane == 0 && wave > 0) sh_down[wave - 1] = down;
+    if (threadIdx.x < 2) {
+        // the ends of the workgroup: thread 0 the 8 bytes in front of its own word, thread 1 the 8 bytes behind the workgroup's last word
+        const int64_t pos = threadIdx.x == 0 ? (w << 6) - 8 : (w + G2_WORDS_PER_BLOCK - 1) << 6;
+        const bool there = threadIdx.x == 0 ? (w > 0 && (w << 6) < n_bytes) : pos < n_bytes;
+        Gpt2Halo h{0, 0, 0, 0, 0, 0, 0, 0};
+        Gpt2Spill hs{0, 0, 0};
+        if (there) h = gpt2_halo_classify(text, n_bytes, (const uint64_t*)docmask, my_lut, pos, uc1, uc2, &hs);
+        if (threadIdx.x == 0) sh_up[0] = gpt2_pack_up(h.L, h.N, h.S, h.SP, h.AP, h.D, hs);
+        else sh_down[3] = gpt2_pack_down(h.L, h.S, h.C, h.D);
     }
-    if constexpr (LEAD) {
-        const unsigned long long ld_n = __shfl_down((unsigned long long)ld, 1, 64);
-        if (q < 3) {
-            const int64_t word = 3 * (Lg >> 2) + q;
-            if (word < n_words_host) leadmask[word] = ((unsigned long long)ld >> (16 * q)) | (ld_n << (SQ_MAIN - 16 * q));
-        }
+    __syncthreads();
+    if (lane == 0) from_below = sh_up[wave];
+    if (lane == 63) from_above = sh_down[wave];
+    const Gpt2Halo hl = gpt2_take_left(from_below, w, m);
+    const Gpt2Halo hr = gpt2_take_right(from_above, w, n_bytes, spill);
+    uint64_t ld = 0;
+    const unsigned long long out = gpt2_word_starts(m, hl, hr, text, w, LEAD ? &ld : nullptr);
+    if (w < n_words_host) {
+        startmask[w] = out;
+        if constexpr (LEAD) leadmask[w] = (unsigned long long)ld;
     }
 }
