@@ -1,6 +1,6 @@
 // CPU harness for tokenizers_amd/csrc/kernels/{scan_util,epilogue}.hip: the epilogue kernels and their launchers -- special tokens,
 // truncation with its overflowing encodings, padding, pairs -- compiled for the host, UNCHANGED, under the SIMT shim of
-// tests/harness/simt/ and driven in the order csrc/capi.cpp drives them (run_pipeline: add_specials / finalize / finalize_pairs).
+// tests/harness/simt/ and driven in the order csrc/capi/epilogue.cpp drives them (Batch::add_specials / finalize / finalize_pairs).
 // Built and used by tests/test_epilogue_core.py: input = the wheel's plain encodings, expected output = the wheel's truncated /
 // padded / overflowing / pair encodings.  Test infrastructure; nothing in the product includes this.
 #include <hip/hip_runtime.h>   // the shim (-I tests/harness/simt)
@@ -36,7 +36,8 @@ extern "C" {
 
 // params[]: 0 add_special, 1 trunc_on, 2 trunc_max_length, 3 trunc_stride, 4 trunc_left, 5 trunc_strategy (0 LongestFirst 1 OnlyFirst 2 OnlySecond),
 //           6 pad_on, 7 pad_fixed, 8 pad_length, 9 pad_multiple, 10 pad_left, 11 pad_id, 12 pad_type_id, 13 want_overflow
-// single sequences: capi.cpp run_pipeline, lambdas add_specials / finalize
+// single sequences: capi/epilogue.cpp Batch::add_specials / Batch::finalize (their read-backs -- read_overflow_count, padded_capacity -- are
+// HIP copies there; here the kernels write host memory and the counts are read directly)
 int epi_single(const int64_t* tok_offsets, int64_t n_docs, const uint32_t* ids, const uint32_t* offsets, const uint32_t* word_ids,
                const uint32_t* prefix, int32_t n_prefix, const uint32_t* suffix, int32_t n_suffix, const uint32_t* params) {
     R = Result{};
@@ -91,7 +92,7 @@ int epi_single(const int64_t* tok_offsets, int64_t n_docs, const uint32_t* ids, 
     return R.err;
 }
 
-// pairs: documents 2i / 2i + 1 are sequence A / B (capi.cpp run_pipeline, lambda finalize_pairs); tpl = [n_tpl][3] kind, id, type id
+// pairs: documents 2i / 2i + 1 are sequence A / B (capi/epilogue.cpp Batch::finalize_pairs); tpl = [n_tpl][3] kind, id, type id
 int epi_pair(const int64_t* tok_offsets, int64_t n_pairs, const uint32_t* ids, const uint32_t* offsets, const uint32_t* word_ids,
              const uint32_t* tpl, int32_t n_tpl, const uint32_t* params) {
     R = Result{};

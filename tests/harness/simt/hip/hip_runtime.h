@@ -20,6 +20,7 @@
 #include <functional>
 #include <map>
 #include <mutex>
+#include <string>
 #include <vector>
 #include <sys/mman.h>
 
@@ -191,6 +192,18 @@ inline void launch(dim3 grid, dim3 block, std::function<void()> fn) {
     body() = outer;
     device_close();
 }
+// The launch log (tests/test_launch_sequence.py): what the host code enqueued, in order, one line per call -- a kernel launch with its
+// grid and block, an asynchronous memset / memcpy with its byte count, a stream synchronisation.  Off until it is first cleared.
+struct LaunchLog { std::mutex mu; bool on = false; std::string text; };
+inline LaunchLog& launch_log() { static LaunchLog l; return l; }
+inline void log_call(const char* what, const char* name, unsigned long long a, unsigned long long b) {
+    LaunchLog& l = launch_log();
+    if (!l.on) return;
+    char line[256];
+    snprintf(line, sizeof(line), what, name, a, b);
+    std::lock_guard<std::mutex> g(l.mu);
+    l.text += line;
+}
 inline uint64_t snap(int lane) { return waves()[cur()->tid.x >> 6].snap[lane]; }
 template <class T> inline uint64_t bits(T v) { uint64_t b = 0; memcpy(&b, &v, sizeof(T)); return b; }
 template <class T> inline T unbits(uint64_t b) { T r; memcpy(&r, &b, sizeof(T)); return r; }
@@ -216,7 +229,8 @@ inline int dpp_src(int lane, int ctrl) {
 #define blockIdx (simt::block_idx())
 #define blockDim (simt::block_dim())
 #define gridDim (simt::grid_dim())
-#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) simt::launch((grid), (block), [&]() { kernel(__VA_ARGS__); })
+#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
+    (simt::log_call("launch %s grid=%llu block=%llu\n", #kernel, dim3(grid).x, dim3(block).x), simt::launch((grid), (block), [&]() { kernel(__VA_ARGS__); }))
 
 // ---- device language ----
 inline void __syncthreads() { simt::block_barrier(); }
@@ -364,12 +378,30 @@ inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
 namespace simt { inline void check_kind(const void*, const void*, hipMemcpyKind) {} }
 #endif
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) { simt::check_kind(d, s, k); simt::device_open(); memmove(d, s, n); simt::device_close(); return hipSuccess; }
-inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t) { return hipMemcpy(d, s, n, k); }
+inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t) {
+    static const char* const kinds[4] = {"HostToHost", "HostToDevice", "DeviceToHost", "DeviceToDevice"};
+    simt::log_call("memcpy %s bytes=%llu\n", kinds[(int)k & 3], n, 0);
+    return hipMemcpy(d, s, n, k);
+}
 inline hipError_t hipMemset(void* d, int v, size_t n) { simt::device_open(); memset(d, v, n); simt::device_close(); return hipSuccess; }
-inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { return hipMemset(d, v, n); }
+inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { simt::log_call("memset%s bytes=%llu\n", "", n, 0); return hipMemset(d, v, n); }
 inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = malloc(1); return hipSuccess; }
 inline hipError_t hipStreamDestroy(hipStream_t s) { free(s); return hipSuccess; }
-inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+inline hipError_t hipStreamSynchronize(hipStream_t) { simt::log_call("sync%s\n", "", 0, 0); return hipSuccess; }
+// the launch log's two entry points (weak: this header is part of every translation unit of the build)
+extern "C" __attribute__((weak, used, visibility("default"))) void simt_launch_log_clear() {
+    simt::LaunchLog& l = simt::launch_log();
+    std::lock_guard<std::mutex> g(l.mu);
+    l.on = true;
+    l.text.clear();
+}
+// copies at most `cap` bytes of the log to `buf`; returns the log's length
+extern "C" __attribute__((weak, used, visibility("default"))) size_t simt_launch_log_read(char* buf, size_t cap) {
+    simt::LaunchLog& l = simt::launch_log();
+    std::lock_guard<std::mutex> g(l.mu);
+    if (buf && cap) memcpy(buf, l.text.data(), std::min(cap, l.text.size()));
+    return l.text.size();
+}
 inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
 inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = nullptr; return hipSuccess; }
 inline hipError_t hipDeviceEnablePeerAccess(int, unsigned) { return hipSuccess; }

@@ -34,7 +34,8 @@ static_assert(TEXT_PAD == TKAMD_TEXT_PAD, "the kernels rely on the slack the ABI
 #include "capi/support.cpp"      // errors, the fork() guard, RCCL opened at first use, the rendezvous objects of a sharded call, DevBuf
 #include "capi/handle.cpp"      // Workspace, tkamd_tokenizer, the pinned-block pool, tkamd_batch / tkamd_text
 #include "capi/tables.cpp"      // stage timers, the device tables made at load: upload, the load-time proof of the whole-word table, the short-word and hot tables
-#include "capi/pipeline.cpp"      // the kernel sequence of one batch (run_pipeline), its queues and workspace sizes, the synchronisation and error mapping
+#include "capi/pipeline.cpp"      // the kernel sequence of one batch (run_pipeline and its stages), its queues and workspace sizes, the synchronisation and error mapping
+#include "capi/epilogue.cpp"      // the epilogues of a batch: special tokens, truncation with its overflowing encodings, padding, pairs
 #include "capi/pool.cpp"      // the workspace pool of a handle
 #include "capi/api_handle.cpp"      // extern "C": handles, device-buffer entries
 #include "capi/sharding.cpp"      // one host-entry call over the devices of a multi-device handle

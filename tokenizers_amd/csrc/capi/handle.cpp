@@ -51,7 +51,7 @@ struct Workspace {
     const int64_t* last_inp_off = nullptr;      // mixed call: the inputs' CSR over the sequences (else null)
     int64_t last_n_inputs = -1;
     DevBuf w_inp_off;                           // ... its validated copy
-    DevBuf w_mask_dirty;                        // one word: the four added-token match masks may hold bits (run_pipeline scatter_masks)
+    DevBuf w_mask_dirty;                        // one word: the four added-token match masks may hold bits (Batch::scatter_masks, capi/pipeline.cpp)
     int64_t last_n_bytes = 0;
     uint32_t last_flags = 0;
     tkamd_device_result last_result{};
@@ -102,7 +102,7 @@ struct tkamd_tokenizer {
     std::atomic<int> claims_pause{0};
     // A tokenizer with added tokens runs a batch as if its text held none (one detection pass per pattern set instead of match / resolve /
     // scatter / piece launches that find nothing in natural text); a batch that did hold one is run again with the matching passes and
-    // the handle's next added_spec_len batches do not speculate (run_pipeline, finish_batch).
+    // the handle's next added_spec_len batches do not speculate (Batch::build_x_text, finish_batch).
     std::atomic<int> added_spec_pause{0};
     int added_spec_len = 32;     // (test hook TKAMD_ADDED_SPEC: 0 never speculate; n: the pause behind a miss)
     int claims_pause_len = 32;   // (test hook TKAMD_CLAIMS_PAUSE; 0: never pause)
