@@ -533,6 +533,17 @@ static void build_decode_tables(HostModel& m, const JsonValue* root, const std::
     std::vector<DecEl> chain;
     auto replace_lit = [](const std::string& t, const std::string& from, const std::string& to) {
         std::string out;
+        if (from.empty()) {                    // str::replace("", to): the empty pattern matches in front of every char and at the end
+            out = to;
+            for (size_t i = 0; i < t.size();) {
+                size_t j = i + 1;
+                while (j < t.size() && ((uint8_t)t[j] & 0xC0u) == 0x80u) ++j;
+                out.append(t, i, j - i);
+                out += to;
+                i = j;
+            }
+            return out;
+        }
         size_t pos = 0;
         for (;;) {
             const size_t hit = t.find(from, pos);
@@ -684,9 +695,10 @@ static void build_decode_tables(HostModel& m, const JsonValue* root, const std::
             first = replace_all("");
             rest = replace_all(" ");
         } else if (m.decoder == DEC_CTC) {
+            // (an empty pad_token replaces nothing by nothing; an empty word_delimiter_token puts a space in front of every char of
+            // the cleaned token and one at its end, as str::replace does -- " " for a token the pad emptied)
             first = replace_lit(t, ctc_pad, "");
-            if (ctc_pad.empty()) first = t;
-            if (cleanup) { first = wp_cleanup(first); if (!ctc_delim.empty()) first = replace_lit(first, ctc_delim, " "); }
+            if (cleanup) first = replace_lit(wp_cleanup(first), ctc_delim, " ");
             rest = first;
         } else if (m.decoder == DEC_FUSE || m.decoder == DEC_BYTE_FALLBACK || m.decoder == DEC_CHAIN) {
             std::string u = t;
