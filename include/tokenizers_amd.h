@@ -85,7 +85,10 @@ extern "C" {
                                      passes when the call synchronises (the host entries before they return, the device entry in
                                      tkamd_device_sync) -- results are the reference's either way.  A caller of the device entry that
                                      consumes the results stream-ordered behind the call, WITHOUT tkamd_device_sync in between, sets this
-                                     flag: the matching passes run outright.                                                            */
+                                     flag: the matching passes run outright.  The same holds for a tokenizer with an NFC normalizer: a
+                                     batch runs over the text as it came behind an exact quick check and is run again through the
+                                     normalizer when the call synchronises and the check failed; with this flag it is normalized outright.
+                                     Without the flag AND without tkamd_device_sync a text that is not NFC would be encoded un-normalized. */
 #define TKAMD_TEXT_PAD 64
 
 typedef struct tkamd_tokenizer tkamd_tokenizer;  /* immutable after creation; owns device tables */

@@ -60,6 +60,8 @@ struct Workspace {
     int last_ntok_slot = 1;
     uint32_t last_counters[CNT_COUNT] = {0};
     bool force_general = false;                  // the next run of the pipeline does not speculate on the added tokens (it repeats a batch that met one)
+    bool force_nfc = false;                      // the next run of the pipeline normalizes outright (it repeats a batch k_nfc_check could not vouch for)
+    bool last_note_nfc = false;                  // the batch synchronised last was run over the text as it came and holds a lane that is not known to be NFC
     bool last_note_added = false;                // the batch synchronised last was speculative and met an added token's content (read_scalars)
     bool last_used_claims = false;               // the batch enqueued last ran with the in-batch claims
     ~Workspace() {
@@ -90,7 +92,7 @@ struct tkamd_tokenizer {
     DevBuf t_at_id[2], t_at_flags[2], t_at_blob[2], t_at_off[2], t_at_first[2];   // AddedVocabulary patterns of the two matching passes
     DevBuf t_pp_single, t_pp_single_plain;      // the single layout as pieces (the single inputs of a mixed batch)
     DevBuf t_pp_pair, t_pp_pair_plain;   // pair template of the post-processor with / without its special tokens: [pieces][3]
-    DevBuf t_pp_prefix, t_pp_suffix, t_pp_prefix_ty, t_pp_suffix_ty, t_bn1, t_bn2, t_bn_map, t_merge_disp, t_dec_entry, t_dec_blob, t_trie;
+    DevBuf t_pp_prefix, t_pp_suffix, t_pp_prefix_ty, t_pp_suffix_ty, t_bn1, t_bn2, t_bn_map, t_nfc1, t_nfc2, t_nfc_map, t_merge_disp, t_dec_entry, t_dec_blob, t_trie;
     int n_cu = 256;
     int n_direct = 0;
     int n_hot = 0;
@@ -104,6 +106,11 @@ struct tkamd_tokenizer {
     // scatter / piece launches that find nothing in natural text); a batch that did hold one is run again with the matching passes and
     // the handle's next added_spec_len batches do not speculate (Batch::build_x_text, finish_batch).
     std::atomic<int> added_spec_pause{0};
+    // the same for the NFC normalizer: batches run over the text as it came behind k_nfc_check; one that fails the check is run again
+    // through the normalizer's kernels and the next nfc_spec_len batches normalize outright.  nfc_reruns counts the batches run again.
+    std::atomic<int> nfc_spec_pause{0};
+    std::atomic<uint32_t> nfc_reruns{0};
+    int nfc_spec_len = 32;
     int added_spec_len = 32;     // (test hook TKAMD_ADDED_SPEC: 0 never speculate; n: the pause behind a miss)
     int claims_pause_len = 32;   // (test hook TKAMD_CLAIMS_PAUSE; 0: never pause)
     std::atomic<uint32_t> q16_div{4};    // capacity of the <= 16-byte queue = n_bytes / q16_div (raised to the worst case when a batch overflows it)

@@ -12,11 +12,13 @@ struct QueueSizes {
     size_t total;
 };
 // What the error word of a batch that has just been read back asks for besides failing: the batch again with a larger <= 16-byte queue
-// (ERR_QUEUE_FULL alone), or again with the added tokens' matching passes (NOTE_ADDED_SEEN: it was run as if its text held none).
+// (ERR_QUEUE_FULL alone), or again with the added tokens' matching passes (NOTE_ADDED_SEEN: it was run as if its text held none), or again
+// through the NFC normalizer's kernels (NOTE_NFC_SEEN: it was run over the text as it came, and k_nfc_check cannot vouch for all of it).
 static bool rerun_wanted(tkamd_tokenizer* t, Workspace* w, int raw) {
     const int err = raw & ~NOTE_BITS;
     bool again = false;
     if (raw & NOTE_ADDED_SEEN) { t->added_spec_pause = t->added_spec_len; w->force_general = true; again = true; }      // (force_general: the run that follows, whoever else draws on the pause)
+    if (raw & NOTE_NFC_SEEN) { t->nfc_spec_pause = t->nfc_spec_len; w->force_nfc = true; ++t->nfc_reruns; again = true; }
     if (err == ERR_QUEUE_FULL && t->q16_div > 1) { t->q16_div = t->q16_div > 2 ? 2 : 1; again = true; }
     return again;
 }
@@ -86,6 +88,7 @@ struct Batch {
     // check_request
     bool mixed = false, want_words = false, want_meta = false, add_special = false, prefix_space = false, metaspace = false, words_in = false, pairs = false;
     bool typed_single = false, has_epilogue = false, want_overflow = false;
+    bool nfc_general = false;      // behind an NFC normalizer: this run normalizes (else X is the text as it came, behind k_nfc_check)
     uint32_t off_mode = 0, mcap = 0;
     int64_t n_x = 0, e_n = 0, W0 = 0, W = 0;      // e_n: encodings the epilogues see; W0 / W: mask words over the original / the X text
     // zero_batch_state: the scalars' slots, the claims
@@ -118,7 +121,7 @@ struct Batch {
     AddedArgs args_of(int c);
     void scatter_masks(int64_t n_text, const int64_t* len_dev, bool with_end);
     const int64_t* build_pieces(const int64_t* doc_csr, int64_t n_text, const int64_t* len_dev);
-    void normalize_bert(); void shift_behind_prefix_spaces(); void metaspace_front(); void read_ntext();
+    void normalize_bert(); void normalize_nfc(); void shift_behind_prefix_spaces(); void metaspace_front(); void read_ntext();
     // helpers of run_model / compact_and_meta
     void* phases_of(int which);
     void open_word_cache();
@@ -156,7 +159,19 @@ void Batch::check_request() {
     mcap = have_added_tokens ? (uint32_t)std::min<size_t>((size_t)n_bytes / std::max<size_t>(at_min_len, 1) + 16, 0x7FFFFFF0u) : 0u;
     // (a prefix space goes in front of every piece: every document, and what follows every match)
     // (the "▁" front: a ' ' becomes three bytes, and a "▁" of three goes in front of a piece -- every document, and what follows every match)
-    n_x = (hm.norm == NORM_BERT) ? 3 * n_bytes + 64
+    // NFC: almost all text is NFC already, so a batch runs over the text as it came with k_nfc_check reading it once; one the check cannot
+    // vouch for is run again through the normalizer (rerun_wanted), the handle's next nfc_spec_len batches normalize outright, and so does
+    // every batch of a caller that never synchronises through the library (TKAMD_NO_SPECULATION).  (NFC grows UTF-8 text at most 3 x.)
+    if (hm.norm == NORM_NFC) {
+        nfc_general = w->force_nfc || (flags & TKAMD_NO_SPECULATION) || t->nfc_spec_len <= 0;
+        w->force_nfc = false;
+        if (!nfc_general) {
+            int p = t->nfc_spec_pause.load();
+            while (p > 0 && !t->nfc_spec_pause.compare_exchange_weak(p, p - 1)) {}
+            nfc_general = p > 0;
+        }
+    }
+    n_x = (hm.norm == NORM_BERT || nfc_general) ? 3 * n_bytes + 64
           : metaspace ? 3 * n_bytes + 3 * (n_docs + 2 * (int64_t)mcap + 1) + 64
           : n_bytes + (prefix_space ? n_docs + (int64_t)mcap : 0);
     if (n_x >= (int64_t)0xFFFFFF00ll) throw Invalid("batch larger than 4 GiB: split it (byte offsets are 32-bit on the device)");
@@ -187,7 +202,9 @@ void Batch::check_request() {
 
 // Reserves the workspace, decides the claims and zeroes what the batch needs zeroed; the result starts as the plain encodings' arrays.
 void Batch::zero_batch_state() {
-    reserve_workspace(t, w, n_x, n_docs, flags, want_meta);
+    // (a device-entry caller holds the result pointers across a re-run: behind NFC the re-run's bound is the normalizer's, three times the
+    // text, so its workspace is sized for that from the first run on -- grow-only buffers do not move then)
+    reserve_workspace(t, w, (hm.norm == NORM_NFC && w->device_bound) ? 3 * n_bytes + 64 : n_x, n_docs, flags, want_meta);
     sc = w->w_scalars.as<int64_t>();
     d_npretok = sc + SC_NPRETOK;
     d_ntok_total = sc + SC_NTOK;
@@ -213,6 +230,7 @@ void Batch::zero_batch_state() {
     z.add(sc, SC_SLOTS * 8);
     // (behind BertNormalizer the mask covers the bound of the normalised text, three times the input: the words that text really has
     // are zeroed behind the normaliser, next to the slack of the text -- launch_zero_tail below)
+    // (behind NFC's general path the whole bound is zeroed all the same: the byte-level pre-tokenizers walk the mask words of the bound, and that path is the rare one)
     if (!(hm.norm == NORM_BERT || metaspace)) z.add(w->w_docmask.p, (size_t)(W + 1) * 8);
     z.add(w->w_qcount.p, (size_t)QCNT_WORDS * 4);
     z.add(w->w_cstate.p, cstate_bytes);
@@ -238,7 +256,7 @@ void Batch::zero_batch_state() {
     out->d_tok_offsets = w->w_tok_offsets.as<int64_t>();
     out->d_n_tokens = d_ntok_total;
     out->d_n_pretokens = d_npretok;
-    out->ids_capacity = n_x + 4;          // what w_ids holds (a token covers a byte of the X text); the epilogues size theirs from the data
+    out->ids_capacity = ((hm.norm == NORM_NFC && w->device_bound) ? 3 * n_bytes + 64 : n_x) + 4;          // what w_ids holds (a token covers a byte of the X text); the epilogues size theirs from the data
     out->d_offsets = out->d_word_ids = out->d_pad_counts = out->d_enc_docs = out->d_enc_parts = nullptr;
     out->d_type_ids = out->d_seq_ids = nullptr;
     out->d_n_encodings = nullptr;
@@ -260,7 +278,7 @@ void Batch::validate_inputs() {
     // copy on its way (it runs behind the whole validation, so it knows the verdict) -- two launches instead of four
     // (every other tokenizer takes the general order).  A malformed CSR still never turns into an access outside the buffers; the batch
     // fails with TKAMD_ERR_INVALID as before.
-    lean = n_bytes > 0 && hm.at[0].size() == 0 && hm.at[1].size() == 0 && hm.norm == NORM_NONE && !prefix_space &&
+    lean = n_bytes > 0 && hm.at[0].size() == 0 && hm.at[1].size() == 0 && (hm.norm == NORM_NONE || (hm.norm == NORM_NFC && !nfc_general)) && !prefix_space &&
            (hm.pretok == PT_BYTELEVEL_GPT2 || hm.pretok == PT_BYTELEVEL_NOREGEX);
     raw_doc_off = d_doc_off;
     if (!lean) {
@@ -356,6 +374,32 @@ void Batch::normalize_bert() {
     launch_bert_normalize(st, bt, d_text, n_bytes, d_doc_off, n_docs, verbatim, w->w_keepmask.as<uint8_t>(), w->w_kprefix.as<uint32_t>(),
                           w->w_bsum.as<uint32_t>(), w->w_wbase.as<uint32_t>(), d_xlen, w->w_ntext.as<uint8_t>(), (uint32_t*)norig, (uint32_t*)norig_e,
                           w->w_ndoc_off.as<int64_t>(), d_err);
+    launch_zero_tail(st, w->w_ntext.as<uint8_t>(), d_xlen, TKAMD_TEXT_PAD, w->w_docmask.as<ull>(), W + 1, t->n_cu * 4);
+    pf.end();
+    if (have_raw) launch_translate_matches_norm(st, mlist, n_match, w->w_keepmask.as<uint8_t>(), w->w_wbase.as<uint32_t>(), n_bytes, d_xlen);
+    read_ntext();
+}
+
+void Batch::normalize_nfc() {
+    // ---- NFC, the general path: text -> normalised text + the source char of every normalised byte (kernels/nfc.hip); the pieces are the
+    // documents and what lies between the matches of pass 1, which are copied verbatim ----
+    w->w_keepmask.reserve(bn_olen_bytes(n_bytes));
+    w->w_kprefix.reserve((size_t)(W0 + 1) * 4);
+    w->w_wbase.reserve((size_t)(W0 + 1) * 4);
+    w->w_ms_dmask.reserve((size_t)(W0 + 2) * 8);
+    HIP_CHECK(hipMemsetAsync(w->w_ms_dmask.p, 0, (size_t)(W0 + 2) * 8, st));
+    launch_mark_doc_starts_n(st, d_doc_off, n_docs, n_bytes, nullptr, w->w_ms_dmask.as<ull>(), d_err);
+    const ull* verbatim = nullptr;
+    if (have_raw) {
+        scatter_masks(n_bytes, nullptr, false);
+        launch_mask_or2(st, w->w_boundmask.as<ull>(), w->w_matchmask.as<ull>(), w->w_spanmask.as<ull>(), W0 + 1);
+        verbatim = w->w_boundmask.as<ull>();
+        launch_nfc_bound(st, w->w_ms_dmask.as<ull>(), verbatim, W0 + 1);
+    }
+    const NfcTables nt{t->t_nfc1.as<uint16_t>(), t->t_nfc2.as<uint8_t>(), t->t_nfc_map.as<MergeSlot>(), hm.nfc_mask, hm.nfc_seed};
+    pf.begin("nfc_normalize");
+    launch_nfc_normalize(st, nt, d_text, n_bytes, d_doc_off, n_docs, verbatim, w->w_ms_dmask.as<ull>(), w->w_keepmask.as<uint8_t>(), w->w_kprefix.as<uint32_t>(),
+                         w->w_bsum.as<uint32_t>(), w->w_wbase.as<uint32_t>(), d_xlen, w->w_ntext.as<uint8_t>(), (uint32_t*)norig, w->w_ndoc_off.as<int64_t>(), d_err);
     launch_zero_tail(st, w->w_ntext.as<uint8_t>(), d_xlen, TKAMD_TEXT_PAD, w->w_docmask.as<ull>(), W + 1, t->n_cu * 4);
     pf.end();
     if (have_raw) launch_translate_matches_norm(st, mlist, n_match, w->w_keepmask.as<uint8_t>(), w->w_wbase.as<uint32_t>(), n_bytes, d_xlen);
@@ -476,12 +520,13 @@ void Batch::build_x_text() {
     }
     x_text = d_text;
     x_doc_off = d_doc_off;
-    if (hm.norm == NORM_BERT || prefix_space || metaspace) {
+    const bool normalized = hm.norm == NORM_BERT || nfc_general;      // X is a normaliser's output (the BnOlen layout, norig without ends)
+    if (normalized || prefix_space || metaspace) {
         w->w_ntext.reserve((size_t)n_x + TKAMD_TEXT_PAD);
         w->w_ndoc_off.reserve((size_t)(n_docs + 2) * 8);
         // (the prefix-space copy leaves nothing unwritten either, but only the normaliser's path has been taken through the tests without
         // this memset: k_zero_tail behind launch_bert_normalize zeroes the slack behind the text it wrote)
-        if (hm.norm != NORM_BERT && !metaspace) HIP_CHECK(hipMemsetAsync(w->w_ntext.p, 0, (size_t)n_x + TKAMD_TEXT_PAD, st));
+        if (!normalized && !metaspace) HIP_CHECK(hipMemsetAsync(w->w_ntext.p, 0, (size_t)n_x + TKAMD_TEXT_PAD, st));
         // test hook TKAMD_POISON_NTEXT (with TKAMD_TEST_HOOKS=1): the normaliser's output buffer starts every batch as 0xFF, so a kernel that
         // reads it beyond *x_len + TEXT_PAD -- bounded by the host's n_x instead of the device length -- changes a result instead of
         // meeting zeros an earlier batch or the allocator happened to leave (tests/test_parity_gpu.py runs the BertNormalizer fixtures so)
@@ -499,14 +544,22 @@ void Batch::build_x_text() {
             norig = w->w_norig.as<uint32_t>();
             // (behind BertNormalizer the END of a byte's original range follows from its start and the original text -- kernels/output.hip
             // norig_end: 4 bytes per normalised byte less to write and to read; the prefix-space copy keeps per-byte ends)
-            if (hm.norm != NORM_BERT && !metaspace) {
+            if (!normalized && !metaspace) {
                 w->w_norig_e.reserve(((size_t)n_x + 4) * 4);
                 norig_e = w->w_norig_e.as<uint32_t>();
             }
         }
     }
     if (hm.norm == NORM_BERT) normalize_bert();
-    n_in = hm.norm == NORM_BERT ? n_x : n_bytes;
+    if (hm.norm == NORM_NFC) {
+        if (nfc_general) normalize_nfc();
+        else {
+            pf.begin("nfc_check");
+            launch_nfc_check(st, NfcTables{t->t_nfc1.as<uint16_t>(), t->t_nfc2.as<uint8_t>(), t->t_nfc_map.as<MergeSlot>(), hm.nfc_mask, hm.nfc_seed}, d_text, n_bytes, d_err);
+            pf.end();
+        }
+    }
+    n_in = normalized ? n_x : n_bytes;
     if (spec && setB.size() > 0) {
         pf.begin("added_token_match2");
         launch_added_detect(st, args_of(1), x_text, n_in, x_len_dev, d_err);
@@ -527,7 +580,7 @@ void Batch::build_x_text() {
         pf.begin("added_token_match2");
         launch_added_match(st, args_of(1), x_text, n_in, x_len_dev, seg, nseg_bound, nseg_dev, have_raw ? w->w_matchmask.as<ull>() : nullptr, t->dt.uc1, t->dt.uc2,
                            w->w_candmask.as<ull>(), w->w_match_docs.as<uint32_t>(), d_counters + CNT_MATCH_DOCS2, mlist, n_match, mcap,
-                           hm.norm == NORM_NONE ? MATCH_LEN_ORIG : 0u, d_err);
+                           normalized ? 0u : MATCH_LEN_ORIG, d_err);
         pf.end();
     }
     if (have_added && !prefix_space && !metaspace) {
@@ -934,7 +987,7 @@ int finish_batch(tkamd_tokenizer* t, Workspace* w, hipStream_t st, int64_t* n_to
     // (rerun_wanted: half the bytes covers every text whose queued pre-tokens have two bytes or more (a word and its separator); one entry
     // per byte covers the rest (runs of one-byte pre-tokens the vocabulary does not know, e.g. punctuation under WordPiece); a speculative
     // batch that met an added token's content is run again with the matching passes -- whatever else its error word says: that run decides)
-    while (rerun_wanted(t, w, bits | (w->last_note_added ? NOTE_ADDED_SEEN : 0))) {
+    while (rerun_wanted(t, w, bits | (w->last_note_added ? NOTE_ADDED_SEEN : 0) | (w->last_note_nfc ? NOTE_NFC_SEEN : 0))) {
         tkamd_device_result again{};
         run_pipeline(t, w, w->last_text, w->last_doc_off, w->last_n_docs, w->last_n_bytes, w->last_seq_off, w->last_n_seqs, w->last_flags, st, &again,
                      w->last_inp_off, w->last_n_inputs);
@@ -957,6 +1010,7 @@ int read_scalars(tkamd_tokenizer* t, Workspace* w, hipStream_t st, int64_t* n_to
     HIP_CHECK(hipStreamSynchronize(st));
     int err = *(int*)&host[SC_ERR] & ~NOTE_BITS;             // (notes of the normalizer and of the added tokens' speculation, not errors)
     w->last_note_added = (*(int*)&host[SC_ERR] & NOTE_ADDED_SEEN) != 0;
+    w->last_note_nfc = (*(int*)&host[SC_ERR] & NOTE_NFC_SEEN) != 0;
     memcpy(w->last_counters, &host[SC_COUNTERS], sizeof(w->last_counters));
     if (w->last_used_claims && t->claims_pause_len > 0) {
         // the claims' yield, counted by the lookup itself: candidates it looked at and how many of them were another pre-token's word.
@@ -977,6 +1031,9 @@ int error_from_bits(int bits) {
         return set_error(TKAMD_ERR_UNSUPPORTED, "BertNormalizer strip_accents: a character with a non-zero combining class that survives the Mn filter "
                                                 "stands in a run of more than 48 combining characters; NFD's canonical ordering of such a run is not built "
                                                 "on the device");
+    if (bits & ERR_NFC_SEGMENT)
+        return set_error(TKAMD_ERR_UNSUPPORTED, "NFC: a character is followed by more than 48 combining characters (or other characters that may compose with it); "
+                                                "the normalization of such a run is not built on the device");
     if (bits & ERR_ADDED_SPLIT) return set_error(TKAMD_ERR_INVALID, "AddedVocabulary bad split");
     if (bits & ERR_INTERNAL) return set_error(TKAMD_ERR_DEVICE, "internal invariant violated");
     if (bits & ERR_QUEUE_FULL) return set_error(TKAMD_ERR_DEVICE, "work queues still too small after growing them");

@@ -213,6 +213,8 @@ int tkamd_profile_counters(tkamd_tokenizer* t, uint32_t* out, int n) {
         if (n > 13) out[13] = (uint32_t)pair_merge_occupancy();            // (workgroups of k_bpe_merge_lds_pair resident per CU: its grid is that x the CUs)
         if (n > 14) out[14] = (uint32_t)std::max(0, t->added_spec_pause.load());      // (batches that will not speculate on the added tokens: a batch met one)
         if (n > 15) out[15] = t->q16_div;                                  // (the <= 16-byte queue's divisor: shrinks when a batch had to be run again)
+        if (n > 16) out[16] = (uint32_t)std::max(0, t->nfc_spec_pause.load());        // (batches that will run the NFC normalizer outright: a batch failed the quick check)
+        if (n > 17) out[17] = t->nfc_reruns.load();                        // (batches run again through the NFC normalizer since the handle was made)
         if (t->device >= 0 && w->w_qcount.p && !g_forked) {             // queue fills of the last batch: the sub-queue counters, summed per queue
             HIP_CHECK(hipSetDevice(t->device));
             HIP_CHECK(hipDeviceSynchronize());

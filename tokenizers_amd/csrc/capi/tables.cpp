@@ -91,6 +91,9 @@ void upload_tables(tkamd_tokenizer* t) {
     upload(t->t_bn1, hm.bn_stage1);
     upload(t->t_bn2, hm.bn_stage2);
     upload(t->t_bn_map, hm.bn_map);
+    upload(t->t_nfc1, hm.nfc_stage1);
+    upload(t->t_nfc2, hm.nfc_stage2);
+    upload(t->t_nfc_map, hm.nfc_map);
     for (int c = 0; c < 2; ++c) {
         upload(t->t_at_blob[c], hm.at[c].blob);
         upload(t->t_at_off[c], hm.at[c].off);

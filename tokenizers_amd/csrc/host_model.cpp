@@ -1,6 +1,7 @@
 // tokenizer.json -> flat tables.  See host_model.hpp.
 #include "host_model.hpp"
 #include "bert_norm_core.hpp"
+#include "nfc_core.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -108,6 +109,27 @@ const BnNfdRow kBnNFD[] = {
 #include "bert_norm_tables.inc"
 };
 #undef BN_WANT_NFD
+struct NfcDecompRow {
+    uint32_t cp, d[4];
+};
+struct NfcCompRow {
+    uint32_t a, b, c;
+};
+#define NFC_WANT_RUNS
+const UcRun kNfcRuns[] = {
+#include "nfc_tables.inc"
+};
+#undef NFC_WANT_RUNS
+#define NFC_WANT_DECOMP
+const NfcDecompRow kNfcDecomp[] = {
+#include "nfc_tables.inc"
+};
+#undef NFC_WANT_DECOMP
+#define NFC_WANT_COMP
+const NfcCompRow kNfcComp[] = {
+#include "nfc_tables.inc"
+};
+#undef NFC_WANT_COMP
 
 // GPT-2 bytes <-> unicode map, pre_tokenizers/byte_level.rs:15-39: printable bytes map to
 // themselves, the other 68 bytes to U+0100+n in byte order.
@@ -344,6 +366,23 @@ void build_bert_norm(HostModel& m) {
     for (const BnMapRow& r : kBnLC) add(r, 1);
     for (const BnNfdRow& r : kBnNFD) items.push_back(MergeSlot{r.cp, 2u, r.packed, 0u});      // kind 2: classes of the NFD pieces (bert_norm_core.hpp)
     build_pair_table(items, &m.bn_map, &m.bn_mask, &m.bn_seed);
+}
+
+// NFC data: flags as a 2-stage table; one pair table with the full canonical decompositions -- (cp, 0) -> three code points packed 21
+// bits each, (cp, 1) -> the fourth -- and the primary composites (first, second) -> composite (a second is never below U+0300)
+void build_nfc_tables(HostModel& m) {
+    std::vector<uint8_t> flat(0x110000, 0);
+    for (const UcRun& r : kNfcRuns)
+        for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
+    two_stage(flat, &m.nfc_stage1, &m.nfc_stage2);
+    std::vector<MergeSlot> items;
+    for (const NfcDecompRow& r : kNfcDecomp) {
+        const uint64_t v = (uint64_t)r.d[0] | ((uint64_t)r.d[1] << 21) | ((uint64_t)r.d[2] << 42);
+        items.push_back(MergeSlot{r.cp, 0u, (uint32_t)v, (uint32_t)(v >> 32)});
+        if (r.d[3] != NFC_FILL) items.push_back(MergeSlot{r.cp, 1u, r.d[3], 0u});
+    }
+    for (const NfcCompRow& r : kNfcComp) items.push_back(MergeSlot{r.a, r.b, r.c, 0u});
+    build_pair_table(items, &m.nfc_map, &m.nfc_mask, &m.nfc_seed);
 }
 
 // The top-level alternatives of a regex source: cut at every '|' outside (...) and [...]; a backslash escapes the next character.
@@ -797,6 +836,15 @@ HostModel HostModel::from_json(const char* json, size_t len) {
             m.bn_lowercase = norm->get_bool("lowercase", true);
             const JsonValue* sa = norm->get("strip_accents");
             m.bn_strip_accents = (sa && sa->is_bool()) ? sa->b : m.bn_lowercase;  // normalizers/bert.rs:124
+        } else if (t == "NFC") {
+            m.norm = NORM_NFC;
+        } else if (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() &&
+                   std::any_of(norm->get("normalizers")->arr.begin(), norm->get("normalizers")->arr.end(),
+                               [](const JsonPtr& v) { return v && v->is_object() && v->get_str("type") == "NFC"; })) {
+            // NFC alone inside a Sequence is NFC; next to any other normalizer the alignment of one is the input of the other: not on the path
+            if (norm->get("normalizers")->arr.size() != 1)
+                throw Unsupported("normalizer: NFC inside a longer Sequence is outside the hot path (only NFC alone, or Sequence[NFC], is on it)");
+            m.norm = NORM_NFC;
         } else if (t == "Sequence" || t == "Replace" || t == "Prepend") {
             // the "▁" normalizers of SentencePiece conversions: Sequence[Prepend("▁"), Replace(" " -> "▁")] (Llama-2, Mistral) or
             // Replace(" " -> "▁") alone (Gemma-style); anything else of these types is outside the path
@@ -1195,6 +1243,12 @@ HostModel HostModel::from_json(const char* json, size_t len) {
             if (v.find(kMetaspace) == v.end()) throw Unsupported("pre_tokenizer: whole-piece BPE (no split at U+2581) with a vocabulary that lacks U+2581 is outside the hot path");
         }
     }
+    if (m.norm == NORM_NFC &&
+        !(m.model == MODEL_BPE && !m.char_bpe && (m.pretok == PT_BYTELEVEL_GPT2 || m.pretok == PT_LLAMA3 || m.pretok == PT_BYTELEVEL_NOREGEX)))
+        throw Unsupported("normalizer: NFC is only on the path in front of byte-level BPE (ByteLevel, or a Split of the tiktoken family + ByteLevel); "
+                          "in front of BPE over characters, WordPiece, WordLevel or the U+2581 front it is not");
+    // (the same refusal every encode call makes for any normalizer, made at load for this one: the file can never encode)
+    if (m.norm == NORM_NFC && m.byte_level && m.add_prefix_space) throw Unsupported("ByteLevel add_prefix_space behind a normalizer (NFC)");
     if (m.norm == NORM_METASPACE)
         for (const AddedToken& a : m.added_tokens)
             if (a.normalized) throw Unsupported("added token '" + a.content + "' is normalized = true behind the U+2581 normalizer (matched on the normalized text: not on the path)");
@@ -1260,6 +1314,7 @@ HostModel HostModel::from_json(const char* json, size_t len) {
 
     build_unicode(m);
     if (m.norm == NORM_BERT) build_bert_norm(m);
+    if (m.norm == NORM_NFC) build_nfc_tables(m);
 
     // ---- AddedVocabulary pattern sets (needs the normalizer tables: normalized tokens match by their normalized form) ----
     {
@@ -1281,6 +1336,11 @@ HostModel HostModel::from_json(const char* json, size_t len) {
                 pat = m.bert_normalize(a.content, &refused);
                 if (refused) throw Unsupported("added token '" + a.content + "' holds a character whose NFD reordering is context dependent");
                 if (pat.empty()) continue;                         // normalizes to nothing: the automaton has nothing to match
+            }
+            if (a.normalized && m.norm == NORM_NFC) {
+                bool refused = false;
+                pat = m.nfc_normalize(a.content, nullptr, &refused);
+                if (refused) throw Unsupported("added token '" + a.content + "' holds a run of more than 48 combining characters (NFC of such a run is not built)");
             }
             pats[a.normalized ? 1 : 0].push_back(Pat{pat, a.id, (a.single_word ? 1u : 0u) | (a.lstrip ? 2u : 0u) | (a.rstrip ? 4u : 0u) | (a.special ? 8u : 0u)});
         }
@@ -1344,6 +1404,42 @@ int HostModel::bn_expand_cp(uint32_t cp, uint32_t* out, int* refused) const {
     }
     if (cjk) out[k++] = ' ';
     return k;
+}
+
+void HostModel::build_nfc() { build_nfc_tables(*this); }
+
+std::string HostModel::nfc_normalize(const std::string& s, std::vector<uint32_t>* norig, bool* refused) const {
+    const NfcTables t{nfc_stage1.data(), nfc_stage2.data(), nfc_map.data(), nfc_mask, nfc_seed};
+    const int64_t n = (int64_t)s.size();
+    std::vector<nfc_mask_t> bound((size_t)(n >> 6) + 2, 0ull);
+    bound[0] = 1ull;                                       // one piece
+    const uint8_t* text = (const uint8_t*)s.data();
+    std::string out;
+    if (norig) norig->clear();
+    NfcSeg g;
+    int64_t p = 0;
+    while (p < n) {
+        uint32_t l;
+        const uint32_t f = nfc_flags(t, nfc_decode(text, n, p, &l));
+        if (nfc_trivial(t, text, n, bound.data(), p, f, l)) {
+            out.append(s, (size_t)p, l);
+            if (norig) norig->insert(norig->end(), l, (uint32_t)p);
+            p += l;
+            continue;
+        }
+        if (!nfc_segment(t, text, n, bound.data(), p, g)) {
+            if (refused) *refused = true;
+            return out;
+        }
+        for (int k = 0; k < g.n; ++k) {
+            uint8_t b[4];
+            const uint32_t bl = nfc_utf8_put(b, g.cp[k]);
+            out.append((const char*)b, bl);
+            if (norig) norig->insert(norig->end(), bl, (uint32_t)p + g.al[k]);
+        }
+        p = g.e;
+    }
+    return out;
 }
 
 std::string HostModel::bert_normalize(const std::string& s, bool* refused) const {

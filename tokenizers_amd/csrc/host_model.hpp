@@ -126,6 +126,10 @@ struct HostModel {
     // pattern normalization at load, tkamd_probe_bert_norm); *refused = a character whose NFD reordering is context dependent
     int bn_expand_cp(uint32_t cp, uint32_t* out, int* refused) const;
     std::string bert_normalize(const std::string& s, bool* refused) const;
+    // NFC of a string that is one piece, by the core the device runs (nfc_core.hpp; host side: pattern normalization at load, the test
+    // harness); norig (or null): per output byte, the first byte of the source char it is aligned to; *refused = a segment beyond NFC_SEG_MAX
+    std::string nfc_normalize(const std::string& s, std::vector<uint32_t>* norig, bool* refused) const;
+    void build_nfc();      // the NFC tables alone (from_json builds them behind an NFC normalizer; the test harness has no tokenizer)
 
     // ---- tables copied to the device ----
     uint32_t byte_id[256];              // byte -> id of its one-symbol token (BPE byte-level); BPE over chars with byte_fallback: id of "<0xXX>"
@@ -159,6 +163,11 @@ struct HostModel {
     std::vector<uint8_t> bn_stage2;
     std::vector<MergeSlot> bn_map;
     uint32_t bn_mask = 0, bn_seed = 0;
+    // NFC per-code-point data (nfc_tables.inc): 2-stage flag table + one pair table, decompositions next to primary composites (nfc_core.hpp)
+    std::vector<uint16_t> nfc_stage1;
+    std::vector<uint8_t> nfc_stage2;
+    std::vector<MergeSlot> nfc_map;
+    uint32_t nfc_mask = 0, nfc_seed = 0;
 
     // ---- decode_batch tables: every decoder on the path is a per-token string function of (id, first kept token of the
     // document?), so decoding is a gather.  dec_entry[id] = {offset of the FIRST-position form, its length | flags,

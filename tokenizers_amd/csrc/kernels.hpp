@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 #include <cstdint>
 
+#include "nfc_core.hpp"
 #include "tables.hpp"
 
 namespace tkamd {
@@ -305,7 +306,10 @@ enum : int {
     NOTE_REORDER_SEEN = 2048,     // not an error: the normalizer met a character NFD's canonical ordering could move (k_bn_reorder_fix then looks at its neighbours)
     NOTE_ADDED_SEEN = 16384,      // not an error: a batch that was run as if the text held no added token (run_pipeline's speculation) met the content of one: the host runs
                                   // it again with the matching passes (finish_batch) and stops speculating for a while
-    NOTE_BITS = NOTE_REORDER_SEEN | NOTE_ADDED_SEEN,
+    NOTE_NFC_SEEN = 32768,        // not an error: a batch behind an NFC normalizer that was run over the text as it came (k_nfc_check vouches for almost all text) holds
+                                  // a lane the quick check cannot vouch for: the host runs it again through the normalizer's kernels and pauses the speculation
+    ERR_NFC_SEGMENT = 65536,      // NFC: a starter with more than 48 chars of combining marks (and other chars that may compose) behind it; such a segment is not normalized on the device
+    NOTE_BITS = NOTE_REORDER_SEEN | NOTE_ADDED_SEEN | NOTE_NFC_SEEN,
     ERR_QUEUE_FULL_PAD = 0,          // a work queue / the row area was too small for this batch: the host grows it and runs the batch again
 };
 
@@ -360,6 +364,14 @@ void launch_emit_pretok_end(hipStream_t st, const unsigned long long* startmask,
 void launch_bert_normalize(hipStream_t st, const BnTables& bt, const uint8_t* text, int64_t n_bytes, const int64_t* doc_off, int64_t n_docs,
                            const unsigned long long* verbatim, uint8_t* olen, uint32_t* wsum, uint32_t* bsum, uint32_t* wbase, int64_t* x_len, uint8_t* ntext,
                            uint32_t* nos, uint32_t* noe, int64_t* ndoc_off, int* err);
+// NFC (kernels/nfc.hip).  check: NOTE_NFC_SEEN into *note unless every 16-byte lane of the text passes the quick check.  bound: the piece
+// starts of the general path, in place over the document-start mask (| verbatim | verbatim << 1).  normalize: count -> scan -> write -> the
+// document CSR in X, in the BertNormalizer's BnOlen layout (olen: bn_olen_bytes(n_bytes)); nos: the source char of every X byte, or null
+void launch_nfc_check(hipStream_t st, const NfcTables& nt, const uint8_t* text, int64_t n_bytes, int* note);
+void launch_nfc_bound(hipStream_t st, unsigned long long* dmask, const unsigned long long* verbatim, int64_t n_words);
+void launch_nfc_normalize(hipStream_t st, const NfcTables& nt, const uint8_t* text, int64_t n_bytes, const int64_t* doc_off, int64_t n_docs,
+                          const unsigned long long* verbatim, const unsigned long long* bound, uint8_t* olen, uint32_t* wsum, uint32_t* bsum, uint32_t* wbase,
+                          int64_t* x_len, uint8_t* ntext, uint32_t* nos, int64_t* ndoc_off, int* err);
 // whole-word vocabulary hits of QUEUED pre-tokens longer than 16 bytes (ignore_merges, WordLevel): a hit becomes the result row and
 // the queue entry is retired (length 0) so that the model kernels skip it
 void launch_long_vocab3(hipStream_t st, int grid, const DevTables& t, const uint8_t* text, const QView& v1, const QView& v2, const QView& v3, void* rows, uint32_t miss_is_unk,

@@ -134,6 +134,28 @@ void launch_bert_normalize(hipStream_t st, const BnTables& bt, const uint8_t* te
     hipLaunchKernelGGL(k_bn_doc_offsets, dim3(blocks_for(n_docs + 1, 256)), dim3(256), 0, st, doc_off, n_docs, n_bytes, ol,
                        (const uint32_t*)wbase, (const int64_t*)x_len, ndoc_off);
 }
+void launch_nfc_check(hipStream_t st, const NfcTables& nt, const uint8_t* text, int64_t n_bytes, int* note) {
+    hipLaunchKernelGGL(k_nfc_check, dim3(blocks_for(n_bytes, 256 * NFC_LANE)), dim3(256), 0, st, nt, text, n_bytes, note);
+}
+void launch_nfc_bound(hipStream_t st, unsigned long long* dmask, const unsigned long long* verbatim, int64_t n_words) {
+    hipLaunchKernelGGL(k_nfc_bound, dim3(blocks_for(n_words, 256)), dim3(256), 0, st, dmask, verbatim, n_words);
+}
+void launch_nfc_normalize(hipStream_t st, const NfcTables& nt, const uint8_t* text, int64_t n_bytes, const int64_t* doc_off, int64_t n_docs,
+                          const unsigned long long* verbatim, const unsigned long long* bound, uint8_t* olen, uint32_t* wsum, uint32_t* bsum, uint32_t* wbase,
+                          int64_t* x_len, uint8_t* ntext, uint32_t* nos, int64_t* ndoc_off, int* err) {
+    const int64_t n_words = (n_bytes >> 6) + 1;
+    uint8_t* const ltot = bn_ltot_of(olen, n_bytes);
+    const BnOlen ol{olen, ltot};
+    const NfcArgs a{nt, text, n_bytes, verbatim, bound};
+    hipLaunchKernelGGL(k_nfc_count, dim3(blocks_for(n_bytes + 1, 256 * NFC_LANE)), dim3(256), 0, st, a, olen, ltot, wsum, err);
+    unsigned nb = blocks_for(n_words, 256);
+    hipLaunchKernelGGL(k_u32_reduce, dim3(nb), dim3(256), 0, st, (const uint32_t*)wsum, n_words, bsum);
+    hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, st, bsum, (int64_t)nb, (const int64_t*)nullptr, (int64_t)1, x_len);
+    hipLaunchKernelGGL(k_u32_down, dim3(nb), dim3(256), 0, st, (const uint32_t*)wsum, n_words, (const uint32_t*)bsum, wbase);
+    hipLaunchKernelGGL(k_nfc_write, dim3(blocks_for(n_bytes, 256 * NFC_LANE)), dim3(256), 0, st, a, ol, (const uint32_t*)wbase, (const int*)err, ntext, nos);
+    hipLaunchKernelGGL(k_bn_doc_offsets, dim3(blocks_for(n_docs + 1, 256)), dim3(256), 0, st, doc_off, n_docs, n_bytes, ol,
+                       (const uint32_t*)wbase, (const int64_t*)x_len, ndoc_off);
+}
 // the "▁" front (kernels/metaspace.hip): count -> scan of the 64-byte words -> write, then the document CSR in X (the BertNormalizer's)
 void launch_metaspace(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* doc_off, int64_t n_docs, const unsigned long long* pstart,
                       const unsigned long long* dstart, const unsigned long long* mmask, const unsigned long long* smask, uint32_t prepend, uint8_t* olen,

@@ -1,0 +1,274 @@
+// The NFC normalizer (normalizers/unicode.rs NFC -> tokenizer/normalizer.rs:461-464 -> unicode-normalization-alignments), one host+device
+// core: the quick check, the segment rules, and the normalization of one segment with the alignment NormalizedString::transform
+// (tokenizer/normalizer.rs:317-428) gives every output char.  kernels/nfc.hip runs it per lane; the loader normalizes the patterns of
+// normalized added tokens with it; tests/harness/nfc_harness.cpp holds it against the reference wheel.
+//
+// Data (nfc_tables.inc, probed from the wheel): one byte per code point in a 2-stage table -- the rank of its canonical combining class
+// among the classes in use (the order is all that ordering and blocking ask of a class), DECOMPOSES, and "NFC_Quick_Check is not Yes" --
+// and one pair table holding the full canonical decompositions (keys (cp, 0): three code points, (cp, 1): the fourth) next to the primary
+// composites (keys (first, second): a second is never below U+0300, so the two kinds of key never meet).  Hangul is arithmetic.
+//
+// A char is ACTIVE when its class is not 0 or its quick check is not Yes: only such a char can change, move, or compose with what
+// stands in front of it.  A SEGMENT starts at a char that is not active, or at a piece start (a document start, either edge of a
+// verbatim added-token match), and runs through every active char behind it.  Segments are independent: a char that is not active is a
+// starter that composes with nothing in front of it, so neither the ordering nor the composition crosses it.  A segment of one char that
+// is not active is the char itself (TRIVIAL); every other one is decomposed, stable-sorted by class, and composed with the blocking rule.
+//
+// Alignment.  The reference's iterators yield (char, change): a decomposition's first char 0, its further chars 1; a composition of k
+// and c carries k's change + c's change - 1; the pairs move through the canonical ordering together.  transform() then walks the SOURCE
+// chars by position: a char with change <= 0 takes the alignment of the next source char and consumes it and -change more; a char with
+// change > 0 takes the alignment of the source char consumed last.  Every output char is so aligned to exactly ONE source char, which is
+// why one `norig` entry per output byte (the source char's first byte) is all the offsets need.
+#pragma once
+#include <cstdint>
+
+#include "tables.hpp"
+
+namespace tkamd {
+
+#if defined(__HIPCC__)
+#define TK_HD_OUTLINE inline __host__ __device__ __attribute__((noinline))
+#else
+#define TK_HD_OUTLINE inline
+#endif
+
+constexpr uint32_t NFC_F_RANK = 0x3Fu, NFC_F_DECOMP = 0x40u, NFC_F_QCN = 0x80u, NFC_F_ACTIVE = NFC_F_RANK | NFC_F_QCN;
+constexpr int NFC_SEG_MAX = 48;        // pieces (and source chars) of one segment, like BN_RUN_MAX; a longer one refuses the batch
+constexpr int NFC_LANE = 16;           // source bytes a lane of the kernels takes (= BN_LANE: the BnOlen layout)
+constexpr uint32_t NFC_S_BASE = 0xAC00u, NFC_L_BASE = 0x1100u, NFC_V_BASE = 0x1161u, NFC_T_BASE = 0x11A7u, NFC_V_N = 21u, NFC_T_N = 28u,
+                   NFC_S_N = 19u * 21u * 28u;
+constexpr uint32_t NFC_FILL = 0x1FFFFFu;
+
+struct NfcTables {
+    const uint16_t* n1;
+    const uint8_t* n2;
+    const MergeSlot* map;
+    uint32_t map_mask, map_seed;
+};
+using nfc_mask_t = unsigned long long;
+
+TK_HD uint32_t nfc_flags(const NfcTables& t, uint32_t cp) { return cp >= 0x110000u ? 0u : t.n2[((uint32_t)t.n1[cp >> 8] << 8) | (cp & 255u)]; }
+TK_HD bool nfc_bit(const nfc_mask_t* m, int64_t i) { return ((m[i >> 6] >> (i & 63)) & 1ull) != 0; }
+TK_HD bool nfc_map(const NfcTables& t, uint32_t a, uint32_t b, uint32_t* lo, uint32_t* hi) {
+    const MergeSlot& x = t.map[merge_hash1(a, b, t.map_seed) & t.map_mask];
+    const MergeSlot& y = t.map[merge_hash2(a, b, t.map_seed) & t.map_mask];
+    const MergeSlot* h = (x.a == a && x.b == b) ? &x : (y.a == a && y.b == b) ? &y : nullptr;
+    if (!h) return false;
+    *lo = h->rank;
+    *hi = h->new_id;
+    return true;
+}
+TK_HD uint32_t nfc_utf8_len(uint32_t cp) { return cp < 0x80u ? 1u : cp < 0x800u ? 2u : cp < 0x10000u ? 3u : 4u; }
+TK_HD uint32_t nfc_utf8_put(uint8_t* o, uint32_t c) {
+    if (c < 0x80u) { o[0] = (uint8_t)c; return 1u; }
+    if (c < 0x800u) { o[0] = (uint8_t)(0xC0u | (c >> 6)); o[1] = (uint8_t)(0x80u | (c & 0x3Fu)); return 2u; }
+    if (c < 0x10000u) { o[0] = (uint8_t)(0xE0u | (c >> 12)); o[1] = (uint8_t)(0x80u | ((c >> 6) & 0x3Fu)); o[2] = (uint8_t)(0x80u | (c & 0x3Fu)); return 3u; }
+    o[0] = (uint8_t)(0xF0u | (c >> 18)); o[1] = (uint8_t)(0x80u | ((c >> 12) & 0x3Fu)); o[2] = (uint8_t)(0x80u | ((c >> 6) & 0x3Fu)); o[3] = (uint8_t)(0x80u | (c & 0x3Fu));
+    return 4u;
+}
+
+// The unit whose first byte is text[i] (i < n): a lead byte with all its continuation bytes inside the text is the code point; any
+// other byte -- ASCII, a stray continuation byte, a lead byte cut short -- is a unit of one byte (U+FFFD for the last two: not active).
+TK_HD uint32_t nfc_decode(const uint8_t* text, int64_t n, int64_t i, uint32_t* len) {
+    const uint32_t b0 = text[i];
+    *len = 1u;
+    if (b0 < 0x80u) return b0;
+    if (b0 < 0xC0u) return 0xFFFDu;
+    const uint32_t l = b0 < 0xE0u ? 2u : b0 < 0xF0u ? 3u : 4u;
+    if (i + (int64_t)l > n) return 0xFFFDu;
+    uint32_t cp = b0 & (0xFFu >> (l + 1u));
+    for (uint32_t k = 1; k < l; ++k) {
+        const uint32_t c = text[i + k];
+        if ((c & 0xC0u) != 0x80u) return 0xFFFDu;
+        cp = (cp << 6) | (c & 0x3Fu);
+    }
+    *len = l;
+    return cp;
+}
+// first byte of the unit that holds byte j
+TK_HD int64_t nfc_unit_start(const uint8_t* text, int64_t n, int64_t j) {
+    if ((text[j] & 0xC0u) != 0x80u) return j;
+    for (int64_t k = 1; k <= 3 && j - k >= 0; ++k) {
+        const uint32_t c = text[j - k];
+        if ((c & 0xC0u) == 0x80u) continue;
+        if (c >= 0xC0u) {
+            uint32_t l;
+            nfc_decode(text, n, j - k, &l);
+            if ((int64_t)l > k) return j - k;
+        }
+        break;
+    }
+    return j;
+}
+
+// ---- the quick check of one 16-byte lane (k_nfc_check): true = "not known to be NFC".  Exact in the direction that matters: a text
+// every lane of which passes has all chars Quick_Check = Yes and every run of non-starters in class order, so it IS its NFC form, and so
+// is every piece of it (pieces are ignored here: a mark that opens a piece is held against the char in front of it all the same, the one
+// place where an NFC text can fail the check).
+TK_HD bool nfc_check_lane(const NfcTables& t, const uint8_t* text, int64_t n, int64_t i0) {
+    uint32_t prev = 0xFFFFFFFFu;                            // class rank of the char in front (not looked up yet)
+    const int64_t i1 = i0 + NFC_LANE < n ? i0 + NFC_LANE : n;
+    for (int64_t i = i0; i < i1; ++i) {
+        const uint32_t b = text[i];
+        if (b < 0x80u) { prev = 0u; continue; }
+        if (b < 0xC0u) continue;
+        uint32_t l;
+        const uint32_t f = nfc_flags(t, nfc_decode(text, n, i, &l));
+        if (f & NFC_F_QCN) return true;
+        const uint32_t r = f & NFC_F_RANK;
+        if (r) {
+            if (prev == 0xFFFFFFFFu) {
+                prev = 0u;
+                if (i > 0) {
+                    uint32_t pl;
+                    prev = nfc_flags(t, nfc_decode(text, n, nfc_unit_start(text, n, i - 1), &pl)) & NFC_F_RANK;
+                }
+            }
+            if (prev > r) return true;
+        }
+        prev = r;
+    }
+    return false;
+}
+
+// ---- segments
+// first byte of the segment that holds the unit starting at cs, or -1 if more than NFC_SEG_MAX chars lie between them
+TK_HD int64_t nfc_seg_start(const NfcTables& t, const uint8_t* text, int64_t n, const nfc_mask_t* bound, int64_t cs) {
+    int64_t s = cs;
+    for (int steps = 0; steps <= NFC_SEG_MAX; ++steps) {
+        if (s <= 0 || nfc_bit(bound, s)) return s;
+        uint32_t l;
+        if (!(nfc_flags(t, nfc_decode(text, n, s, &l)) & NFC_F_ACTIVE)) return s;
+        s = nfc_unit_start(text, n, s - 1);
+    }
+    return -1;
+}
+// the unit at s (flags f, length l) is a segment head: is the segment that unit alone, unchanged?
+TK_HD bool nfc_trivial(const NfcTables& t, const uint8_t* text, int64_t n, const nfc_mask_t* bound, int64_t s, uint32_t f, uint32_t l) {
+    if (f & NFC_F_ACTIVE) return false;
+    const int64_t p = s + l;
+    if (p >= n || nfc_bit(bound, p)) return true;
+    if (text[p] < 0x80u) return true;
+    uint32_t l2;
+    return !(nfc_flags(t, nfc_decode(text, n, p, &l2)) & NFC_F_ACTIVE);
+}
+// output bytes charged to source byte k of a segment of S source bytes and O output bytes (O <= 3 S): one each as far as they go, then
+// up to two more each from the front.  A segment that keeps its length charges every byte 1, as a lane that is copied whole does.
+TK_HD uint32_t nfc_charge(uint32_t k, uint32_t O, uint32_t S) {
+    const uint32_t base = O < S ? O : S, extra = O - base;
+    const uint32_t x = extra > 2u * k ? extra - 2u * k : 0u;
+    return (k < O ? 1u : 0u) + (x > 2u ? 2u : x);
+}
+
+struct NfcSeg {
+    uint32_t cp[NFC_SEG_MAX];          // pieces, then the output chars
+    uint8_t rank[NFC_SEG_MAX];
+    int8_t chg[NFC_SEG_MAX];
+    uint8_t src[NFC_SEG_MAX];          // first byte of every source char, relative to the segment's
+    uint8_t al[NFC_SEG_MAX];           // per output char: first byte of the source char it is aligned to, relative to the segment's
+    int n;                             // output chars
+    int64_t e;                         // end of the segment in the text
+    uint32_t obytes;                   // UTF-8 bytes of the output
+};
+
+TK_HD uint32_t nfc_compose(const NfcTables& t, uint32_t a, uint32_t b) {
+    if (a - NFC_L_BASE < 19u && b - NFC_V_BASE < NFC_V_N) return NFC_S_BASE + ((a - NFC_L_BASE) * NFC_V_N + (b - NFC_V_BASE)) * NFC_T_N;
+    if (a - NFC_S_BASE < NFC_S_N && (a - NFC_S_BASE) % NFC_T_N == 0u && b - (NFC_T_BASE + 1u) < NFC_T_N - 1u) return a + (b - NFC_T_BASE);
+    if (b < 0x300u) return 0u;
+    uint32_t lo, hi;
+    return nfc_map(t, a, b, &lo, &hi) ? lo : 0u;
+}
+
+// Normalizes the segment whose head is the unit at s (a char that is not active, or a piece start).  False: it holds more than
+// NFC_SEG_MAX chars or pieces (or would outgrow three times its source bytes, which no canonical decomposition does) -- nothing is valid then.
+TK_HD_OUTLINE bool nfc_segment(const NfcTables& t, const uint8_t* text, int64_t n, const nfc_mask_t* bound, int64_t s, NfcSeg& g) {
+    int np = 0, nsrc = 0;
+    int64_t p = s;
+    while (p < n) {
+        if (nsrc && nfc_bit(bound, p)) break;
+        uint32_t l;
+        const uint32_t cp = nfc_decode(text, n, p, &l);
+        const uint32_t f = nfc_flags(t, cp);
+        if (nsrc && !(f & NFC_F_ACTIVE)) break;
+        if (nsrc == NFC_SEG_MAX) return false;
+        uint32_t d[4] = {cp, NFC_FILL, NFC_FILL, NFC_FILL};
+        if (f & NFC_F_DECOMP) {
+            if (cp - NFC_S_BASE < NFC_S_N) {
+                const uint32_t x = cp - NFC_S_BASE;
+                d[0] = NFC_L_BASE + x / (NFC_V_N * NFC_T_N);
+                d[1] = NFC_V_BASE + (x % (NFC_V_N * NFC_T_N)) / NFC_T_N;
+                if (x % NFC_T_N) d[2] = NFC_T_BASE + x % NFC_T_N;
+            } else {
+                uint32_t lo, hi;
+                if (nfc_map(t, cp, 0u, &lo, &hi)) {
+                    const unsigned long long v = ((unsigned long long)hi << 32) | lo;
+                    d[0] = (uint32_t)(v & NFC_FILL); d[1] = (uint32_t)((v >> 21) & NFC_FILL); d[2] = (uint32_t)((v >> 42) & NFC_FILL);
+                    if (d[2] != NFC_FILL && nfc_map(t, cp, 1u, &lo, &hi)) d[3] = lo;
+                }
+            }
+        }
+        for (int q = 0; q < 4 && d[q] != NFC_FILL; ++q) {
+            if (np == NFC_SEG_MAX) return false;
+            g.cp[np] = d[q];
+            g.rank[np] = (uint8_t)(((f & NFC_F_DECOMP) ? nfc_flags(t, d[q]) : f) & NFC_F_RANK);
+            g.chg[np] = (int8_t)(q ? 1 : 0);
+            ++np;
+        }
+        g.src[nsrc++] = (uint8_t)(p - s);
+        p += l;
+    }
+    g.e = p;
+    // canonical ordering: a stable sort by class of every run of non-starters (a starter never moves, nothing moves across one)
+    for (int k = 1; k < np; ++k) {
+        const uint8_t r = g.rank[k];
+        if (!r) continue;
+        const uint32_t c = g.cp[k];
+        const int8_t h = g.chg[k];
+        int j = k - 1;
+        while (j >= 0 && g.rank[j] > r) { g.cp[j + 1] = g.cp[j]; g.rank[j + 1] = g.rank[j]; g.chg[j + 1] = g.chg[j]; --j; }
+        g.cp[j + 1] = c; g.rank[j + 1] = r; g.chg[j + 1] = h;
+    }
+    // composition, in place: out[0, no) is final, the composee is held aside, the chars it could not take wait at out[no + 1, no + 1 + nb)
+    int no = 0, nb = 0;
+    bool have = false;
+    uint32_t kc = 0, last = 0;                             // last: class of the char buffered last (0: none is buffered)
+    int kh = 0;
+    for (int i = 0; i < np; ++i) {
+        const uint32_t c = g.cp[i], r = g.rank[i];
+        const int h = g.chg[i];
+        if (!have) {
+            if (r) { g.cp[no] = c; g.chg[no] = (int8_t)h; ++no; continue; }
+            have = true; kc = c; kh = h;
+            continue;
+        }
+        const bool blocked = nb > 0 && last >= r;
+        const uint32_t m = blocked ? 0u : nfc_compose(t, kc, c);
+        if (m) { kc = m; kh = kh + h - 1; continue; }
+        if (r == 0u) {                                       // a starter the composee does not take: the composee and what waits go out
+            g.cp[no] = kc; g.chg[no] = (int8_t)kh;
+            no += 1 + nb; nb = 0; last = 0u;
+            kc = c; kh = h;
+            continue;
+        }
+        g.cp[no + 1 + nb] = c; g.chg[no + 1 + nb] = (int8_t)h; ++nb;
+        last = r;
+    }
+    if (have) { g.cp[no] = kc; g.chg[no] = (int8_t)kh; no += 1 + nb; }
+    // alignment by position in the stream of source chars
+    int ptr = 0;
+    uint32_t ob = 0;
+    for (int k = 0; k < no; ++k) {
+        const int h = g.chg[k];
+        if (h > 0) g.al[k] = g.src[ptr > 0 ? ptr - 1 : 0];
+        else {
+            g.al[k] = g.src[ptr < nsrc ? ptr : nsrc - 1];
+            ptr += 1 - h;
+        }
+        ob += nfc_utf8_len(g.cp[k]);
+    }
+    g.n = no;
+    g.obytes = ob;
+    return ob <= 3u * (uint32_t)(g.e - s);
+}
+
+}  // namespace tkamd

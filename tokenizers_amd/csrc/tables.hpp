@@ -193,7 +193,8 @@ enum PretokKind {
     PT_METASPACE = 7         // the "▁" front of SentencePiece-style BPE: Metaspace (metaspace.rs:122-146), or null behind NORM_METASPACE
 };
 // NORM_METASPACE: Sequence[Prepend("▁"), Replace(" " -> "▁")] or Replace(" " -> "▁") alone (prepend.rs:16-24, replace.rs:83)
-enum NormKind { NORM_NONE = 0, NORM_BERT = 1, NORM_METASPACE = 2 };
+// NORM_NFC: NFC alone or Sequence[NFC] (normalizers/unicode.rs), in front of byte-level BPE (nfc_core.hpp, kernels/nfc.hip)
+enum NormKind { NORM_NONE = 0, NORM_BERT = 1, NORM_METASPACE = 2, NORM_NFC = 3 };
 // where the "▁" front puts a "▁" in front of a piece (the raw text between document edges and added-token matches)
 enum MsPrepend {
     MS_NEVER = 0,      // Metaspace prepend_scheme "never"; Replace alone

@@ -1063,7 +1063,9 @@ class Tokenizer:
                             offsets: str = "none", word_ids: bool = False, stream: int = 0, unsynced: bool = False) -> DeviceBatch:
         """Inputs already in HBM (raw device pointers; text needs TEXT_PAD readable slack).  Enqueue only.  ``unsynced``: the results
         will be consumed stream-ordered behind this call without :meth:`DeviceBatch.sync` in between (``TKAMD_NO_SPECULATION``: a
-        tokenizer with added tokens runs their matching passes outright instead of leaving a second run to the synchronisation)."""
+        tokenizer with added tokens runs their matching passes outright, and one with an NFC normalizer normalizes outright, instead of
+        leaving a second run to the synchronisation -- without the flag and without ``sync()`` a text that holds an added token or is not
+        NFC would be read back as if it held none / as it came)."""
         flags = {"none": _lib.OFFSETS_NONE, "byte": _lib.OFFSETS_BYTE, "char": _lib.OFFSETS_CHAR}[offsets]
         if word_ids:
             flags |= _lib.WANT_WORD_IDS
@@ -1099,12 +1101,13 @@ class Tokenizer:
 
     def queue_sizes(self) -> dict[str, int]:
         """Merge work-queue sizes of the last synchronised batch (diagnostics)."""
-        arr = (C.c_uint32 * 16)()
-        _lib.check(self._lib.tkamd_profile_counters(self._h, arr, 16))
+        arr = (C.c_uint32 * 18)()
+        _lib.check(self._lib.tkamd_profile_counters(self._h, arr, 18))
         out = {"merge16": arr[0], "merge32": arr[3], "merge64": arr[1], "merge_long": arr[2], "pretok_slow_docs": arr[4], "merge_huge": arr[7]}
         if arr[5]:                                       # in-batch claims: candidates the lookup looked at / how many were another pre-token's word
             out["claim_candidates"], out["claim_shared"] = arr[5], arr[6]
         out["added_spec_pause"] = arr[14]                # batches that will run the added tokens' matching passes outright (a speculative batch met a token's content)
+        out["nfc_spec_pause"], out["nfc_reruns"] = arr[16], arr[17]      # behind an NFC normalizer: batches that will normalize outright / batches run again (the quick check failed)
         out["merge_pair_wg_per_cu"] = arr[13]            # resident workgroups per CU of the launch that merges both LDS queues (its grid is that x the CUs)
         out["q16_div"] = arr[15]                         # the <= 16-byte queue holds n_bytes / q16_div entries (a queue overflow re-runs the batch with 2, then 1)
         if arr[12]:                                      # (profiling runs) merge-table probes of the LDS merge kernels, (k - 1) + 2 m per word
