@@ -4,9 +4,12 @@
 #include "nfc_core.hpp"
 
 #include <algorithm>
+#include <cctype>
+#include <cstdio>
 #include <cstring>
 #include <functional>
 #include <random>
+#include <set>
 #include <unordered_map>
 
 #include "json.hpp"
@@ -81,6 +84,9 @@ const UcRun kUcRuns[] = {
 };
 const UcRun kUcCaseRuns[] = {      // (flags: UCC_UPPER / UCC_LOWER, tables.hpp)
 #include "unicode_case_ranges.inc"
+};
+const UcRun kUcPsmRuns[] = {       // (flags: UC2_P / UC2_S / UC2_M / UC2_CJK, tables.hpp)
+#include "unicode_psm_ranges.inc"
 };
 
 struct BnMapRow {
@@ -450,6 +456,171 @@ bool parse_split_pattern(const std::string& rx, SplitRule* rule, bool* gpt2, std
     return true;
 }
 
+// ---- the DeepSeek-V3 chain: Sequence[Split(\p{N}{1,3}), Split([CJK class]+), Split(stage 3), ByteLevel(use_regex=false)] -------------------
+// (pretok_ds3_core.hpp).  The three patterns are READ like the tiktoken family's: alternative by alternative, the two classes the rule
+// depends on by their MEMBER SETS, whatever the spelling.
+
+std::string cp_name(uint32_t cp) {
+    char buf[16];
+    snprintf(buf, sizeof buf, "U+%04X", cp);
+    return buf;
+}
+
+// A bracket class of literal members at rx[*pos] == '[': chars, ranges a-b, backslash escapes of punctuation, \r \n \t, \xHH, \uHHHH,
+// \x{H..}.  The members go to *out and *pos behind the ']'.  False (with *why) for a negated class or one that holds a property or a nested class.
+bool parse_literal_class(const std::string& rx, size_t* pos, std::set<uint32_t>* out, std::string* why) {
+    const uint8_t* s = (const uint8_t*)rx.data();
+    const size_t n = rx.size();
+    size_t i = *pos;
+    if (i >= n || s[i] != '[') { *why = "a bracket class was expected in '" + rx + "'"; return false; }
+    ++i;
+    if (i < n && s[i] == '^') { *why = "negated class in '" + rx + "'"; return false; }
+    auto member = [&](uint32_t* cp) -> bool {            // one member at i
+        if (s[i] == '\\') {
+            if (i + 1 >= n) return false;
+            const char e = (char)s[i + 1];
+            i += 2;
+            if (e == 'r') { *cp = '\r'; return true; }
+            if (e == 'n') { *cp = '\n'; return true; }
+            if (e == 't') { *cp = '\t'; return true; }
+            if (e == 'x' || e == 'u') {
+                size_t digits = e == 'u' ? 4 : 2;
+                bool braces = i < n && s[i] == '{';
+                if (braces) { ++i; digits = 8; }
+                uint32_t v = 0;
+                size_t k = 0;
+                for (; k < digits && i < n && isxdigit(s[i]); ++k, ++i) v = v * 16 + (uint32_t)(isdigit(s[i]) ? s[i] - '0' : (s[i] | 0x20) - 'a' + 10);
+                if (k == 0 || (!braces && k != digits)) return false;
+                if (braces) { if (i >= n || s[i] != '}') return false; ++i; }
+                *cp = v;
+                return true;
+            }
+            if (isalnum((unsigned char)e)) return false;   // \p{..}, \s, \d, \w ...: not a literal member
+            *cp = (uint8_t)e;
+            return true;
+        }
+        if (s[i] == '[') return false;
+        const int l = utf8_decode(s + i, n - i, cp);
+        if (!l) return false;
+        i += l;
+        return true;
+    };
+    bool first = true;
+    while (i < n && (s[i] != ']' || first)) {
+        first = false;
+        uint32_t a, b;
+        if (!member(&a)) { *why = "a class member that is not a literal char in '" + rx + "'"; return false; }
+        b = a;
+        if (i + 1 < n && s[i] == '-' && s[i + 1] != ']') {
+            ++i;
+            if (!member(&b) || b < a) { *why = "a bad range in '" + rx + "'"; return false; }
+        }
+        if (b - a > 0x10000u) { *why = "a range of more than 65,536 chars in '" + rx + "'"; return false; }
+        for (uint32_t c = a; c <= b; ++c) out->insert(c);
+    }
+    if (i >= n) { *why = "unterminated class in '" + rx + "'"; return false; }
+    *pos = i + 1;
+    return true;
+}
+
+// `got` against `want`: the first member one of them has and the other lacks, named
+bool same_members(const std::set<uint32_t>& got, const std::set<uint32_t>& want, const char* what, std::string* why) {
+    for (uint32_t c : got)
+        if (!want.count(c)) { *why = std::string(what) + " holds " + cp_name(c) + ", which is not in the class the path builds"; return false; }
+    for (uint32_t c : want)
+        if (!got.count(c)) { *why = std::string(what) + " lacks " + cp_name(c); return false; }
+    return true;
+}
+
+// raw CR / LF / TAB in a pattern (JSON decodes "\r" to the char itself) -> their escapes, so both spellings read alike
+std::string escape_controls(const std::string& rx) {
+    std::string o;
+    for (char c : rx) {
+        if (c == '\r') o += "\\r";
+        else if (c == '\n') o += "\\n";
+        else if (c == '\t') o += "\\t";
+        else o += c;
+    }
+    return o;
+}
+
+enum ChainStage { CHAIN_DIGITS = 1, CHAIN_CJK = 2, CHAIN_MAIN = 3 };
+// which stage a pattern is meant to be (by its outline; the stage's own reader then accepts or refuses it)
+ChainStage chain_stage_of(const std::string& rx) {
+    if (rx.compare(0, 5, "\\p{N}") == 0 && rx.find('|') == std::string::npos) return CHAIN_DIGITS;
+    if (!rx.empty() && rx[0] == '[' && rx.find('|') == std::string::npos && rx.find("\\p{") == std::string::npos) return CHAIN_CJK;
+    return CHAIN_MAIN;
+}
+
+void parse_chain_digits(const std::string& rx) {
+    if (rx != "\\p{N}{1,3}") throw Unsupported("pre_tokenizer: chained Split: digit count '" + rx + "' (only \\p{N}{1,3} is on the path)");
+}
+
+void parse_chain_cjk(const std::string& rx) {
+    std::set<uint32_t> got, want;
+    for (uint32_t c = 0x4E00; c <= 0x9FA5; ++c) want.insert(c);
+    for (uint32_t c = 0x3040; c <= 0x30FF; ++c) want.insert(c);
+    size_t pos = 0;
+    std::string why;
+    if (!parse_literal_class(rx, &pos, &got, &why)) throw Unsupported("pre_tokenizer: chained Split: CJK class: " + why);
+    if (rx.compare(pos, std::string::npos, "+") != 0) throw Unsupported("pre_tokenizer: chained Split: CJK class: '" + rx + "' is not a class followed by +");
+    if (!same_members(got, want, "the CJK class", &why))
+        throw Unsupported("pre_tokenizer: chained Split: " + why + " (only [U+4E00-U+9FA5 U+3040-U+309F U+30A0-U+30FF]+ is on the path)");
+}
+
+void parse_chain_main(const std::string& rx_in) {
+    const std::string rx = escape_controls(rx_in);
+    const std::vector<std::string> alt = regex_alternatives(rx);
+    const std::string head = "pre_tokenizer: chained Split: third pattern: ";
+    if (alt.size() != 6) throw Unsupported(head + std::to_string(alt.size()) + " alternatives where the path builds six");
+    {
+        std::set<uint32_t> got, want;
+        for (uint32_t c = 0x21; c < 0x7F; ++c)
+            if (!isalnum((int)c)) want.insert(c);
+        size_t pos = 0;
+        std::string why;
+        if (!parse_literal_class(alt[0], &pos, &got, &why)) throw Unsupported(head + "punctuation class: " + why);
+        if (alt[0].compare(pos, std::string::npos, "[A-Za-z]+") != 0) throw Unsupported(head + "alternative '" + alt[0] + "' is not [punctuation][A-Za-z]+");
+        if (!same_members(got, want, "the punctuation class", &why)) throw Unsupported(head + why + " (the 32 ASCII punctuation chars)");
+    }
+    static const char* const rest[5] = {"[^\\r\\n\\p{L}\\p{P}\\p{S}]?[\\p{L}\\p{M}]+", " ?[\\p{P}\\p{S}]+[\\r\\n]*", "\\s*[\\r\\n]+", "\\s+(?!\\S)", "\\s+"};
+    for (int k = 0; k < 5; ++k)
+        if (alt[k + 1] != rest[k]) throw Unsupported(head + "alternative '" + alt[k + 1] + "' where the path builds '" + rest[k] + "'");
+}
+
+// pt is a Sequence of more than two pre-tokenizers that ends in a ByteLevel and holds nothing but Splits in front of it
+bool parse_split_chain(const JsonValue* seq, HostModel& m) {
+    const size_t n = seq->arr.size();
+    if (n < 3 || seq->arr[n - 1]->get_str("type") != "ByteLevel") return false;
+    for (size_t k = 0; k + 1 < n; ++k)
+        if (seq->arr[k]->get_str("type") != "Split") return false;
+    if (n != 4) throw Unsupported("pre_tokenizer: a chain of " + std::to_string(n - 1) + " Splits in front of ByteLevel (only the chain of three -- digits, CJK class, "
+                                  "main pattern -- is on the path)");
+    std::string rx[3];
+    for (size_t k = 0; k < 3; ++k) {
+        const JsonValue* a = seq->arr[k].get();
+        const JsonValue* pat = a->get("pattern");
+        rx[k] = pat ? pat->get_str("Regex") : "";
+        const bool invert = a->get_bool("invert", false);
+        const std::string beh = a->get_str("behavior");
+        if (rx[k].empty()) throw Unsupported("pre_tokenizer: chained Split with a String pattern (only Regex patterns are on the path)");
+        if (invert || beh != "Isolated") throw Unsupported("pre_tokenizer: chained Split with behavior '" + beh + "'" + (invert ? " inverted" : "") + " (only Isolated is on the path)");
+    }
+    const JsonValue* b = seq->arr[3].get();
+    if (b->get_bool("use_regex", true)) throw Unsupported("pre_tokenizer: Sequence[Split, Split, Split, ByteLevel(use_regex=true)] applies one regex more");
+    if (b->get_bool("add_prefix_space", true))
+        throw Unsupported("pre_tokenizer: Sequence[Split, Split, Split, ByteLevel(add_prefix_space=true)] (a prefix space in front of every pre-token)");
+    const ChainStage got[3] = {chain_stage_of(rx[0]), chain_stage_of(rx[1]), chain_stage_of(rx[2])};
+    if (got[0] != CHAIN_DIGITS || got[1] != CHAIN_CJK || got[2] != CHAIN_MAIN)
+        throw Unsupported("pre_tokenizer: chained Split: the order of the stages is not digits, CJK class, main pattern");
+    parse_chain_digits(rx[0]);
+    parse_chain_cjk(rx[1]);
+    parse_chain_main(rx[2]);
+    m.byte_level = true;
+    m.add_prefix_space = false;
+    return true;
+}
+
 const char* const kMetaspace = "\xE2\x96\x81";     // U+2581, the "▁" of SentencePiece
 
 PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
@@ -515,6 +686,7 @@ PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
                 return PT_LLAMA3;
             }
         }
+        if (seq && seq->is_array() && parse_split_chain(seq, m)) return PT_SPLIT_CHAIN;
         throw Unsupported("pre_tokenizer: this Sequence is outside the hot path");
     }
     throw Unsupported("pre_tokenizer: type '" + type + "' is outside the hot path");
@@ -838,6 +1010,8 @@ HostModel HostModel::from_json(const char* json, size_t len) {
             m.bn_strip_accents = (sa && sa->is_bool()) ? sa->b : m.bn_lowercase;  // normalizers/bert.rs:124
         } else if (t == "NFC") {
             m.norm = NORM_NFC;
+        } else if (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() && norm->get("normalizers")->arr.empty()) {
+            // Sequence[] applies nothing (normalizers/utils.rs: a loop over no normalizer): DeepSeek-V3 files carry it
         } else if (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() &&
                    std::any_of(norm->get("normalizers")->arr.begin(), norm->get("normalizers")->arr.end(),
                                [](const JsonPtr& v) { return v && v->is_object() && v->get_str("type") == "NFC"; })) {
@@ -877,6 +1051,14 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     if (m.pretok == PT_LLAMA3 && m.split_rule.letters == 2) {         // the case classes of the case-split letter alternatives
         std::vector<uint8_t> flat(0x110000, 0);
         for (const UcRun& r : kUcCaseRuns)
+            for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
+        two_stage(flat, &m.ucc_stage1, &m.ucc_stage2);
+    }
+    if (m.pretok == PT_SPLIT_CHAIN) {                                  // \p{P}, \p{S}, \p{M} for the chain's third pattern: the same slot, the rule's second class table
+        if (m.norm != NORM_NONE && m.norm != NORM_NFC)
+            throw Unsupported("pre_tokenizer: the chained Split behind a normalizer other than NFC");
+        std::vector<uint8_t> flat(0x110000, 0);
+        for (const UcRun& r : kUcPsmRuns)
             for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
         two_stage(flat, &m.ucc_stage1, &m.ucc_stage2);
     }
@@ -1244,7 +1426,7 @@ HostModel HostModel::from_json(const char* json, size_t len) {
         }
     }
     if (m.norm == NORM_NFC &&
-        !(m.model == MODEL_BPE && !m.char_bpe && (m.pretok == PT_BYTELEVEL_GPT2 || m.pretok == PT_LLAMA3 || m.pretok == PT_BYTELEVEL_NOREGEX)))
+        !(m.model == MODEL_BPE && !m.char_bpe && (m.pretok == PT_BYTELEVEL_GPT2 || m.pretok == PT_LLAMA3 || m.pretok == PT_SPLIT_CHAIN || m.pretok == PT_BYTELEVEL_NOREGEX)))
         throw Unsupported("normalizer: NFC is only on the path in front of byte-level BPE (ByteLevel, or a Split of the tiktoken family + ByteLevel); "
                           "in front of BPE over characters, WordPiece, WordLevel or the U+2581 front it is not");
     // (the same refusal every encode call makes for any normalizer, made at load for this one: the file can never encode)

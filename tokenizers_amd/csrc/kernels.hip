@@ -32,6 +32,7 @@
 #include "nfc_core.hpp"
 #include "pretok_gpt2_core.hpp"
 #include "pretok_l3_core.hpp"
+#include "pretok_ds3_core.hpp"
 #include "pretok_local_core.hpp"
 #include "tables.hpp"
 
@@ -80,6 +81,7 @@ static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)(
 #include "kernels/documents.hip"
 #include "kernels/pretok_gpt2.hip"
 #include "kernels/pretok_llama3.hip"
+#include "kernels/pretok_ds3.hip"
 #include "kernels/pretok_local.hip"
 #include "kernels/bert_norm.hip"
 #include "kernels/nfc.hip"

@@ -385,6 +385,11 @@ void launch_pretok_llama3(hipStream_t st, const uint8_t* text, int64_t n_bytes, 
                           SplitRule rule, const uint16_t* ucc1, const uint8_t* ucc2, unsigned long long* tileflags, unsigned long long* leadmask = nullptr);      // leadmask: as launch_pretok_gpt2's (the bit-parallel members only)
 // (tileflags: L3_TILEFLAG_WORDS(n_bytes) zeroed 64-bit words -- a bit per 2048 bytes of text, the tile kernel's work list)
 inline size_t l3_tileflag_words(int64_t n_bytes) { return (size_t)((n_bytes + 1) / 2048 + 1) / 64 + 2; }
+// The chained Split of DeepSeek-V3 / R1 (PT_SPLIT_CHAIN, pretok_ds3_core.hpp): the arguments of launch_pretok_llama3, with the chain's second
+// class table (ps1 / ps2: UC2_P / UC2_S / UC2_M) in place of the rule; slowmask: (n_bytes >> 6) + 1 words the lane kernel writes whole
+void launch_pretok_ds3(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* docmask,
+                       const uint16_t* uc1, const uint8_t* uc2, const uint16_t* ps1, const uint8_t* ps2, unsigned long long* startmask, unsigned long long* slowmask,
+                       const int64_t* doc_off, int64_t n_docs, const int64_t* n_docs_dev, uint32_t* slow_docs, uint32_t* n_slow_docs, unsigned long long* leadmask = nullptr);
 void launch_leadmask(hipStream_t st, const uint8_t* text, int64_t n_bytes, unsigned long long* leadmask);
 void launch_seq_regroup(hipStream_t st, const int64_t* seq_off, int64_t n_seqs, int64_t n_words, const int64_t* word_tok_off, int64_t* seq_tok_off, uint32_t* widx,
                         int64_t* first_tok);

@@ -226,6 +226,19 @@ void launch_pretok_llama3(hipStream_t st, const uint8_t* text, int64_t n_bytes, 
         hipLaunchKernelGGL(k_pretok_llama3_slow, dim3(8192), dim3(64), 0, st, text, doc_off, (const uint32_t*)slow_docs, (const uint32_t*)n_slow_docs, q, startmask);
     }
 }
+void launch_pretok_ds3(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* docmask,
+                       const uint16_t* uc1, const uint8_t* uc2, const uint16_t* ps1, const uint8_t* ps2, unsigned long long* startmask, unsigned long long* slowmask,
+                       const int64_t* doc_off, int64_t n_docs, const int64_t* n_docs_dev, uint32_t* slow_docs, uint32_t* n_slow_docs, unsigned long long* leadmask) {
+    // Two tiers, as for the case-split members of the tiktoken family: the per-lane bit-parallel kernel, then the sequential matcher on the
+    // sentences (doc_off: documents, or the pieces between added-token matches) in which that one left a byte undecided.
+    const Ds3Seq q{uc1, uc2, ps1, ps2};
+    const unsigned doc_blocks = std::min<unsigned>(blocks_for(n_docs, 256), 4096u);
+    if (leadmask) hipLaunchKernelGGL((k_pretok_ds3_lane<true>), dim3(blocks_for(n_bytes + 1, 256 * L3W_MAIN)), dim3(256), 0, st, text, n_bytes, len_dev, docmask, uc1, uc2, ps1, ps2, startmask, slowmask, leadmask);
+    else hipLaunchKernelGGL((k_pretok_ds3_lane<false>), dim3(blocks_for(n_bytes + 1, 256 * L3W_MAIN)), dim3(256), 0, st, text, n_bytes, len_dev, docmask, uc1, uc2, ps1, ps2, startmask, slowmask,
+                            (unsigned long long*)nullptr);
+    hipLaunchKernelGGL(k_l3_slow_docs, dim3(doc_blocks), dim3(256), 0, st, (const unsigned long long*)slowmask, doc_off, n_docs, n_docs_dev, slow_docs, n_slow_docs);
+    hipLaunchKernelGGL(k_pretok_ds3_slow, dim3(1024), dim3(64), 0, st, text, doc_off, (const uint32_t*)slow_docs, (const uint32_t*)n_slow_docs, q, startmask);
+}
 void launch_leadmask(hipStream_t st, const uint8_t* text, int64_t n_bytes, unsigned long long* leadmask) {
     hipLaunchKernelGGL(k_leadmask, dim3(blocks_for(n_bytes + 64, 256 * 16)), dim3(256), 0, st, text, n_bytes, leadmask);
 }

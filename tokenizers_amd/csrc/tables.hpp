@@ -190,7 +190,8 @@ enum PretokKind {
     PT_WHITESPACE_SPLIT = 4, // char::is_whitespace                             whitespace.rs:35-41
     PT_BERT = 5,             // BertPreTokenizer                                bert.rs:14-17
     PT_BYTELEVEL_NOREGEX = 6,// ByteLevel(use_regex=false): whole doc is one pre-token
-    PT_METASPACE = 7         // the "▁" front of SentencePiece-style BPE: Metaspace (metaspace.rs:122-146), or null behind NORM_METASPACE
+    PT_METASPACE = 7,        // the "▁" front of SentencePiece-style BPE: Metaspace (metaspace.rs:122-146), or null behind NORM_METASPACE
+    PT_SPLIT_CHAIN = 8       // Sequence[Split(\p{N}{1,3}), Split(CJK class +), Split(stage 3), ByteLevel(use_regex=false)]: DeepSeek-V3 / R1 (pretok_ds3_core.hpp)
 };
 // NORM_METASPACE: Sequence[Prepend("▁"), Replace(" " -> "▁")] or Replace(" " -> "▁") alone (prepend.rs:16-24, replace.rs:83)
 // NORM_NFC: NFC alone or Sequence[NFC] (normalizers/unicode.rs), in front of byte-level BPE (nfc_core.hpp, kernels/nfc.hip)
@@ -223,6 +224,8 @@ TK_HD bool split_rule_fast(const SplitRule& r) { return r.letters == 0 && r.othe
 // one left a byte of undecided (no tile tier)
 TK_HD bool split_rule_fast_cs(const SplitRule& r) { return r.letters == 2 && (r.contr == 0 || r.contr == 3); }
 // case classes of the case-split letters (generated data: unicode_case_ranges.inc)
+// second class table of the chained Split (PT_SPLIT_CHAIN; generated data: unicode_psm_ranges.inc)
+enum : uint8_t { UC2_P = 1 /* \p{P} */, UC2_S = 2 /* \p{S} */, UC2_M = 4 /* \p{M} */, UC2_CJK = 8 /* the class of the chain's second Split */ };
 enum : uint8_t { UCC_UPPER = 1 /* [\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}] */, UCC_LOWER = 2 /* [\p{Ll}\p{Lm}\p{Lo}\p{M}] */ };
 
 }  // namespace tkamd
