@@ -376,7 +376,10 @@ int tkamd_profile_enable(tkamd_tokenizer* tok, int on);
 int tkamd_profile_read(tkamd_tokenizer* tok, tkamd_stage_time* stages, int max_stages, int* n_stages, int reset);
 
 /* Work-queue sizes of the last synchronised batch: out[0] = pre-tokens sent to the 16-lane merge
- * kernel, out[1] = to the 64-lane kernel, out[2] = to the workgroup (long) kernel. */
+ * kernel, out[1] = to the 64-lane kernel, out[2] = to the workgroup (long) kernel.  Behind the batch's counters and the handle's
+ * adaptive settings (out[13..17]), the shape of the load-time tables, filled from the handle also before its first batch:
+ * out[18] = slots of the short-word table, out[19] = its displacement buckets, out[20] = its largest displacement,
+ * out[21] = slots of the merge table (out[18..20] are 0 on a host-only handle). */
 int tkamd_profile_counters(tkamd_tokenizer* tok, uint32_t* out, int n);
 
 /* Where the two longest kernels spend their time.  With the test hook TKAMD_PHASES (TKAMD_TEST_HOOKS=1 TKAMD_PHASES=1) the whole-word

@@ -208,6 +208,11 @@ int tkamd_profile_counters(tkamd_tokenizer* t, uint32_t* out, int n) {
         std::lock_guard<std::mutex> lk(t->mu);
         Workspace* w = t->last_used;
         for (int i = 0; i < n; ++i) out[i] = 0;
+        // the shape of the load-time tables, from the handle (also before its first batch; a host-only handle has no short-word table)
+        if (n > 18) out[18] = t->dt.shortw ? t->dt.shortw_mask + 1u : 0u;  // (short-word slots)
+        if (n > 19) out[19] = t->dt.shortw ? t->dt.shortw_bmask + 1u : 0u; // (short-word displacement buckets)
+        if (n > 20) out[20] = t->shortw_max_disp;                          // (the largest short-word displacement: above 255, the placement needed its 16 bits)
+        if (n > 21) out[21] = (uint32_t)t->hm.merge_table.size();          // (merge-table slots)
         if (!w) return TKAMD_OK;
         for (int i = 0; i < n && i < CNT_COUNT; ++i) out[i] = w->last_counters[i];
         if (n > 13) out[13] = (uint32_t)pair_merge_occupancy();            // (workgroups of k_bpe_merge_lds_pair resident per CU: its grid is that x the CUs)

@@ -202,44 +202,46 @@ void verify_direct_words(tkamd_tokenizer* t) {
 }
 
 // The short-word table (tables.hpp): what pass 2 of the lookup probes.  Built from the 32-byte table (the host's copy of record) once
-// its WORD_DIRECT flags are final; same seed (the kernel hashes a key once), its own size.  The displacements must fit eight bits: a
-// placement that needs a larger one gets a table twice the size (a bucket of k keys fits a given displacement with probability
-// (1 - fill)^k, and there are 256 tries).
+// its WORD_DIRECT flags are final; same seed (the kernel hashes a key once), its own size.  The table is packed DENSELY -- every line of
+// it the lookup has to fetch from beyond the L2 costs (kernels/lookup.hip), and a table of half the size stays in the L2 next to the
+// tile's streams where the sparse one was evicted by them: a bucket of k keys fits a given displacement with probability (1 - fill)^k,
+// so with 16-bit displacements (65,536 tries) and at most about eight keys a bucket a table 95 % full still places.  The search, in
+// this order and deterministic: the power of two at or above words / 0.96 slots (62,000 words and 3,900 both land at 0.95 of
+// theirs); the power of two at or above words / 8 buckets, doubled while the placement fails, up to words / 2 (the FEWEST buckets
+// that place win: the displacement array is read in front of every probe and should stay small, 16 KB for 50 k words); only then
+// twice the slots.  (Measured: DESIGN.md section 4, profiles/dense_tables_*.)
 void build_shortw_table(tkamd_tokenizer* t) {
     HostModel& hm = t->hm;
     std::vector<const WordSlot*> ws;
     for (const WordSlot& w : hm.word_table)
         if (w.len) ws.push_back(&w);
-    // the first size tried: the power of two at or above 1.3 slots a word (a fuller table is fewer lines for the caches to hold and more
-    // displacements to try; a size that cannot be placed doubles below)
-    const size_t x10 = 13;
-    // displacement buckets: SHORTW_BUCKETS, four times that for a vocabulary beyond 65,536 words (Llama-3's 128 k: fifteen words a bucket
-    // find no eight-bit displacement in a table less than a quarter full -- 8 MB for 124 k words; four a bucket settle at 47 %, 4 MB)
-    const uint32_t n_buckets = ws.size() > 65536 ? 4u * (uint32_t)SHORTW_BUCKETS : (uint32_t)SHORTW_BUCKETS;
+    const size_t n = ws.size();
     uint32_t cap = 16;
-    while (cap < ws.size() * x10 / 10) cap <<= 1;
-    std::vector<uint32_t> h1(ws.size()), km(ws.size()), where(ws.size());
-    for (size_t i = 0; i < ws.size(); ++i) {
+    while ((uint64_t)cap * 24u < (uint64_t)n * 25u) cap <<= 1;
+    uint32_t nb_first = 16;
+    while ((size_t)nb_first * 8u < n) nb_first <<= 1;
+    std::vector<uint32_t> h1(n), km(n), where(n);
+    for (size_t i = 0; i < n; ++i) {
         h1[i] = word_hash1(ws[i]->lo, ws[i]->hi, ws[i]->len, hm.word_seed);
         km[i] = shortw_kmix((uint32_t)ws[i]->lo, (uint32_t)(ws[i]->lo >> 32), (uint32_t)ws[i]->hi, (uint32_t)(ws[i]->hi >> 32));
     }
-    // hash-and-displace, the fullest buckets first, each takes the smallest displacement < 256 that drops all its words on free slots
-    std::vector<std::vector<uint32_t>> buckets((size_t)n_buckets);
-    for (size_t i = 0; i < ws.size(); ++i) buckets[h1[i] & (n_buckets - 1u)].push_back((uint32_t)i);
-    std::vector<uint32_t> order((size_t)n_buckets);
-    for (uint32_t b = 0; b < n_buckets; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return buckets[x].size() > buckets[y].size(); });
-    std::vector<uint8_t> disp;
-    for (;;) {
+    // hash-and-displace, the fullest buckets first, each takes the smallest displacement < 65,536 that drops all its words on free slots
+    std::vector<uint16_t> disp;
+    std::vector<std::vector<uint32_t>> buckets;
+    std::vector<uint32_t> order, slots;
+    auto place = [&](uint32_t n_buckets) -> bool {
+        buckets.assign((size_t)n_buckets, std::vector<uint32_t>());
+        for (size_t i = 0; i < n; ++i) buckets[h1[i] & (n_buckets - 1u)].push_back((uint32_t)i);
+        order.resize((size_t)n_buckets);
+        for (uint32_t b = 0; b < n_buckets; ++b) order[b] = b;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return buckets[x].size() > buckets[y].size(); });
         std::vector<uint8_t> used((size_t)cap, 0);
         disp.assign((size_t)n_buckets, 0);
-        bool ok = true;
-        std::vector<uint32_t> slots;
         for (uint32_t b : order) {
             const std::vector<uint32_t>& keys = buckets[b];
             if (keys.empty()) break;
             bool placed = false;
-            for (uint32_t d = 0; d < 256u && !placed; ++d) {
+            for (uint32_t d = 0; d < 65536u && !placed; ++d) {
                 slots.clear();
                 bool clash = false;
                 for (uint32_t i : keys) {
@@ -249,15 +251,22 @@ void build_shortw_table(tkamd_tokenizer* t) {
                 }
                 if (clash) continue;
                 for (size_t k = 0; k < keys.size(); ++k) { used[slots[k]] = 1; where[keys[k]] = slots[k]; }
-                disp[b] = (uint8_t)d;
+                disp[b] = (uint16_t)d;
                 placed = true;
             }
-            if (!placed) { ok = false; break; }
+            if (!placed) return false;
         }
-        if (ok) break;
+        return true;
+    };
+    uint32_t n_buckets = nb_first;
+    for (;;) {
+        if (place(n_buckets)) break;
+        if ((size_t)n_buckets * 2u * 2u <= n) { n_buckets <<= 1; continue; }       // (twice the buckets, while that leaves two words a bucket)
         if (cap >= (1u << 26)) throw Invalid("could not build the short-word hash table");
         cap <<= 1;
+        n_buckets = nb_first;
     }
+    t->shortw_max_disp = disp.empty() ? 0u : (uint32_t)*std::max_element(disp.begin(), disp.end());
     std::vector<HotSlot> tab(cap, HotSlot{0u, 0u, 0u, 0u});
     std::vector<uint32_t> k3(cap, 0u);
     for (size_t i = 0; i < ws.size(); ++i) {
@@ -271,7 +280,7 @@ void build_shortw_table(tkamd_tokenizer* t) {
     t->dt.shortw_k3 = t->t_shortw_k3.as<uint32_t>();
     upload(t->t_shortw_disp, disp, 64);
     t->dt.shortw = t->t_shortw.p;
-    t->dt.shortw_disp = t->t_shortw_disp.as<uint8_t>();
+    t->dt.shortw_disp = t->t_shortw_disp.as<uint16_t>();
     t->dt.shortw_mask = cap - 1;
     t->dt.shortw_bmask = n_buckets - 1u;
 }

@@ -29,9 +29,9 @@ struct DevTables {
     uint32_t word_seed;               // seed of the whole-word hashes (the two-choice table of record lives on the host, tables.hpp)
     const void* shortw;               // the short-word table (tables.hpp): every whole word of <= 16 bytes in 16-byte slots
     const uint32_t* shortw_k3;        // bytes 12..15 of the key in slot i
-    const uint8_t* shortw_disp;       // [SHORTW_BUCKETS] eight-bit displacements (the lookup kernel keeps them in LDS)
+    const uint16_t* shortw_disp;      // [shortw_bmask + 1] 16-bit displacements (a hot array in memory: 16 KB for 50 k words)
     uint32_t shortw_mask;
-    uint32_t shortw_bmask;            // buckets - 1 of the displacement array (SHORTW_BUCKETS of them; four times that for vocabularies beyond 65,536 words)
+    uint32_t shortw_bmask;            // buckets - 1 of the displacement array (the fewest that place the table, capi/tables.cpp build_shortw_table)
     uint32_t ignore_merges;
     uint32_t long_probe_max_len;      // whole-word probes of keys > 16 bytes only up to this length (WordPiece: max_input_chars)
     uint32_t unk_id, has_unk;

@@ -28,7 +28,7 @@
 //      <= 12 bytes, hash-and-displace, 16-byte slots.  A hit stores its id; a miss costs one more LDS store: its rank goes to the
 //      workgroup's miss list;
 //   4. PASS 2, the misses only, densely packed 64 to a step (four to five tenths of the pre-tokens on natural text): the full
-//      16-byte key in the short-word table in HBM (tables.hpp: one 16-byte slot behind an 8-bit displacement); what still misses is queued by
+//      16-byte key in the short-word table in HBM (tables.hpp: one 16-byte slot behind a 16-bit displacement); what still misses is queued by
 //      length class: every workgroup appends to its OWN sub-queue of each queue (results.hip) -- the position comes from an
 //      LDS counter, no global atomic -- the queue entry is (start, length), and
 //      the tok0 word of a queued pre-token names the row its result will be written to (results.hip).
@@ -41,7 +41,7 @@ static_assert(LU_TILE == LOOKUP_TILE_BYTES, "the host sizes the sub-queues per t
 constexpr int LU_TEXT_SLACK = 64;                        // staged past the tile: a key may start at its last byte
 // The shape: a hot-word table of 1,024 slots (16.5 KB), 3,072 pre-tokens expanded per round (a tile of prose holds ~2,700): 52 KB of LDS and
 // <= 80 VGPRs, THREE workgroups per CU -- passes 2 and 3 wait for memory, and more wavefronts hide more of it; the short-word
-// displacements are read from memory (a hot 8 KB array), pass 2 takes one step at a time.  (Rounds 3-5 also shipped a two-workgroup shape
+// displacements are read from memory (a hot 16 KB array), pass 2 takes one step at a time.  (Rounds 3-5 also shipped a two-workgroup shape
 // with 2,048 hot slots and the displacements in LDS -- 0.2279 against 0.2237 ms on C2, slower on C3 -- and a FUSED shape with the
 // pre-tokenizer and the mask scan inside this kernel -- parity-green, 0.474 ms against 0.285 for the three kernels; both were deleted in
 // round 6, HISTORY.md has their measurements.)
@@ -65,7 +65,7 @@ struct LookupArgs {
     uint32_t word_seed;
     const uint4* shortw;             // the short-word table behind the hot table (tables.hpp): 16-byte slots {k0, k1, k2, id | len << 24 | SHORTW_DIRECT}
     const uint32_t* shortw_k3;       // bytes 12..15 of the key in slot i (read by the pre-tokens longer than 12 bytes only)
-    const uint8_t* shortw_disp;      // [SHORTW_BUCKETS] the displacements: copied into LDS (shape HOT = 2048)
+    const uint16_t* shortw_disp;     // [shortw_bmask + 1] the 16-bit displacements (read from memory: a hot array of 16 KB for 50 k words)
     uint32_t shortw_mask;
     uint32_t shortw_bmask;           // displacement buckets - 1
     uint32_t any_hit_final;          // ignore_merges / WordLevel / WordPiece: every hit is final (else only WORD_DIRECT ones)
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(LU_NT, LU_WAVES_PER_SIMD) void k_lookup(LookupArgs 
     if (tid == 0) { s_seen = 0u; s_shared = 0u; s_claims_on = a.claims ? 1u : 0u; }
     static_assert(hot_table_bytes(HOT) % 16 == 0, "whole 16-byte words");
     for (int i = tid; i < hot_table_bytes(HOT) / 16; i += LU_NT) s_hot[i] = a.hot[i];      // (slots and displacements: one buffer)
-    const uint8_t* const wdisp = a.shortw_disp;                    // the short-word displacements: a hot 8 KB array in memory
+    const uint16_t* const wdisp = a.shortw_disp;                   // the short-word displacements: a hot 16 KB array in memory
     if (tid < 17) {
         const uint32_t l = (uint32_t)tid;
         auto m = [&](uint32_t lo) -> uint32_t { return l >= lo + 4u ? 0xFFFFFFFFu : (l > lo ? ((1u << (8u * (l - lo))) - 1u) : 0u); };

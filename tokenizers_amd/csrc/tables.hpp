@@ -80,7 +80,7 @@ TK_HD uint32_t ph_slot(uint32_t h2, uint32_t d, uint32_t mask) { return (h2 + mu
 // Static TWO-CHOICE table, HOST ONLY since round 5: a key lives in slot word_slot_a or word_slot_b of its hash (cuckoo insertion at
 // load, load factor <= 0.4).  It is the copy of record -- the WORD_DIRECT flags are proved on it (verify_direct_words), tkamd_probe_word
 // reads it, and the table the lookup kernel PROBES, the short-word table below, is built from it.  (Round 4 probed it on the device,
-// both 32-byte slots in one round trip: slower than one 16-byte slot behind an 8-bit displacement, profiles/r4i-k.)
+// both 32-byte slots in one round trip: slower than one 16-byte slot behind a small displacement array, profiles/r4i-k.)
 struct WordSlot {
     uint64_t lo, hi;
     uint32_t len;    // 0 = empty slot
@@ -106,8 +106,11 @@ TK_HD uint32_t word_slot_b(uint32_t h1, uint32_t mask) {       // (never slot a:
 // ---- the short-word table: every word of the table above once more, in 16-byte slots (device only, built when the flags above are
 // final) -- what pass 2 of the lookup kernel probes:  slot = {k0, k1, k2, id | len << 24 | SHORTW_DIRECT}, bytes 12..15 of the key
 // in a parallel array k3[slot] that only the 3 % of pre-tokens longer than 12 bytes read (same index: no dependent load).
-// Hash-and-displace with EIGHT-bit displacements over SHORTW_BUCKETS buckets: the 8 KB of displacements sit in the kernel's LDS, so
-// a probe is ONE 16-byte request at ONE random line.  bucket = h1 & (SHORTW_BUCKETS - 1), slot = shortw_slot(h1, key mix, d, mask).
+// Hash-and-displace with 16-bit displacements: the displacement array is small and hot (16 KB for 50 k words), so a probe is ONE
+// 16-byte request at ONE random line.  bucket = h1 & (buckets - 1), slot = shortw_slot(h1, key mix, d, mask).  The builder
+// (capi/tables.cpp build_shortw_table) packs the table up to 95 % full with the fewest buckets that place it: until the dense tables the
+// displacements had eight bits, which forced a table at 0.38 load (2 MB + 0.5 MB of k3 for 50 k words, at the edge of an XCD's 4 MB of L2
+// while the tile's streams pass through it); 16 bits place the same words in half of that.
 // How it got there, as measured in round 4 (the table was displacement-in-HBM + one 32-byte slot before: 0.233..0.243 ms for the
 // kernel on C2, 0.44..0.455 on out-of-distribution text): both 32-byte slots of a two-choice table at once -- four requests, ONE
 // round trip -- 0.265 ms; both 16-byte slots of a two-choice table -- two requests, one round trip -- 0.257 ms (profiles/r4i_*,
@@ -115,7 +118,6 @@ TK_HD uint32_t word_slot_b(uint32_t h1, uint32_t mask) {       // (never slot a:
 // there, one here), not the length of its chain.  One 16-byte slot behind an LDS displacement: 0.235 / 0.40 ms (r4k_*).
 constexpr uint32_t SHORTW_DIRECT = 0x80000000u;
 constexpr uint32_t SHORTW_LEN_SHIFT = 24, SHORTW_LEN_MASK = 0x1Fu, SHORTW_ID_MASK = 0xFFFFFFu;
-constexpr int SHORTW_BUCKETS = 8192;
 // The slot: double hashing on the displacement -- (base + d * step) & mask, base and step from the key bytes once more.  The table
 // shares the 32-byte table's seed (the kernel hashes a key once), so it cannot answer an unlucky placement with another seed: a
 // displacement that moves every key of a bucket by the SAME amount (the merge table's ph_slot) can never part two keys of a bucket

@@ -1101,8 +1101,8 @@ class Tokenizer:
 
     def queue_sizes(self) -> dict[str, int]:
         """Merge work-queue sizes of the last synchronised batch (diagnostics)."""
-        arr = (C.c_uint32 * 18)()
-        _lib.check(self._lib.tkamd_profile_counters(self._h, arr, 18))
+        arr = (C.c_uint32 * 22)()
+        _lib.check(self._lib.tkamd_profile_counters(self._h, arr, 22))
         out = {"merge16": arr[0], "merge32": arr[3], "merge64": arr[1], "merge_long": arr[2], "pretok_slow_docs": arr[4], "merge_huge": arr[7]}
         if arr[5]:                                       # in-batch claims: candidates the lookup looked at / how many were another pre-token's word
             out["claim_candidates"], out["claim_shared"] = arr[5], arr[6]
@@ -1110,6 +1110,8 @@ class Tokenizer:
         out["nfc_spec_pause"], out["nfc_reruns"] = arr[16], arr[17]      # behind an NFC normalizer: batches that will normalize outright / batches run again (the quick check failed)
         out["merge_pair_wg_per_cu"] = arr[13]            # resident workgroups per CU of the launch that merges both LDS queues (its grid is that x the CUs)
         out["q16_div"] = arr[15]                         # the <= 16-byte queue holds n_bytes / q16_div entries (a queue overflow re-runs the batch with 2, then 1)
+        # the shape of the load-time tables (known before the first batch): short-word slots / displacement buckets / largest displacement, merge slots
+        out["shortw_slots"], out["shortw_buckets"], out["shortw_max_disp"], out["merge_slots"] = arr[18], arr[19], arr[20], arr[21]
         if arr[12]:                                      # (profiling runs) merge-table probes of the LDS merge kernels, (k - 1) + 2 m per word
             out["merge_probes"] = arr[12]
         return out
