@@ -96,7 +96,7 @@ typedef struct tkamd_batch     tkamd_batch;      /* one encode_batch result (hos
 
 /* What was recognised in tokenizer.json (for the host shim / diagnostics). */
 typedef struct tkamd_info {
-    int32_t model;          /* 1 BPE, 2 WordPiece, 3 WordLevel                                  */
+    int32_t model;          /* 1 BPE, 2 WordPiece, 3 WordLevel, 4 Unigram                       */
     int32_t pre_tokenizer;  /* 1 ByteLevel(GPT-2 regex; also that regex spelled as a Split), 2 Split(a pattern of the tiktoken family:
                                Llama-3 / cl100k, Qwen2, o200k, tekken ...; pre_tokenizers/split.rs:76-105) + ByteLevel, 3 Whitespace,
                                4 WhitespaceSplit, 5 BertPreTokenizer, 6 ByteLevel(use_regex=false), 7 the U+2581 front of SentencePiece-style BPE,

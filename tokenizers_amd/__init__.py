@@ -1,7 +1,7 @@
 """tokenizers_amd -- MI355X-native ``encode_batch`` for huggingface/tokenizers.
 
 One hot path, nothing else: ByteLevel / Whitespace / Bert pre-tokenization ->
-BPE / WordPiece / WordLevel -> token-id CSR arrays, as hand-written HIP kernels
+BPE / WordPiece / WordLevel / Unigram -> token-id CSR arrays, as hand-written HIP kernels
 for gfx950 behind a C ABI (``include/tokenizers_amd.h``).  See DESIGN.md.
 """
 from ._lib import DeviceError, TokenizersAmdError, UnsupportedError  # noqa: F401

@@ -33,6 +33,7 @@ struct Workspace {
         w_match_docs, w_match_list;
     // host entry staging
     DevBuf h_text, h_doc_off, h_seq_off, h_inp_off;
+    DevBuf w_uni_state, w_uni_flags;             // Unigram: Viterbi state of the words beyond 64 bytes, 16 bytes per text byte (kernels/unigram.hip); a byte per token: a fallback token
     DevBuf w_tok_b8;                             // with offsets: per token, the boundary byte its row carried (kernels/results.hip row_boundary)
     DevBuf w_trim1;                              // per token: process_offsets took one leading space off it (MetaArgs::trim1)
     const uint8_t* cur_trim1 = nullptr;          // ... of the batch being enqueued, or null
@@ -92,7 +93,7 @@ struct tkamd_tokenizer {
     DevBuf t_at_id[2], t_at_flags[2], t_at_blob[2], t_at_off[2], t_at_first[2];   // AddedVocabulary patterns of the two matching passes
     DevBuf t_pp_single, t_pp_single_plain;      // the single layout as pieces (the single inputs of a mixed batch)
     DevBuf t_pp_pair, t_pp_pair_plain;   // pair template of the post-processor with / without its special tokens: [pieces][3]
-    DevBuf t_pp_prefix, t_pp_suffix, t_pp_prefix_ty, t_pp_suffix_ty, t_bn1, t_bn2, t_bn_map, t_nfc1, t_nfc2, t_nfc_map, t_merge_disp, t_dec_entry, t_dec_blob, t_trie;
+    DevBuf t_pp_prefix, t_pp_suffix, t_pp_prefix_ty, t_pp_suffix_ty, t_bn1, t_bn2, t_bn_map, t_nfc1, t_nfc2, t_nfc_map, t_merge_disp, t_dec_entry, t_dec_blob, t_trie, t_uni_score, t_uni_is_byte;
     int n_cu = 256;
     int n_direct = 0;
     int n_hot = 0;

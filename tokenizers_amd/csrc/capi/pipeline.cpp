@@ -179,9 +179,10 @@ void Batch::check_request() {
     const bool local_pretok = hm.pretok == PT_WHITESPACE || hm.pretok == PT_WHITESPACE_SPLIT || hm.pretok == PT_BERT;
     const bool word_models = (hm.model == MODEL_WORDLEVEL || hm.model == MODEL_WORDPIECE) && local_pretok;
     const bool char_bpe = hm.model == MODEL_BPE && hm.char_bpe && (local_pretok || metaspace);      // BPE over characters rides the word models' pre-tokenizers, or the "▁" front
-    if (!bpe_path && !word_models && !char_bpe)
+    const bool unigram = hm.model == MODEL_UNIGRAM && metaspace;                                     // Unigram: behind the "▁" front (split = true) only
+    if (!bpe_path && !word_models && !char_bpe && !unigram)
         throw Unsupported("this build covers {ByteLevel(GPT-2 regex), Llama-3 Split+ByteLevel, ByteLevel(no regex)}+BPE and "
-                          "{Whitespace,WhitespaceSplit,BertPreTokenizer}+{WordLevel,WordPiece,BPE over characters} and the U+2581 front+BPE over characters");
+                          "{Whitespace,WhitespaceSplit,BertPreTokenizer}+{WordLevel,WordPiece,BPE over characters} and the U+2581 front+{BPE over characters, Unigram}");
     if (prefix_space && hm.norm != NORM_NONE) throw Unsupported("ByteLevel add_prefix_space behind a normalizer");
     // what the epilogues see: one encoding per document, or per sequence of words
     words_in = n_seqs >= 0;
@@ -218,7 +219,7 @@ void Batch::zero_batch_state() {
     const char* const claims_hook = test_hook("TKAMD_CLAIMS");
     const bool claims_on = !(claims_hook && !strcmp(claims_hook, "0"));
     use_claims = claims_on && !t->word_cache &&
-                 (hm.model == MODEL_BPE || (hm.model == MODEL_WORDPIECE && hm.max_input_chars >= (uint32_t)WORD_MAX_KEY));
+                 (hm.model == MODEL_BPE || hm.model == MODEL_UNIGRAM || (hm.model == MODEL_WORDPIECE && hm.max_input_chars >= (uint32_t)WORD_MAX_KEY));
     if (use_claims) {                                      // paused by an earlier batch that shared nothing (read_scalars)? one batch less to go
         int p = t->claims_pause.load();
         while (p > 0 && !t->claims_pause.compare_exchange_weak(p, p - 1)) {}
@@ -834,6 +835,20 @@ void Batch::run_model() {
             launch_word_cache_insert(st, grid, mdt, x_text, plan.v[0], w->w_rows.p, wc);
             pf.end();
         }
+    } else if (hm.model == MODEL_UNIGRAM) {
+        // Unigram::tokenize (unigram/model.rs:443-477): the lookup settles a pre-token that is a piece whose own Viterbi was proved at load
+        // to yield [id] (WORD_DIRECT; no other hit is final), the claims keep one occurrence of every other word, and the Unigram kernel
+        // runs the search on those.  (The reference's per-model cache changes no result; the word cache across batches stays closed.)
+        if (use_claims) open_word_cache();
+        set_publish();
+        pf.begin("lookup");
+        launch_lookup(st, lookup_grid(t), t->dt, x_text, n_x, x_len_dev, w->w_startmask.as<ull>(), endmask, w->w_wprefix.as<uint32_t>(),
+                      w->w_tok0.as<uint32_t>(), plan, d_err, matchmask, t->t_hot.p, wc, 0u, 0u, phases_of(0), d_counters);
+        pf.end();
+        w->w_uni_state.reserve(N > 64 ? (N + 2) * 16 : 64);      // (a word beyond 64 bytes keeps its state at its own bytes: kernels/unigram.hip)
+        pf.begin("unigram");
+        launch_unigram_all(st, grid, t->n_cu, mdt, x_text, plan, w->w_rows.p, w->w_tmp_ids.as<uint32_t>(), tmp_end, d_err, w->w_uni_state.p);
+        pf.end();
     } else if (hm.model == MODEL_WORDLEVEL) {
         // WordLevel::tokenize (wordlevel/mod.rs:162-178) is the lookup itself: every hit is final, a miss is the unk id
         DevTables wt = t->dt;
@@ -923,7 +938,7 @@ void Batch::compact_and_meta() {
         a.norig = norig;                                   // normalised / shifted text: every byte's original byte range
         a.norig_e = norig_e;
         a.byte_level = hm.byte_level;
-        a.snap_chars = hm.byte_level || hm.char_bpe;
+        a.snap_chars = hm.byte_level || hm.char_bpe || hm.uni_bytes;      // (Unigram's <0xXX> tokens cut their char like BPE's)
         if (hm.char_bpe && !hm.unk_configured && !hm.byte_fallback) {      // (chars can be dropped: offsets are running sums)
             a.char_id = t->dt.char_id;
             a.cb = t->dt.cb;
@@ -958,6 +973,18 @@ void Batch::compact_and_meta() {
         pf.begin("token_meta");
         launch_token_meta(st, grid, a);
         pf.end();
+        if (a.want_offsets && hm.uni_bytes) {
+            // Unigram byte_fallback: every <0xXX> token of a run carries the WHOLE run's offsets (unigram/model.rs:459); token_meta gave each
+            // its own char's.  The documents' token CSR (the words', for pre-tokenized input): a run never crosses a document.
+            // k_unigram_run_offsets reads the runs off the result; what it relies on: (1) split = true, so every pre-token that follows another
+            // inside a piece begins with a U+2581 (k_ms_units marks every U+2581; refused otherwise, host_model.cpp); (2) that U+2581 is a piece
+            // and the unk piece does not begin with one, so no unk node -- and no fallback run -- starts there (both checked at load); (3) a
+            // pre-token that opens a piece follows a document edge (the CSR) or an added-token match, whose token is no fallback token
+            w->w_uni_flags.reserve((size_t)n_x + 64);
+            pf.begin("unigram_run_offsets");
+            launch_unigram_run_offsets(st, grid, t->dt, w->w_ids.as<uint32_t>(), a.offsets, w->w_tok_offsets.as<int64_t>(), n_docs, d_ntok_total, w->w_uni_flags.as<uint8_t>());
+            pf.end();
+        }
         if (a.want_offsets) out->d_offsets = a.offsets;
         if (a.want_words) out->d_word_ids = a.word_ids;
     }

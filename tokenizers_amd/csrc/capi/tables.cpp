@@ -126,6 +126,23 @@ void upload_tables(tkamd_tokenizer* t) {
     d.trie_mask = hm.trie.mask;
     d.trie_seed = hm.trie.seed;
     d.max_input_chars = hm.max_input_chars;
+    // Unigram (host_model.cpp; unigram_core.hpp)
+    d.uni_score = nullptr;
+    d.uni_unk_score = hm.uni_unk_score;
+    d.uni_is_byte = nullptr;
+    d.uni_bytes = hm.uni_bytes ? 1u : 0u;
+    d.uni_n_ids = 0u;
+    if (hm.model == MODEL_UNIGRAM) {
+        upload(t->t_uni_score, hm.uni_score);
+        d.uni_score = t->t_uni_score.as<double>();
+        if (hm.uni_bytes) {
+            std::vector<uint8_t> isb(hm.uni_score.size(), 0);
+            for (int b = 0; b < 256; ++b) isb[hm.byte_id[b]] = 1;
+            upload(t->t_uni_is_byte, isb);
+            d.uni_is_byte = t->t_uni_is_byte.as<uint8_t>();
+            d.uni_n_ids = (uint32_t)isb.size();
+        }
+    }
     // BPE over characters (host_model.cpp: char_id; tables.hpp CB_*)
     d.char_id = nullptr;
     d.cb = 0u;
@@ -141,7 +158,7 @@ void upload_tables(tkamd_tokenizer* t) {
 // entry and keep the flag only where merge_word's result is exactly [own id].
 void verify_direct_words(tkamd_tokenizer* t) {
     HostModel& hm = t->hm;
-    if (hm.model != MODEL_BPE || hm.n_words == 0) return;
+    if ((hm.model != MODEL_BPE && hm.model != MODEL_UNIGRAM) || hm.n_words == 0) return;
     std::vector<uint8_t> text;
     std::vector<uint32_t> starts, slot_of;
     for (uint32_t sidx = 0; sidx <= hm.word_mask; ++sidx) {
@@ -170,7 +187,21 @@ void verify_direct_words(tkamd_tokenizer* t) {
     d_tmp.reserve(n * 4 + 64);
     HIP_CHECK(hipMemset(d_rows.p, 0, (size_t)P * 16));
     const QView v{(QItem*)d_items.p, d_n.as<uint32_t>(), P, 0u};
-    if (hm.char_bpe) {
+    if (hm.model == MODEL_UNIGRAM) {
+        // Unigram: a whole-word hit is final only if the Viterbi of the word alone yields exactly [id] (with unusual scores a split wins);
+        // the Unigram kernel itself says so.  Every word in the <= 16-byte queue, the three others empty; errors (a word that needs an unk
+        // the model lacks) do not count, nothing is published
+        DevBuf d_errs, d_zero;
+        d_errs.reserve(64);
+        HIP_CHECK(hipMemset(d_errs.p, 0, 64));
+        std::vector<uint32_t> zero((size_t)NSQ * QCNT_STRIDE, 0u);
+        upload(d_zero, zero);
+        QueuePlan plan{};
+        plan.v[0] = v;
+        for (int c = 1; c < 4; ++c) plan.v[c] = QView{(QItem*)d_items.p, d_zero.as<uint32_t>(), 1u, 0u};
+        launch_unigram_all(nullptr, std::max(1, (int)std::min<uint32_t>(P / 256 + 1, 4096)), 1, t->dt, d_text.as<uint8_t>(), plan, d_rows.p, d_tmp.as<uint32_t>(), nullptr,
+                           d_errs.as<int>(), nullptr);
+    } else if (hm.char_bpe) {
         // BPE over characters: the kernels that know its start; nothing is published, errors of the vocabulary's own entries do not count
         DevBuf d_errs, d_hl;
         d_errs.reserve(64);
@@ -295,7 +326,7 @@ void build_hot_table(tkamd_tokenizer* t) {
     std::vector<HotSlot> hot(slots, HotSlot{0u, 0u, 0u, 0u});
     std::vector<uint16_t> disp(n_buckets, 0);
     std::vector<const WordSlot*> cand;
-    const bool all_final = hm.model != MODEL_BPE || hm.ignore_merges;
+    const bool all_final = (hm.model != MODEL_BPE && hm.model != MODEL_UNIGRAM) || hm.ignore_merges;
     for (const WordSlot& w : hm.word_table)
         if (w.len && w.len <= (uint32_t)HOT_MAX_KEY && (all_final || (w.flags & WORD_DIRECT))) cand.push_back(&w);
     // the lowest ids (= the most frequent words: the trainers append tokens in frequency order), as many as fit at 15/16 full

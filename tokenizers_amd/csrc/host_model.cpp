@@ -5,9 +5,11 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <random>
 #include <set>
 #include <unordered_map>
@@ -349,7 +351,7 @@ void build_trie(HostModel& m, const std::vector<std::pair<std::string, uint32_t>
     std::vector<MergeSlot> items;
     for (uint32_t n = 0; n < nodes.size(); ++n)
         for (auto& e : nodes[n].kids) items.push_back(MergeSlot{n, (uint32_t)e.first, e.second, nodes[e.second].id});
-    if (nodes.size() >= ((size_t)1 << 24)) throw Unsupported("WordPiece trie beyond 2^24 nodes");
+    if (nodes.size() >= ((size_t)1 << 24)) throw Unsupported("byte trie of the vocabulary (WordPiece / Unigram) beyond 2^24 nodes");
     m.trie.n_nodes = (uint32_t)nodes.size();
     build_pair_table(items, &m.trie.table, &m.trie.mask, &m.trie.seed);
 }
@@ -623,6 +625,92 @@ bool parse_split_chain(const JsonValue* seq, HostModel& m) {
 
 const char* const kMetaspace = "\xE2\x96\x81";     // U+2581, the "▁" of SentencePiece
 
+// A JSON number as serde_json reads it into an f64 WITHOUT its float_roundtrip feature -- how the reference is built (tokenizers/Cargo.toml:
+// serde_json = "1.0", no features) and so what its Unigram scores are: the digits are gathered into a u64 significand (those that no
+// longer fit are dropped), converted to f64 and multiplied or divided by ONE power of ten from a table (serde_json src/de.rs parse_integer,
+// parse_decimal, parse_decimal_overflow, parse_long_integer, parse_exponent, f64_from_parts).  Two roundings where strtod makes one: 153 of
+// the 3,000 seeded scores of tests/golden/unigram_ms come out one ulp off strtod's, and a Viterbi comparison can turn on that ulp.
+double serde_json_f64(const std::string& t) {
+    static const std::vector<double> pow10 = [] { std::vector<double> p; for (int e = 0; e <= 308; ++e) p.push_back(strtod(("1e" + std::to_string(e)).c_str(), nullptr)); return p; }();
+    size_t i = 0;
+    const size_t n = t.size();
+    auto digit_at = [&](size_t k) { return k < n && t[k] >= '0' && t[k] <= '9'; };
+    auto would_overflow = [](uint64_t a, uint64_t b) { const uint64_t c = ~0ull; return a >= c / 10 && (a > c / 10 || b > c % 10); };
+    const bool positive = !(n && t[0] == '-');
+    if (!positive) ++i;
+    if (!digit_at(i)) throw Invalid("tokenizer.json: bad number '" + t + "'");
+    uint64_t sig = 0;
+    int32_t exponent = 0;
+    bool is_float = false;
+    if (t[i] == '0') ++i;
+    else {
+        while (digit_at(i)) {
+            const uint64_t d = (uint64_t)(t[i] - '0');
+            if (would_overflow(sig, d)) {                 // parse_long_integer: the digits that no longer fit only count
+                is_float = true;
+                while (digit_at(i)) { ++i; ++exponent; }
+                break;
+            }
+            sig = sig * 10 + d;
+            ++i;
+        }
+    }
+    if (i < n && t[i] == '.') {
+        is_float = true;
+        ++i;
+        if (!digit_at(i)) throw Invalid("tokenizer.json: bad number '" + t + "'");
+        while (digit_at(i)) {
+            const uint64_t d = (uint64_t)(t[i] - '0');
+            if (would_overflow(sig, d)) {                 // parse_decimal_overflow: "just ignore all further digits"
+                while (digit_at(i)) ++i;
+                break;
+            }
+            sig = sig * 10 + d;
+            --exponent;
+            ++i;
+        }
+    }
+    if (i < n && (t[i] == 'e' || t[i] == 'E')) {
+        is_float = true;
+        ++i;
+        bool pos_exp = true;
+        if (i < n && (t[i] == '+' || t[i] == '-')) { pos_exp = t[i] == '+'; ++i; }
+        if (!digit_at(i)) throw Invalid("tokenizer.json: bad number '" + t + "'");
+        int64_t ex = 0;
+        bool huge = false;
+        while (digit_at(i)) { ex = ex * 10 + (t[i] - '0'); if (ex > 0x7FFFFFFFll) { huge = true; ex = 0x7FFFFFFFll; } ++i; }
+        if (huge) {                                       // parse_exponent_overflow
+            if (sig != 0 && pos_exp) throw Invalid("tokenizer.json: number out of range '" + t + "'");
+            return positive ? 0.0 : -0.0;
+        }
+        const int64_t fe = pos_exp ? (int64_t)exponent + ex : (int64_t)exponent - ex;
+        exponent = (int32_t)std::max<int64_t>(std::min<int64_t>(fe, 0x7FFFFFFFll), -0x80000000ll);
+    }
+    if (i != n) throw Invalid("tokenizer.json: bad number '" + t + "'");
+    if (!is_float) {
+        // an integer: u64, or i64 when negative and in range; `as f64` rounds to nearest
+        if (positive) return (double)sig;
+        const int64_t neg = (int64_t)(0ull - sig);
+        return neg >= 0 ? -(double)sig : (double)neg;
+    }
+    double f = (double)sig;                               // f64_from_parts
+    for (;;) {
+        const uint32_t a = exponent < 0 ? (uint32_t)(-(int64_t)exponent) : (uint32_t)exponent;
+        if (a < pow10.size()) {
+            if (exponent >= 0) {
+                f *= pow10[a];
+                if (std::isinf(f)) throw Invalid("tokenizer.json: number out of range '" + t + "'");
+            } else f /= pow10[a];
+            break;
+        }
+        if (f == 0.0) break;
+        if (exponent >= 0) throw Invalid("tokenizer.json: number out of range '" + t + "'");
+        f /= 1e308;
+        exponent += 308;
+    }
+    return positive ? f : -f;
+}
+
 PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
     if (!pt || pt->is_null()) {
         // the "▁" normalizers leave every piece ONE pre-token (the device cuts it into units: the model check below proves that exact)
@@ -735,8 +823,9 @@ static std::string wp_cleanup(std::string t) {
 //                                                     then cleanup()
 //   none      (mod.rs:950-952)                        tokens.join(" ")
 // so decoding is a gather of precomputed byte strings.
+// by_index (Unigram): id -> piece of an array vocabulary, where two ids may share a piece and `vocab` only knows the later one
 static void build_decode_tables(HostModel& m, const JsonValue* root, const std::unordered_map<std::string, uint32_t>& vocab,
-                                const std::unordered_map<uint32_t, uint8_t>& c2b) {
+                                const std::unordered_map<uint32_t, uint8_t>& c2b, const std::vector<std::string>* by_index = nullptr) {
     const JsonValue* dec = root->get("decoder");
     std::string prefix = "##", suffix = "</w>", ctc_pad, ctc_delim, post_strip;
     bool cleanup = true, chain_bytes = false;
@@ -850,11 +939,14 @@ static void build_decode_tables(HostModel& m, const JsonValue* root, const std::
     // id -> token string: model vocabulary, overridden by the added vocabulary (added_vocabulary.rs:239-246)
     uint32_t n_ids = 0;
     for (auto& kv : vocab) n_ids = std::max(n_ids, kv.second + 1);
+    if (by_index) n_ids = std::max(n_ids, (uint32_t)by_index->size());
     for (const AddedToken& a : m.added_tokens) n_ids = std::max(n_ids, a.id + 1);
     if (n_ids > (1u << 26)) { m.decoder = DEC_UNSUPPORTED; m.dec_unsupported = "token ids beyond 2^26"; return; }
     std::vector<const std::string*> tok(n_ids, nullptr);
     std::vector<uint8_t> special(n_ids, 0);
     for (auto& kv : vocab) tok[kv.second] = &kv.first;
+    if (by_index)
+        for (size_t i = 0; i < by_index->size(); ++i) tok[i] = &(*by_index)[i];
     std::unordered_map<std::string, bool> special_set;
     for (const AddedToken& a : m.added_tokens) {
         if (a.normalized && m.norm != NORM_NONE) {
@@ -1210,18 +1302,46 @@ HostModel HostModel::from_json(const char* json, size_t len) {
         else if (model->get("continuing_subword_prefix")) mtype = "WordPiece";
         else mtype = "WordLevel";
     }
-    if (!vocab || !vocab->is_object()) throw Invalid("tokenizer.json: model.vocab missing");
+    // Unigram keeps its vocabulary as an ARRAY of [piece, score], id = index (models/unigram/serialization.rs:13-30); every other model
+    // as an object piece -> id.  Both fill the same map `v` that added tokens, templates, padding and the decode tables read.
+    const bool unigram = mtype == "Unigram";
+    if (unigram ? !(vocab && vocab->is_array()) : !(vocab && vocab->is_object())) throw Invalid("tokenizer.json: model.vocab missing");
 
     std::unordered_map<std::string, uint32_t> v;
-    v.reserve(vocab->obj.size() * 2);
-    for (auto& kv : vocab->obj) {
-        if (!kv.second->is_number()) throw Invalid("tokenizer.json: vocab id is not a number");
-        v[kv.first] = (uint32_t)kv.second->num;   // duplicate keys: last wins, like serde's map
-        // the pair hashes (tables.hpp) multiply 24-bit operands and the result rows keep ids in 24 bits: larger ids would
-        // collide for every seed, so they are refused here with the reason instead of failing table construction
-        if (kv.second->num < 0 || kv.second->num >= (double)(1u << 24)) throw Unsupported("token id beyond 2^24 (vocab entry '" + kv.first + "')");
+    std::vector<std::string> uni_pieces;      // Unigram: id -> piece, per index (id_to_token, unigram/model.rs:483-485)
+    if (unigram) {
+        // Unigram::from (unigram/model.rs:104-151): token_to_ids.insert in index order -- of two equal pieces the LATER id encodes --,
+        // min_score over every entry (the shadowed and the unk piece included); scores are f64 as the reference's own JSON reader rounds them
+        // (serde_json_f64 above: not always strtod's value)
+        const size_t n = vocab->arr.size();
+        if (n == 0) throw Unsupported("model: Unigram with an empty vocab (EmptyVocabulary) is outside the hot path");
+        if (n >= ((size_t)1 << 24)) throw Unsupported("token id beyond 2^24 (Unigram vocab of " + std::to_string(n) + " pieces)");
+        v.reserve(n * 2);
+        uni_pieces.reserve(n);
+        m.uni_score.reserve(n);
+        double min_score = std::numeric_limits<double>::infinity();
+        for (size_t i = 0; i < n; ++i) {
+            const JsonValue* e = vocab->arr[i].get();
+            if (!e->is_array() || e->arr.size() != 2 || !e->arr[0]->is_string() || !e->arr[1]->is_number())
+                throw Invalid("tokenizer.json: Unigram vocab entry " + std::to_string(i) + " is not [piece, score]");
+            v[e->arr[0]->str] = (uint32_t)i;
+            uni_pieces.push_back(e->arr[0]->str);
+            const double score = serde_json_f64(e->arr[1]->str);
+            m.uni_score.push_back(score);
+            if (score < min_score) min_score = score;
+        }
+        m.uni_unk_score = min_score - 10.0;      // K_UNK_PENALTY, unigram/model.rs:277
+    } else {
+        v.reserve(vocab->obj.size() * 2);
+        for (auto& kv : vocab->obj) {
+            if (!kv.second->is_number()) throw Invalid("tokenizer.json: vocab id is not a number");
+            v[kv.first] = (uint32_t)kv.second->num;   // duplicate keys: last wins, like serde's map
+            // the pair hashes (tables.hpp) multiply 24-bit operands and the result rows keep ids in 24 bits: larger ids would
+            // collide for every seed, so they are refused here with the reason instead of failing table construction
+            if (kv.second->num < 0 || kv.second->num >= (double)(1u << 24)) throw Unsupported("token id beyond 2^24 (vocab entry '" + kv.first + "')");
+        }
     }
-    m.vocab_size = (uint32_t)v.size();
+    m.vocab_size = unigram ? (uint32_t)uni_pieces.size() : (uint32_t)v.size();      // (get_vocab_size: the array's length, duplicates and all, unigram/model.rs:439-441)
     if (m.trim_offsets && !m.byte_level) {
         // a trimming post-processor (ByteLevel / RobertaProcessing) on a model that is not byte-level: process_offsets moves the offsets
         // of every token whose STRING starts or ends with whitespace or 'Ġ' (byte_level.rs:202-234).  The added tokens' raw slices
@@ -1288,7 +1408,7 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     }
     const size_t n_raw_plain = m.raw_tokens.size();
 
-    build_decode_tables(m, root.get(), v, c2b);
+    build_decode_tables(m, root.get(), v, c2b, unigram ? &uni_pieces : nullptr);
 
     auto opt_str = [&](const char* key, std::string* out) -> bool {
         const JsonValue* x = model->get(key);
@@ -1410,10 +1530,53 @@ HostModel HostModel::from_json(const char* json, size_t len) {
         m.unk_token = model->get_str("unk_token", "<unk>");
         auto it = v.find(m.unk_token);
         if (it != v.end()) { m.has_unk = true; m.unk_id = it->second; }
+    } else if (unigram) {
+        // Unigram (models/unigram/model.rs): a Viterbi search per pre-token over f64 scores (unigram_core.hpp, kernels/unigram.hip).  On the
+        // path behind Metaspace(split = true) alone: the front's other layouts cut a piece into units, and a comparison of prefix + score
+        // sums made on a unit alone can round differently from the reference's, made over the whole piece
+        m.model = MODEL_UNIGRAM;
+        if (m.pretok != PT_METASPACE) {
+            const JsonValue* pt = root->get("pre_tokenizer");
+            const std::string ptype = (pt && pt->is_object()) ? pt->get_str("type") : "null";
+            throw Unsupported("model: Unigram (a vocab of scored pieces) is on the path behind Metaspace(split = true) only; pre_tokenizer '" + ptype + "' is not");
+        }
+        if (m.norm != NORM_NONE || !m.ms_split)
+            throw Unsupported("model: Unigram (a vocab of scored pieces) over whole pieces -- Metaspace(split = false), or a null pre_tokenizer behind the U+2581 "
+                              "normalizers -- is outside the hot path: the front cuts such a piece into units, and the reference compares f64 sums of "
+                              "prefix + score over the whole piece, which a unit alone can round differently (only Metaspace(split = true) is on the path)");
+        const JsonValue* uk = model->get("unk_id");
+        if (uk && uk->is_number()) {
+            if (uk->num < 0 || uk->num >= (double)uni_pieces.size()) throw Unsupported("model: Unigram unk_id " + std::to_string((long long)uk->num) + " is beyond the vocab (UnkIdNotInVocabulary)");
+            m.has_unk = true;
+            m.unk_id = (uint32_t)uk->num;
+            m.unk_token = uni_pieces[m.unk_id];
+        }
+        m.byte_fallback = model->get_bool("byte_fallback", false);
+        for (int b = 0; b < 256; ++b) m.byte_id[b] = CHAR_NONE;
+        if (m.byte_fallback) {
+            // a run the vocabulary lacks becomes the <0xXX> tokens of its bytes only if ALL of them exist (unigram/model.rs:453-468: per
+            // run in the reference; every byte of valid UTF-8 but 0xC0, 0xC1, 0xF5.. can occur, so the flag asks for all 256 and a file
+            // that lacks one keeps its unk runs -- what the reference does for every run that holds such a byte; the others are refused)
+            int have = 0;
+            for (int b = 0; b < 256; ++b) {
+                char code[8];
+                snprintf(code, sizeof(code), "<0x%02X>", b);
+                auto it = v.find(code);
+                if (it != v.end()) { m.byte_id[b] = it->second; ++have; }
+            }
+            m.uni_bytes = have == 256;
+            if (have != 0 && have != 256)
+                throw Unsupported("model: Unigram byte_fallback with " + std::to_string(have) + " of the 256 <0xXX> pieces (all or none are on the path)");
+        }
+        if (v.count("")) throw Unsupported("model: Unigram vocab with an empty piece is outside the hot path");
+        // (the offsets of a byte-fallback run are put together from the result itself, kernels/unigram.hip k_unigram_run_offsets: no run may
+        // begin with the U+2581 that opens a pre-token, which holds when U+2581 is a piece and the unk piece does not begin with one)
+        if (m.uni_bytes && (!v.count(kMetaspace) || (m.has_unk && m.unk_token.compare(0, 3, kMetaspace) == 0)))
+            throw Unsupported("model: Unigram byte_fallback with a vocab that lacks the piece U+2581 (or whose unk piece begins with it) is outside the hot path");
     } else {
         throw Unsupported("model: type '" + mtype + "' is outside the hot path");
     }
-    if (m.pretok == PT_METASPACE) {
+    if (m.pretok == PT_METASPACE && m.model != MODEL_UNIGRAM) {
         if (m.model != MODEL_BPE || !m.char_bpe)
             throw Unsupported("pre_tokenizer: the U+2581 front (Metaspace, or null behind the U+2581 normalizers) is only on the path in front of BPE over characters");
         if (!m.bpe_prefix.empty() || !m.bpe_suffix.empty())
@@ -1453,8 +1616,9 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     }
 
     // ---- whole-word tables (BPE: ignore_merges + merge-stable shortcut; WordLevel: the model) ----
-    if (m.model == MODEL_BPE || m.model == MODEL_WORDLEVEL || m.model == MODEL_WORDPIECE) {
+    if (m.model == MODEL_BPE || m.model == MODEL_WORDLEVEL || m.model == MODEL_WORDPIECE || m.model == MODEL_UNIGRAM) {
         // (WordPiece: the longest candidate piece is the whole word, so a whole-word hit ends the match at once)
+        // (Unigram: a whole-word hit is final only where the Viterbi of that word alone yields [id] -- proved on the device at load)
         std::vector<WordSlot> words;
         m.long_off.push_back(0);
         for (size_t i = 0; i < m.raw_tokens.size(); ++i) {
@@ -1491,6 +1655,13 @@ HostModel HostModel::from_json(const char* json, size_t len) {
             else if (m.cont_prefix.empty())
                 cont.emplace_back(r, m.raw_ids[i]);
         }
+        build_trie(m, ini, cont);
+    }
+    if (m.model == MODEL_UNIGRAM) {
+        // the byte trie over all pieces (the reference's common_prefix_search, unigram/model.rs:285-288): the WordPiece table, word-initial root only
+        std::vector<std::pair<std::string, uint32_t>> ini, cont;
+        for (size_t i = 0; i < m.raw_tokens.size(); ++i)
+            if (!m.raw_tokens[i].empty()) ini.emplace_back(m.raw_tokens[i], m.raw_ids[i]);
         build_trie(m, ini, cont);
     }
 

@@ -156,7 +156,12 @@ struct HostModel {
     std::vector<uint32_t> long_id;      // [n_long]
     std::vector<uint32_t> long_table;   // open addressing: entry index+1, 0 = empty; size long_mask+1
     uint32_t long_mask = 0;
-    ByteTrie trie;                      // WordPiece
+    ByteTrie trie;                      // WordPiece; Unigram (every piece under root 0)
+    // Unigram (models/unigram/model.rs): f64 score per id as the file spells it, min_score - 10.0, and whether byte_fallback is on with
+    // all 256 <0xXX> pieces present (byte_id[] then holds their ids)
+    std::vector<double> uni_score;
+    double uni_unk_score = 0.0;
+    bool uni_bytes = false;
 
     // BertNormalizer per-code-point data (bert_norm_tables.inc): 2-stage flag table + cuckoo map (cp, kind) -> 3 x 21-bit cps
     std::vector<uint16_t> bn_stage1;

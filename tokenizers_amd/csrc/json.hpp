@@ -192,6 +192,11 @@ class JsonParser {
             v->kind = JsonValue::Number;
             v->num = strtod(t.c_str(), &e);
             if (e == t.c_str()) fail("bad number");
+            // the number as the file spells it, beside its strtod value.  ONE consumer reads it: the Unigram scores, which must be rounded the way
+            // the reference's own parser rounds them (host_model.cpp serde_json_f64).  Every other number of every file pays a small string for
+            // that (150 k of them for a 150 k-entry BPE vocabulary, freed with the tree when the load ends); the reader does not know which
+            // array it is in, and a second pass over the source text for the scores alone would be a second parser
+            v->str = t;
             p_ = q;
         } else {
             fail("unexpected character");

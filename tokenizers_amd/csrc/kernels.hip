@@ -12,6 +12,7 @@
 //        │                       table, then the perfect hash in HBM); misses queued by length class
 //        │──────bpe────────────► min-rank merge loop, one lane per queued pre-token (Word in LDS)  kernels/bpe.hip, bpe_huge.hip
 //        │──────word_models────► WordPiece trie walk of the queued words                          kernels/word_models.hip
+//        │──────unigram────────► Unigram Viterbi of the queued words (f64 scores, state in LDS)    kernels/unigram.hip
 //        │──────scan_emit──────► pt_start[P+1] only when offsets / word ids are requested          kernels/scan_emit.hip
 //        │──────output─────────► ids[T] (single-pass look-back compaction), per-document CSR,      kernels/output.hip, results.hip
 //        │                       offsets, word ids, specials
@@ -34,6 +35,7 @@
 #include "pretok_l3_core.hpp"
 #include "pretok_ds3_core.hpp"
 #include "pretok_local_core.hpp"
+#include "unigram_core.hpp"
 #include "tables.hpp"
 
 namespace tkamd {
@@ -90,6 +92,7 @@ static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)(
 #include "kernels/bpe.hip"
 #include "kernels/lookup.hip"
 #include "kernels/word_models.hip"
+#include "kernels/unigram.hip"
 #include "kernels/bpe_huge.hip"
 #include "kernels/output.hip"
 #include "kernels/epilogue.hip"

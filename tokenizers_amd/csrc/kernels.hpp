@@ -45,6 +45,12 @@ struct DevTables {
     const MergeSlot* trie;
     uint32_t trie_mask, trie_seed;
     uint32_t max_input_chars;
+    // Unigram (unigram_core.hpp): the trie above holds every piece; f64 score per id, min_score - 10.0, byte_fallback with all 256 <0xXX>
+    // pieces (their ids in byte_id), and -- only then -- a byte per id that says "a <0xXX> piece" (k_unigram_run_flags)
+    const double* uni_score;
+    double uni_unk_score;
+    const uint8_t* uni_is_byte;
+    uint32_t uni_bytes, uni_n_ids;
 };
 
 // BertNormalizer tables + options, passed by value
@@ -376,6 +382,12 @@ void launch_nfc_normalize(hipStream_t st, const NfcTables& nt, const uint8_t* te
 // the queue entry is retired (length 0) so that the model kernels skip it
 void launch_long_vocab3(hipStream_t st, int grid, const DevTables& t, const uint8_t* text, const QView& v1, const QView& v2, const QView& v3, void* rows, uint32_t miss_is_unk,
                         int* err, const WordCache& wc);
+// Unigram: the four queues in one launch (kernels/unigram.hip); state: 16 bytes per byte of the text + 1 for the words beyond 64 bytes
+void launch_unigram_all(hipStream_t st, int grid_short, int grid_long, const DevTables& t, const uint8_t* text, const QueuePlan& plan, void* rows, uint32_t* tmp_ids,
+                        uint32_t* tmp_end, int* err, void* state);
+// ... and, with offsets and byte_fallback, the tokens of a fallback run of several chars take the whole run's offsets (flags: a byte per token)
+void launch_unigram_run_offsets(hipStream_t st, int grid, const DevTables& t, const uint32_t* ids, uint32_t* offsets, const int64_t* tok_offsets, int64_t n_docs,
+                                const int64_t* n_tok, uint8_t* flags);
 void launch_wordpiece_all(hipStream_t st, int grid_short, int grid_long, const DevTables& t, const uint8_t* text, const QueuePlan& plan, void* rows, uint32_t* tmp_ids,
                           uint32_t* tmp_end, int* err);      // the <= 16-byte queue and the three longer ones in one launch
 // (rule: the member of the tiktoken family, tables.hpp SplitRule; ucc1 / ucc2: the case classes its case-split letter alternatives read, else null)

@@ -191,6 +191,16 @@ void launch_wordpiece_all(hipStream_t st, int grid_short, int grid_long, const D
     hipLaunchKernelGGL(k_wordpiece_all, dim3(3 * grid_long + grid_short), dim3(256), 0, st, t, text, plan.v[0], plan.v[1], plan.v[2], plan.v[3], (uint4*)rows, tmp_ids, tmp_end, err,
                        (uint32_t)(3 * grid_long));
 }
+void launch_unigram_all(hipStream_t st, int grid_short, int grid_long, const DevTables& t, const uint8_t* text, const QueuePlan& plan, void* rows, uint32_t* tmp_ids,
+                        uint32_t* tmp_end, int* err, void* state) {
+    hipLaunchKernelGGL(k_unigram_all, dim3(3 * grid_long + grid_short), dim3(256), 0, st, t, text, plan.v[0], plan.v[1], plan.v[2], plan.v[3], (uint4*)rows, tmp_ids, tmp_end, err,
+                       (uint4*)state, (uint32_t)(3 * grid_long));
+}
+void launch_unigram_run_offsets(hipStream_t st, int grid, const DevTables& t, const uint32_t* ids, uint32_t* offsets, const int64_t* tok_offsets, int64_t n_docs,
+                                const int64_t* n_tok, uint8_t* flags) {
+    hipLaunchKernelGGL(k_unigram_run_flags, dim3(grid), dim3(256), 0, st, ids, (const uint32_t*)offsets, n_tok, t.uni_is_byte, t.uni_n_ids, flags);
+    hipLaunchKernelGGL(k_unigram_run_offsets, dim3(grid), dim3(256), 0, st, offsets, tok_offsets, n_docs, n_tok, (const uint8_t*)flags);
+}
 void launch_pretok_llama3(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* docmask,
                           const uint16_t* uc1, const uint8_t* uc2, unsigned long long* startmask, unsigned long long* slowmask,
                           const int64_t* doc_off, int64_t n_docs, const int64_t* n_docs_dev, uint32_t* slow_docs, uint32_t* n_slow_docs,

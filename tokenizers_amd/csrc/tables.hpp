@@ -183,7 +183,7 @@ constexpr uint32_t DEC_BYTE = 0x20000000u;      // a <0xXX> token under the Byte
 constexpr uint32_t DEC_LEN_MASK = 0x1FFFFFFFu;
 
 // ---- tokenizer kinds -------------------------------------------------------------------------
-enum ModelKind { MODEL_NONE = 0, MODEL_BPE = 1, MODEL_WORDPIECE = 2, MODEL_WORDLEVEL = 3 };
+enum ModelKind { MODEL_NONE = 0, MODEL_BPE = 1, MODEL_WORDPIECE = 2, MODEL_WORDLEVEL = 3, MODEL_UNIGRAM = 4 };
 enum PretokKind {
     PT_NONE = 0,
     PT_BYTELEVEL_GPT2 = 1,   // ByteLevel(use_regex=true)                       byte_level.rs:119-148

@@ -553,13 +553,22 @@ class Tokenizer:
         return "".join(out)
 
     @staticmethod
+    def _model_vocab(d: dict) -> tuple[dict, int]:
+        """The model's piece -> id map and its size.  Unigram keeps an array of [piece, score] with id = index: of two equal pieces the
+        later id is the one a lookup by string finds (unigram/model.rs:125-126), and the size is the array's."""
+        v = d["model"]["vocab"]
+        if isinstance(v, list):
+            return {e[0]: i for i, e in enumerate(v)}, len(v)
+        return v, len(v)
+
+    @staticmethod
     def _effective_added(d: dict) -> list[dict]:
         """The added tokens with the ids the reference gives them at load: AddedVocabulary::add_tokens over the file's list in order
         (serialization.rs:153-167, added_vocabulary.rs:272-360) -- a content the model knows gets the model's id, any other the next
         free id from the model's vocabulary size on, a content listed twice keeps its first id and its last properties.  (The `id`
         fields of a file the library wrote say the same; the reference only warns when they do not.)"""
-        vocab = d["model"]["vocab"]
-        out, seen, next_id = [], {}, len(vocab)
+        vocab, n_vocab = Tokenizer._model_vocab(d)
+        out, seen, next_id = [], {}, n_vocab
         for a in d.get("added_tokens") or []:
             if not a.get("content"):
                 continue
@@ -579,7 +588,8 @@ class Tokenizer:
     def _id_to_token(self) -> dict[int, str]:
         if self._vocab_r is None:
             d = json.loads(self._json)
-            r = {int(i): t for t, i in d["model"]["vocab"].items()}
+            mv = d["model"]["vocab"]
+            r = {i: e[0] for i, e in enumerate(mv)} if isinstance(mv, list) else {int(i): t for t, i in mv.items()}
             for a in self._effective_added(d):
                 # the token string of an added-token match is the matched slice of the NORMALIZED text (added_vocabulary.rs:497-516), i.e.
                 # the token's normalized pattern when it is matched through the normalizer
@@ -684,9 +694,8 @@ class Tokenizer:
     def _add(self, tokens, special: bool) -> int:
         d = json.loads(self._json)
         added = self._effective_added(d)
-        model_vocab = d["model"]["vocab"]
+        model_vocab, n_model = self._model_vocab(d)
         by_content = {a["content"]: a for a in added}
-        n_model = len(model_vocab)
         max_added = max((int(a["id"]) for a in added), default=None)
         next_id = n_model if max_added is None else (max_added + 1 if (max_added >= n_model or n_model == 0) else n_model)
         n_new = 0
@@ -724,13 +733,15 @@ class Tokenizer:
         return self._add(list(tokens), special=True)
 
     def get_vocab_size(self, with_added_tokens: bool = True) -> int:
+        if with_added_tokens and self.info["model"] == 4:      # Unigram: the size of get_vocab (tokenizer/mod.rs:702-709), where a piece listed twice counts once
+            return len(self.get_vocab(True))
         return len(self._id_to_token()) if with_added_tokens else self.info["vocab_size"]
 
     # ---- vocabulary lookups (TokenizerImpl::get_vocab / token_to_id / id_to_token, tokenizer/mod.rs:683-735: the added vocabulary
     # answers first); host-side, from the tokenizer.json the handle was built from ----
     def get_vocab(self, with_added_tokens: bool = True) -> dict[str, int]:
         d = json.loads(self._json)
-        v = dict(d["model"]["vocab"])
+        v = dict(self._model_vocab(d)[0])
         if with_added_tokens:
             for a in self._effective_added(d):
                 v[a["content"]] = int(a["id"])
