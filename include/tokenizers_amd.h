@@ -329,6 +329,11 @@ int tkamd_probe_truncation(uint64_t n_tokens, uint32_t max_len, uint32_t stride,
  * move (they survive the Mn filter with a non-zero combining class): whether it does depends on their neighbours, see
  * tkamd_probe_bert_alone. */
 int tkamd_probe_bert_norm(const tkamd_tokenizer* tok, uint32_t cp, uint32_t* out, int32_t* n, int32_t* refused);
+/* The Precompiled normalizer (normalizers/precompiled.rs) of ONE piece -- text[0 .. n): a document, or what lies between two added-token
+ * matches -- by the host run of the very core the kernels run (csrc/precompiled_core.hpp): out[0 .. *n_out) the normalized bytes,
+ * src[k] the first byte of the source char that byte k is aligned to (the chars the reference loses at a piece's start included).
+ * cap: what out and src hold; *n_out is set even when it is too small (TKAMD_ERR_INVALID then). */
+int tkamd_probe_precompiled(const tkamd_tokenizer* tok, const uint8_t* text, int64_t n, uint8_t* out, uint32_t* src, int64_t cap, int64_t* n_out);
 /* BertNormalizer strip_accents on the character whose lead byte is text[pos] (text[0 .. n) = one piece handed to the normalizer: a
  * document, or what lies between two added-token matches): *reorder = 1 if it survives the Mn filter with a non-zero combining
  * class (NFD's canonical ordering could move it), *alone = 1 if it is alone in its run of non-starters -- nothing moves; 0: the

@@ -19,6 +19,7 @@ struct Workspace {
     hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
     // (sized by the largest batch seen)
     DevBuf w_l3_tiles;                          // a bit per 2048 bytes: tiles the Llama-3 family's lane kernel left bytes undecided in (zeroed with the batch's scratch)
+    DevBuf w_ptext, w_pnorig, w_pdoc_off, w_pc_ltot;       // behind a Precompiled normalizer: its text, the original byte of every byte of it, the documents in it; the count pass's lane totals
     DevBuf w_ms_dmask, w_pprefix, w_pt_word;               // the "▁" front: the raw text's document starts; piece starts in front of every X word, piece rank of every pre-token
     DevBuf w_docmask, w_startmask, w_wprefix, w_bsum, w_tile_w, w_pt_start, w_tok0, w_pt_tokoff, w_tmp_ids, w_tmp_end, w_rows;
     DevBuf w_len1, w_fin, w_fbsum, w_pad_count, w_keep, w_type_ids2, w_seq_ids2;   // truncation / padding / pair epilogue
@@ -93,7 +94,7 @@ struct tkamd_tokenizer {
     DevBuf t_at_id[2], t_at_flags[2], t_at_blob[2], t_at_off[2], t_at_first[2];   // AddedVocabulary patterns of the two matching passes
     DevBuf t_pp_single, t_pp_single_plain;      // the single layout as pieces (the single inputs of a mixed batch)
     DevBuf t_pp_pair, t_pp_pair_plain;   // pair template of the post-processor with / without its special tokens: [pieces][3]
-    DevBuf t_pp_prefix, t_pp_suffix, t_pp_prefix_ty, t_pp_suffix_ty, t_bn1, t_bn2, t_bn_map, t_nfc1, t_nfc2, t_nfc_map, t_merge_disp, t_dec_entry, t_dec_blob, t_trie, t_uni_score, t_uni_is_byte;
+    DevBuf t_pp_prefix, t_pp_suffix, t_pp_prefix_ty, t_pp_suffix_ty, t_bn1, t_bn2, t_bn_map, t_nfc1, t_nfc2, t_nfc_map, t_pc_units, t_pc_rep, t_gc1, t_gc2, t_merge_disp, t_dec_entry, t_dec_blob, t_trie, t_uni_score, t_uni_is_byte;
     int n_cu = 256;
     int n_direct = 0;
     int n_hot = 0;

@@ -88,6 +88,9 @@ struct Batch {
     // check_request
     bool mixed = false, want_words = false, want_meta = false, add_special = false, prefix_space = false, metaspace = false, words_in = false, pairs = false;
     bool typed_single = false, has_epilogue = false, want_overflow = false;
+    bool precomp = false;          // behind a Precompiled normalizer: the "▁" front reads its output (normalize_precompiled)
+    int64_t n_p = 0;               // ... the host's bound of that text
+    const uint8_t* p_text = nullptr; const int64_t *p_doc_off = nullptr, *d_plen = nullptr; const uint32_t* p_norig = nullptr;
     bool nfc_general = false;      // behind an NFC normalizer: this run normalizes (else X is the text as it came, behind k_nfc_check)
     uint32_t off_mode = 0, mcap = 0;
     int64_t n_x = 0, e_n = 0, W0 = 0, W = 0;      // e_n: encodings the epilogues see; W0 / W: mask words over the original / the X text
@@ -121,7 +124,7 @@ struct Batch {
     AddedArgs args_of(int c);
     void scatter_masks(int64_t n_text, const int64_t* len_dev, bool with_end);
     const int64_t* build_pieces(const int64_t* doc_csr, int64_t n_text, const int64_t* len_dev);
-    void normalize_bert(); void normalize_nfc(); void shift_behind_prefix_spaces(); void metaspace_front(); void read_ntext();
+    void normalize_bert(); void normalize_nfc(); void normalize_precompiled(); void shift_behind_prefix_spaces(); void metaspace_front(); void read_ntext();
     // helpers of run_model / compact_and_meta
     void* phases_of(int which);
     void open_word_cache();
@@ -171,8 +174,13 @@ void Batch::check_request() {
             nfc_general = p > 0;
         }
     }
+    // (Precompiled: a source byte stands for at most pc_growth output bytes, found at load; the "▁" front then reads that text)
+    precomp = hm.norm == NORM_PRECOMPILED;
+    n_p = precomp ? (int64_t)hm.pc_growth * n_bytes + 64 : n_bytes;
+    // (behind the normalizer only: every other tokenizer's text is bounded by the check of n_x below, as before)
+    if (precomp && n_p >= (int64_t)0x55555500ll) throw Invalid("batch larger than 4 GiB behind the normalizer's bound: split it (byte offsets are 32-bit on the device)");
     n_x = (hm.norm == NORM_BERT || nfc_general) ? 3 * n_bytes + 64
-          : metaspace ? 3 * n_bytes + 3 * (n_docs + 2 * (int64_t)mcap + 1) + 64
+          : metaspace ? 3 * n_p + 3 * (n_docs + 2 * (int64_t)mcap + 1) + 64
           : n_bytes + (prefix_space ? n_docs + (int64_t)mcap : 0);
     if (n_x >= (int64_t)0xFFFFFF00ll) throw Invalid("batch larger than 4 GiB: split it (byte offsets are 32-bit on the device)");
     const bool bpe_path = hm.model == MODEL_BPE && !hm.char_bpe && (hm.pretok == PT_BYTELEVEL_GPT2 || hm.pretok == PT_LLAMA3 || hm.pretok == PT_SPLIT_CHAIN || hm.pretok == PT_BYTELEVEL_NOREGEX);
@@ -407,6 +415,44 @@ void Batch::normalize_nfc() {
     read_ntext();
 }
 
+void Batch::normalize_precompiled() {
+    // ---- Precompiled: text -> normalized text + the source char of every normalized byte (kernels/precompiled.hip); the pieces are the
+    // documents and what lies between the matches of pass 1, which are copied verbatim.  The "▁" front reads the result. ----
+    const int64_t Wp = (n_p >> 6) + 1;
+    w->w_ptext.reserve((size_t)n_p + TKAMD_TEXT_PAD);
+    w->w_pdoc_off.reserve((size_t)(n_docs + 2) * 8);
+    w->w_pc_ltot.reserve((((size_t)n_bytes >> 4) + 8) * 2);
+    w->w_keepmask.reserve(bn_olen_bytes(n_p));              // (sized for the front's pass over the normalized text too: the buffers do not move between the two)
+    w->w_kprefix.reserve((size_t)(Wp + 1) * 4);
+    w->w_wbase.reserve((size_t)(Wp + 1) * 4);
+    w->w_ms_dmask.reserve((size_t)(Wp + 2) * 8);
+    if (off_mode != TKAMD_OFFSETS_NONE) w->w_pnorig.reserve(((size_t)n_p + 4) * 4);
+    HIP_CHECK(hipMemsetAsync(w->w_ms_dmask.p, 0, (size_t)(W0 + 2) * 8, st));
+    launch_mark_doc_starts_n(st, d_doc_off, n_docs, n_bytes, nullptr, w->w_ms_dmask.as<ull>(), d_err);
+    const ull* verbatim = nullptr;
+    if (have_raw) {
+        scatter_masks(n_bytes, nullptr, false);
+        launch_mask_or2(st, w->w_boundmask.as<ull>(), w->w_matchmask.as<ull>(), w->w_spanmask.as<ull>(), W0 + 1);
+        verbatim = w->w_boundmask.as<ull>();
+        launch_nfc_bound(st, w->w_ms_dmask.as<ull>(), verbatim, W0 + 1);
+    }
+    const PcTables pt{t->t_pc_units.as<uint32_t>(), (uint32_t)hm.pc_units.size(), t->t_pc_rep.as<uint8_t>(), (uint32_t)hm.pc_rep.size(), t->t_gc1.as<uint16_t>(), t->t_gc2.as<uint8_t>(),
+                      {hm.pc_first[0], hm.pc_first[1], hm.pc_first[2], hm.pc_first[3]}};
+    int64_t* plen = sc + SC_PLEN;
+    uint32_t* pnorig = off_mode != TKAMD_OFFSETS_NONE ? w->w_pnorig.as<uint32_t>() : nullptr;
+    pf.begin("precompiled_normalize");
+    launch_precompiled(st, pt, d_text, n_bytes, d_doc_off, n_docs, verbatim, w->w_ms_dmask.as<ull>(), w->w_keepmask.as<uint8_t>(), w->w_pc_ltot.as<uint16_t>(),
+                       w->w_kprefix.as<uint32_t>(), w->w_bsum.as<uint32_t>(), w->w_wbase.as<uint32_t>(), plen, w->w_ptext.as<uint8_t>(), pnorig, w->w_pdoc_off.as<int64_t>(), d_err,
+                       t->n_cu * 4, n_p);
+    launch_zero_tail(st, w->w_ptext.as<uint8_t>(), plen, TKAMD_TEXT_PAD);
+    pf.end();
+    if (have_raw) launch_pc_translate_matches(st, mlist, n_match, w->w_keepmask.as<uint8_t>(), w->w_pc_ltot.as<uint16_t>(), w->w_wbase.as<uint32_t>(), n_bytes, plen);
+    p_text = w->w_ptext.as<uint8_t>();
+    p_doc_off = w->w_pdoc_off.as<int64_t>();
+    d_plen = plen;
+    p_norig = pnorig;
+}
+
 void Batch::shift_behind_prefix_spaces() {
     // ---- ByteLevel add_prefix_space: every piece shifted behind its virtual leading space (byte_level.rs:120-125) ----
     const int64_t* seg = d_doc_off;
@@ -441,27 +487,32 @@ void Batch::shift_behind_prefix_spaces() {
 }
 
 void Batch::metaspace_front() {
-    // ---- the "▁" front: the raw text's pieces (documents, and what lies between added-token matches) -> the "▁" text X + the original
-    // byte of every X byte; the matches are copied as they are and move into X coordinates like the normaliser's (kernels/metaspace.hip) ----
-    w->w_ms_dmask.reserve((size_t)(W0 + 2) * 8);
-    HIP_CHECK(hipMemsetAsync(w->w_ms_dmask.p, 0, (size_t)(W0 + 2) * 8, st));
-    launch_mark_doc_starts_n(st, d_doc_off, n_docs, n_bytes, nullptr, w->w_ms_dmask.as<ull>(), d_err);
+    // ---- the "▁" front: the pieces (documents, and what lies between added-token matches) of the raw text -- behind a Precompiled normalizer:
+    // of its output, whose length only the device knows -- -> the "▁" text X + the original byte of every X byte; the matches are copied as
+    // they are and move into X coordinates like the normaliser's (kernels/metaspace.hip) ----
+    const uint8_t* in_text = precomp ? p_text : d_text;
+    const int64_t n_i = precomp ? n_p : n_bytes, Wi = (n_i >> 6) + 1;
+    const int64_t* in_len = precomp ? d_plen : nullptr;
+    const int64_t* in_doc = precomp ? p_doc_off : d_doc_off;
+    w->w_ms_dmask.reserve((size_t)(Wi + 2) * 8);
+    HIP_CHECK(hipMemsetAsync(w->w_ms_dmask.p, 0, (size_t)(Wi + 2) * 8, st));
+    launch_mark_doc_starts_n(st, in_doc, n_docs, n_i, in_len, w->w_ms_dmask.as<ull>(), d_err);
     const ull* pstart = w->w_ms_dmask.as<ull>();
     if (have_added) {
-        scatter_masks(n_bytes, nullptr, false);
-        build_pieces(d_doc_off, n_bytes, nullptr);
+        scatter_masks(n_i, in_len, false);
+        build_pieces(in_doc, n_i, in_len);
         pstart = w->w_boundmask.as<ull>();
     }
-    w->w_keepmask.reserve(bn_olen_bytes(n_bytes));          // output bytes per source byte (kernels.hpp bn_olen_bytes)
-    w->w_kprefix.reserve((size_t)(W0 + 1) * 4);
-    w->w_wbase.reserve((size_t)(W0 + 1) * 4);
+    w->w_keepmask.reserve(bn_olen_bytes(n_i));          // output bytes per source byte (kernels.hpp bn_olen_bytes)
+    w->w_kprefix.reserve((size_t)(Wi + 1) * 4);
+    w->w_wbase.reserve((size_t)(Wi + 1) * 4);
     pf.begin("metaspace");
-    launch_metaspace(st, d_text, n_bytes, d_doc_off, n_docs, pstart, w->w_ms_dmask.as<ull>(), have_added ? w->w_matchmask.as<ull>() : nullptr,
+    launch_metaspace(st, in_text, n_i, in_doc, n_docs, pstart, w->w_ms_dmask.as<ull>(), have_added ? w->w_matchmask.as<ull>() : nullptr,
                      have_added ? w->w_spanmask.as<ull>() : nullptr, (uint32_t)hm.ms_prepend, w->w_keepmask.as<uint8_t>(), w->w_kprefix.as<uint32_t>(),
-                     w->w_bsum.as<uint32_t>(), w->w_wbase.as<uint32_t>(), d_xlen, w->w_ntext.as<uint8_t>(), (uint32_t*)norig, w->w_ndoc_off.as<int64_t>());
+                     w->w_bsum.as<uint32_t>(), w->w_wbase.as<uint32_t>(), d_xlen, w->w_ntext.as<uint8_t>(), (uint32_t*)norig, w->w_ndoc_off.as<int64_t>(), in_len, p_norig);
     launch_zero_tail(st, w->w_ntext.as<uint8_t>(), d_xlen, TKAMD_TEXT_PAD, w->w_docmask.as<ull>(), W + 1, t->n_cu * 4);
     pf.end();
-    if (have_added) launch_translate_matches_norm(st, mlist, n_match, w->w_keepmask.as<uint8_t>(), w->w_wbase.as<uint32_t>(), n_bytes, d_xlen);
+    if (have_added) launch_translate_matches_norm(st, mlist, n_match, w->w_keepmask.as<uint8_t>(), w->w_wbase.as<uint32_t>(), n_i, d_xlen);
     read_ntext();
     if (have_added) {
         scatter_masks(n_x, x_len_dev, off_mode != TKAMD_OFFSETS_NONE);
@@ -560,6 +611,7 @@ void Batch::build_x_text() {
             pf.end();
         }
     }
+    if (precomp) normalize_precompiled();
     n_in = normalized ? n_x : n_bytes;
     if (spec && setB.size() > 0) {
         pf.begin("added_token_match2");

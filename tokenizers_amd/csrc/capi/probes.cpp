@@ -92,6 +92,20 @@ int tkamd_probe_bert_norm(const tkamd_tokenizer* t, uint32_t cp, uint32_t* out, 
     return TKAMD_OK;
 }
 
+// The Precompiled normalizer of one piece, by the host run of the core the kernels run (precompiled_core.hpp): out[0 .. *n_out) the
+// normalized bytes, src[k] the first byte of the source char byte k is aligned to.  *n_out is set even when cap is too small (TKAMD_ERR_INVALID).
+int tkamd_probe_precompiled(const tkamd_tokenizer* t, const uint8_t* text, int64_t n, uint8_t* out, uint32_t* src, int64_t cap, int64_t* n_out) {
+    if (!t || (!text && n) || n < 0 || !n_out || cap < 0 || (cap && (!out || !src))) return set_error(TKAMD_ERR_INVALID, "bad argument");
+    const HostModel& hm = t->hm;
+    if (hm.norm != NORM_PRECOMPILED) return set_error(TKAMD_ERR_UNSUPPORTED, "the tokenizer has no Precompiled normalizer");
+    std::vector<uint32_t> al;
+    const std::string o = hm.precompiled_normalize(std::string((const char*)text, (size_t)n), &al);
+    *n_out = (int64_t)o.size();
+    if ((int64_t)o.size() > cap) return set_error(TKAMD_ERR_INVALID, "the output buffer is too small");
+    if (!o.empty()) { memcpy(out, o.data(), o.size()); memcpy(src, al.data(), al.size() * 4); }
+    return TKAMD_OK;
+}
+
 int tkamd_probe_bert_alone(const tkamd_tokenizer* t, const uint8_t* text, int64_t n, int64_t pos, int32_t* reorder, int32_t* alone) {
     if (!t || !text || !reorder || !alone || n < 0 || pos < 0 || pos >= n) return set_error(TKAMD_ERR_INVALID, "bad argument");
     const HostModel& hm = t->hm;

@@ -3,7 +3,7 @@
 namespace {
 
 // scalars block layout (int64 slots)
-enum { SC_NPRETOK = 0, SC_NTOK = 1, SC_ERR = 2 /* int */, SC_NKEPT = 3, SC_PADMAX = 4 /* uint32 */, SC_NSEG = 5, SC_NENC = 6, SC_NCHARS = 8, SC_HUGE_USED = 9, SC_NTOK2 = 10, SC_NPIECE = 11,
+enum { SC_NPRETOK = 0, SC_NTOK = 1, SC_ERR = 2 /* int */, SC_NKEPT = 3, SC_PADMAX = 4 /* uint32 */, SC_NSEG = 5, SC_NENC = 6, SC_NCHARS = 8, SC_HUGE_USED = 9, SC_NTOK2 = 10, SC_NPIECE = 11, SC_PLEN = 12,
        SC_COUNTERS = 16 /* uint32[CNT_COUNT] */, SC_SLOTS = 32 };
 
 struct Prof {
@@ -94,6 +94,12 @@ void upload_tables(tkamd_tokenizer* t) {
     upload(t->t_nfc1, hm.nfc_stage1);
     upload(t->t_nfc2, hm.nfc_stage2);
     upload(t->t_nfc_map, hm.nfc_map);
+    if (hm.norm == NORM_PRECOMPILED) {
+        upload(t->t_pc_units, hm.pc_units);
+        upload(t->t_pc_rep, hm.pc_rep);
+        upload(t->t_gc1, hm.gc_stage1);
+        upload(t->t_gc2, hm.gc_stage2);
+    }
     for (int c = 0; c < 2; ++c) {
         upload(t->t_at_blob[c], hm.at[c].blob);
         upload(t->t_at_off[c], hm.at[c].off);

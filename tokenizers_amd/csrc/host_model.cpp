@@ -2,6 +2,7 @@
 #include "host_model.hpp"
 #include "bert_norm_core.hpp"
 #include "nfc_core.hpp"
+#include "precompiled_core.hpp"
 
 #include <algorithm>
 #include <cctype>
@@ -89,6 +90,10 @@ const UcRun kUcCaseRuns[] = {      // (flags: UCC_UPPER / UCC_LOWER, tables.hpp)
 };
 const UcRun kUcPsmRuns[] = {       // (flags: UC2_P / UC2_S / UC2_M / UC2_CJK, tables.hpp)
 #include "unicode_psm_ranges.inc"
+};
+
+const UcRun kGcRuns[] = {          // (flags: GC_* of precompiled_core.hpp)
+#include "grapheme_tables.inc"
 };
 
 struct BnMapRow {
@@ -711,6 +716,28 @@ double serde_json_f64(const std::string& t) {
     return positive ? f : -f;
 }
 
+bool base64_decode(const std::string& in, std::string* out) {
+    uint32_t acc = 0;
+    int bits = 0;
+    size_t pad = 0;
+    for (char ch : in) {
+        int v;
+        if (ch >= 'A' && ch <= 'Z') v = ch - 'A';
+        else if (ch >= 'a' && ch <= 'z') v = ch - 'a' + 26;
+        else if (ch >= '0' && ch <= '9') v = ch - '0' + 52;
+        else if (ch == '+' || ch == '-') v = 62;
+        else if (ch == '/' || ch == '_') v = 63;
+        else if (ch == '=') { ++pad; continue; }
+        else if (ch == '\n' || ch == '\r') continue;
+        else return false;
+        if (pad) return false;
+        acc = (acc << 6) | (uint32_t)v;
+        bits += 6;
+        if (bits >= 8) { bits -= 8; out->push_back((char)((acc >> bits) & 0xFFu)); }
+    }
+    return pad <= 2;
+}
+
 PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
     if (!pt || pt->is_null()) {
         // the "▁" normalizers leave every piece ONE pre-token (the device cuts it into units: the model check below proves that exact)
@@ -724,7 +751,9 @@ PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
                           "' are outside the hot path (only with a null pre_tokenizer)");
     if (type == "Metaspace") {
         // pre_tokenizers/metaspace.rs:34-77 (deserialisation: split defaults to true, the legacy add_prefix_space = false means "never")
-        if (m.norm != NORM_NONE) throw Unsupported("pre_tokenizer: Metaspace behind a normalizer");
+        if (m.norm != NORM_NONE && m.norm != NORM_PRECOMPILED) throw Unsupported("pre_tokenizer: Metaspace behind a normalizer");
+        // (behind bare Metaspace a run of spaces is a run of U+2581: the Replace(Regex " {2,}") member is not inert there)
+        if (m.pc_space_runs) throw Unsupported("normalizer: Replace(Regex ' {2,}' -> ' ') behind Precompiled is only on the path in front of Sequence[WhitespaceSplit, Metaspace]");
         const std::string rep = pt->get_str("replacement");
         if (rep != kMetaspace) throw Unsupported("pre_tokenizer: Metaspace with replacement '" + rep + "' (only U+2581 is on the path)");
         const JsonValue* ps = pt->get("prepend_scheme");
@@ -773,6 +802,23 @@ PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
                 m.split_rule = rule;
                 return PT_LLAMA3;
             }
+        }
+        if (seq && seq->is_array() && seq->arr.size() == 2 && seq->arr[0] && seq->arr[1] && seq->arr[0]->get_str("type") == "WhitespaceSplit" &&
+            seq->arr[1]->get_str("type") == "Metaspace") {
+            // Sequence[WhitespaceSplit, Metaspace] (XLM-R, T5, mBART): the words between char::is_whitespace chars, each with its "▁".  On the
+            // path behind Precompiled alone: the front then reads the normalizer's text, where the word rule runs (kernels/metaspace.hip MS_WORD)
+            if (m.norm != NORM_PRECOMPILED)
+                throw Unsupported("pre_tokenizer: Sequence[WhitespaceSplit, Metaspace] is only on the path behind a Precompiled normalizer");
+            const JsonValue* b = seq->arr[1].get();
+            const std::string rep = b->get_str("replacement");
+            if (rep != kMetaspace) throw Unsupported("pre_tokenizer: Metaspace with replacement '" + rep + "' (only U+2581 is on the path)");
+            const JsonValue* ps = b->get("prepend_scheme");
+            const std::string scheme = (ps && ps->is_string()) ? ps->str : (b->get_bool("add_prefix_space", true) ? "always" : "never");
+            if (scheme != "always")
+                throw Unsupported("pre_tokenizer: Sequence[WhitespaceSplit, Metaspace] with prepend_scheme '" + scheme + "' (only 'always' is on the path)");
+            m.ms_prepend = MS_WORD;
+            m.ms_split = b->get_bool("split", true);
+            return PT_METASPACE;
         }
         if (seq && seq->is_array() && parse_split_chain(seq, m)) return PT_SPLIT_CHAIN;
         throw Unsupported("pre_tokenizer: this Sequence is outside the hot path");
@@ -1102,6 +1148,31 @@ HostModel HostModel::from_json(const char* json, size_t len) {
             m.bn_strip_accents = (sa && sa->is_bool()) ? sa->b : m.bn_lowercase;  // normalizers/bert.rs:124
         } else if (t == "NFC") {
             m.norm = NORM_NFC;
+        } else if (t == "Precompiled" || (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() && !norm->get("normalizers")->arr.empty() &&
+                                          norm->get("normalizers")->arr[0] && norm->get("normalizers")->arr[0]->is_object() &&
+                                          norm->get("normalizers")->arr[0]->get_str("type") == "Precompiled")) {
+            // Precompiled, alone or first in a Sequence whose only other member may be the Replace(Regex " {2,}" -> " ") of XLM-R / T5 files: behind
+            // WhitespaceSplit that member is inert (it touches runs of spaces alone, which the split drops), so no kernel runs for it -- the
+            // pre-tokenizer below refuses it in front of anything else
+            const JsonValue* pc = norm;
+            if (t == "Sequence") {
+                const auto& arr = norm->get("normalizers")->arr;
+                pc = arr[0].get();
+                for (size_t k = 1; k < arr.size(); ++k) {
+                    const JsonValue* r = arr[k].get();
+                    const std::string rt = (r && r->is_object()) ? r->get_str("type") : "?";
+                    const JsonValue* pat = rt == "Replace" ? r->get("pattern") : nullptr;
+                    if (k != 1 || arr.size() != 2 || !pat || !pat->is_object() || !pat->get("Regex") || pat->get_str("Regex") != " {2,}" || r->get_str("content") != " ")
+                        throw Unsupported("normalizer: '" + rt + "' behind Precompiled in a Sequence is outside the hot path (only Replace(Regex ' {2,}' -> ' ') is on it)");
+                    m.pc_space_runs = true;
+                }
+            }
+            const JsonValue* cm = pc->get("precompiled_charsmap");
+            if (!cm || !cm->is_string()) throw Unsupported("normalizer: Precompiled without a precompiled_charsmap string");
+            std::string blob;
+            if (!base64_decode(cm->str, &blob)) throw Unsupported("normalizer: Precompiled precompiled_charsmap is not base64");
+            m.set_precompiled(blob);
+            m.norm = NORM_PRECOMPILED;
         } else if (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() && norm->get("normalizers")->arr.empty()) {
             // Sequence[] applies nothing (normalizers/utils.rs: a loop over no normalizer): DeepSeek-V3 files carry it
         } else if (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() &&
@@ -1540,7 +1611,7 @@ HostModel HostModel::from_json(const char* json, size_t len) {
             const std::string ptype = (pt && pt->is_object()) ? pt->get_str("type") : "null";
             throw Unsupported("model: Unigram (a vocab of scored pieces) is on the path behind Metaspace(split = true) only; pre_tokenizer '" + ptype + "' is not");
         }
-        if (m.norm != NORM_NONE || !m.ms_split)
+        if ((m.norm != NORM_NONE && m.norm != NORM_PRECOMPILED) || !m.ms_split)
             throw Unsupported("model: Unigram (a vocab of scored pieces) over whole pieces -- Metaspace(split = false), or a null pre_tokenizer behind the U+2581 "
                               "normalizers -- is outside the hot path: the front cuts such a piece into units, and the reference compares f64 sums of "
                               "prefix + score over the whole piece, which a unit alone can round differently (only Metaspace(split = true) is on the path)");
@@ -1594,6 +1665,11 @@ HostModel HostModel::from_json(const char* json, size_t len) {
                           "in front of BPE over characters, WordPiece, WordLevel or the U+2581 front it is not");
     // (the same refusal every encode call makes for any normalizer, made at load for this one: the file can never encode)
     if (m.norm == NORM_NFC && m.byte_level && m.add_prefix_space) throw Unsupported("ByteLevel add_prefix_space behind a normalizer (NFC)");
+    if (m.norm == NORM_PRECOMPILED) {
+        if (m.model != MODEL_UNIGRAM) throw Unsupported("normalizer: Precompiled is only on the path in front of a Unigram model");
+        for (const AddedToken& a : m.added_tokens)
+            if (a.normalized) throw Unsupported("added token '" + a.content + "' is normalized = true behind the Precompiled normalizer (matched on the normalized text: not on the path)");
+    }
     if (m.norm == NORM_METASPACE)
         for (const AddedToken& a : m.added_tokens)
             if (a.normalized) throw Unsupported("added token '" + a.content + "' is normalized = true behind the U+2581 normalizer (matched on the normalized text: not on the path)");
@@ -1760,6 +1836,108 @@ int HostModel::bn_expand_cp(uint32_t cp, uint32_t* out, int* refused) const {
 }
 
 void HostModel::build_nfc() { build_nfc_tables(*this); }
+
+// The charsmap of a Precompiled normalizer (precompiled_core.hpp for the layout).  Everything the device will ever index is checked here:
+// the sizes, the replacement strings (UTF-8, NUL-terminated), and every unit a key's walk can reach from the root -- its next position,
+// its value's position and the value itself -- so a blob the reference would panic on is refused, not probed.
+void HostModel::set_precompiled(const std::string& blob) {
+    const char* const bad = "normalizer: Precompiled precompiled_charsmap is malformed: ";
+    if (blob.empty()) throw Unsupported("normalizer: Precompiled with an empty precompiled_charsmap");
+    if (blob.size() < 8) throw Unsupported(std::string(bad) + "shorter than its header and one unit");
+    auto le32 = [&](size_t at) { return (uint32_t)(uint8_t)blob[at] | ((uint32_t)(uint8_t)blob[at + 1] << 8) | ((uint32_t)(uint8_t)blob[at + 2] << 16) | ((uint32_t)(uint8_t)blob[at + 3] << 24); };
+    const uint32_t trie_bytes = le32(0);
+    if (trie_bytes < 4u || (trie_bytes & 3u) || (size_t)trie_bytes > blob.size() - 4) throw Unsupported(std::string(bad) + "trie size " + std::to_string(trie_bytes) + " of a blob of " + std::to_string(blob.size()) + " bytes");
+    const uint32_t n = trie_bytes / 4u;
+    pc_units.resize(n);
+    for (uint32_t k = 0; k < n; ++k) pc_units[k] = le32(4 + 4 * (size_t)k);
+    pc_rep.assign(blob.begin() + 4 + trie_bytes, blob.end());
+    if (pc_rep.empty() || pc_rep.back() != 0u) pc_rep.push_back(0u);        // (the crate reads a replacement up to a NUL or the blob's end)
+    for (size_t i = 0; i < pc_rep.size();) {                                 // the crate holds them as one str: UTF-8
+        const uint32_t b0 = pc_rep[i];
+        const uint32_t l = b0 < 0x80u ? 1u : (b0 >= 0xC2u && b0 < 0xE0u) ? 2u : (b0 >= 0xE0u && b0 < 0xF0u) ? 3u : (b0 >= 0xF0u && b0 < 0xF5u) ? 4u : 0u;
+        bool ok = l != 0u && i + l <= pc_rep.size();
+        for (uint32_t k = 1; ok && k < l; ++k) ok = (pc_rep[i + k] & 0xC0u) == 0x80u;
+        if (ok && l == 3u) ok = !(b0 == 0xE0u && pc_rep[i + 1] < 0xA0u) && !(b0 == 0xEDu && pc_rep[i + 1] >= 0xA0u);
+        if (ok && l == 4u) ok = !(b0 == 0xF0u && pc_rep[i + 1] < 0x90u) && !(b0 == 0xF4u && pc_rep[i + 1] >= 0x90u);
+        if (!ok) throw Unsupported(std::string(bad) + "the replacement strings are not UTF-8 (byte " + std::to_string(i) + ")");
+        i += l;
+    }
+    auto offset_of = [](uint32_t u) { return (u >> 10) << ((u & 0x200u) >> 6); };
+    for (int q = 0; q < 4; ++q) pc_first[q] = 0ull;
+    pc_growth = 1;
+    struct Node { uint32_t pos, depth; };
+    std::vector<Node> stack;
+    std::vector<uint8_t> seen(n, 0);
+    const uint32_t root = offset_of(pc_units[0]);
+    if (root >= n) throw Unsupported(std::string(bad) + "the root points outside the array");
+    stack.push_back({root, 0u});
+    seen[root] = 1;
+    // (darts-clone builds from a DAWG: two units may lead to one node.  The walk is breadth first, so a node is first reached -- and its
+    // leaves' growth taken -- at the SMALLEST depth any key reaches it at: the bound holds whichever path a text takes)
+    for (size_t head = 0; head < stack.size(); ++head) {
+        const Node nd = stack[head];
+        for (uint32_t c = 1; c < 256u; ++c) {
+            const uint32_t p = nd.pos ^ c;
+            if (p >= n) continue;                                            // (the device reads no unit there: no match)
+            const uint32_t u = pc_units[p];
+            if ((u & 0x800000FFu) != c) continue;
+            const uint32_t next = p ^ offset_of(u);
+            if (next >= n) throw Unsupported(std::string(bad) + "unit " + std::to_string(p) + " points outside the array");
+            if (nd.depth == 0u) pc_first[c >> 6] |= 1ull << (c & 63u);
+            if ((u >> 8) & 1u) {
+                const uint32_t v = pc_units[next] & 0x7FFFFFFFu;
+                if (v >= pc_rep.size()) throw Unsupported(std::string(bad) + "the value of unit " + std::to_string(next) + " lies outside the replacement strings");
+                uint32_t e = v;
+                while (pc_rep[e] != 0u) ++e;
+                if (e - v > PC_REP_MAX) throw Unsupported("normalizer: Precompiled with a replacement of " + std::to_string(e - v) + " bytes (at most " + std::to_string(PC_REP_MAX) + " are on the path)");
+                pc_growth = std::max(pc_growth, (e - v + nd.depth) / (nd.depth + 1u));
+            }
+            if (!seen[next] && nd.depth < 64u) { seen[next] = 1; stack.push_back({next, nd.depth + 1u}); }
+        }
+    }
+    std::vector<uint8_t> flat(0x110000, 0);
+    for (const UcRun& r : kGcRuns)
+        for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
+    two_stage(flat, &gc_stage1, &gc_stage2);
+}
+
+std::string HostModel::precompiled_normalize(const std::string& s, std::vector<uint32_t>* norig) const {
+    PcTables t{pc_units.data(), (uint32_t)pc_units.size(), pc_rep.data(), (uint32_t)pc_rep.size(), gc_stage1.data(), gc_stage2.data(), {pc_first[0], pc_first[1], pc_first[2], pc_first[3]}};
+    const int64_t n = (int64_t)s.size();
+    std::vector<nfc_mask_t> bound((size_t)(n >> 6) + 2, 0ull);
+    bound[0] = 1ull;                                       // one piece
+    std::string padded = s;
+    padded.append(8, '\0');
+    const uint8_t* text = (const uint8_t*)padded.data();
+    std::string out;
+    if (norig) norig->clear();
+    const uint32_t lost = pc_lost_chars(t, text, n, bound.data(), 0);
+    for (int64_t p = 0; p < n;) {
+        uint32_t l, ro = 0, rl = 0;
+        int64_t se = 0;
+        nfc_decode(text, n, p, &l);
+        const PcOut k = pc_char_out(t, text, n, bound.data(), p, &ro, &rl, &se);
+        if (k == PC_COPY) {
+            out.append(s, (size_t)p, l);
+            if (norig) norig->insert(norig->end(), l, (uint32_t)pc_chars_back(text, n, p, lost));
+        } else if (k == PC_REP) {
+            int64_t q = p;                                  // the source char the replacement's next char takes
+            bool inserted = false;                          // ... which is beyond the last source char
+            for (uint32_t z = 0; z < rl;) {
+                uint32_t cl, ql;
+                nfc_decode(t.rep + ro, rl, z, &cl);
+                out.append((const char*)t.rep + ro + z, cl);
+                z += cl;
+                const int64_t src = (inserted && z == rl && pc_tail_moves(t, text, n, bound.data(), se)) ? se : q;
+                if (norig) norig->insert(norig->end(), cl, (uint32_t)pc_chars_back(text, n, src, lost));
+                nfc_decode(text, n, q, &ql);
+                if (q + ql < se) q += ql; else inserted = true;
+            }
+        }
+        p += l;
+    }
+    return out;
+}
 
 std::string HostModel::nfc_normalize(const std::string& s, std::vector<uint32_t>* norig, bool* refused) const {
     const NfcTables t{nfc_stage1.data(), nfc_stage2.data(), nfc_map.data(), nfc_mask, nfc_seed};

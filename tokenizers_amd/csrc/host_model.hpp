@@ -129,6 +129,10 @@ struct HostModel {
     // NFC of a string that is one piece, by the core the device runs (nfc_core.hpp; host side: pattern normalization at load, the test
     // harness); norig (or null): per output byte, the first byte of the source char it is aligned to; *refused = a segment beyond NFC_SEG_MAX
     std::string nfc_normalize(const std::string& s, std::vector<uint32_t>* norig, bool* refused) const;
+    // Precompiled of a string that is one piece, by the core the device runs (precompiled_core.hpp; host side: tkamd_probe_precompiled, the
+    // test harness); norig (or null): per output byte, the first byte of the source char it is aligned to, the lost chars at the piece's start included
+    std::string precompiled_normalize(const std::string& s, std::vector<uint32_t>* norig) const;
+    void set_precompiled(const std::string& blob);      // decodes and validates a charsmap (Unsupported: malformed), builds the tables below
     void build_nfc();      // the NFC tables alone (from_json builds them behind an NFC normalizer; the test harness has no tokenizer)
 
     // ---- tables copied to the device ----
@@ -173,6 +177,16 @@ struct HostModel {
     std::vector<uint8_t> nfc_stage2;
     std::vector<MergeSlot> nfc_map;
     uint32_t nfc_mask = 0, nfc_seed = 0;
+
+    // Precompiled (precompiled_core.hpp): the charsmap's double array and replacement strings as the file holds them, the bytes a key starts
+    // with, the most output bytes a source byte can stand for (the bound of the normalized text), and the grapheme classes in two stages
+    std::vector<uint32_t> pc_units;
+    std::vector<uint8_t> pc_rep;
+    unsigned long long pc_first[4] = {0ull, 0ull, 0ull, 0ull};
+    uint32_t pc_growth = 1;
+    bool pc_space_runs = false;         // Sequence[Precompiled, Replace(Regex " {2,}" -> " ")]: inert behind WhitespaceSplit, refused elsewhere
+    std::vector<uint16_t> gc_stage1;
+    std::vector<uint8_t> gc_stage2;
 
     // ---- decode_batch tables: every decoder on the path is a per-token string function of (id, first kept token of the
     // document?), so decoding is a gather.  dec_entry[id] = {offset of the FIRST-position form, its length | flags,

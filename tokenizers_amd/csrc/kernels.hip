@@ -5,6 +5,7 @@
 //   text bytes ──documents─────► doc-start bitmask (+ added-token matches, prefix space)          kernels/documents.hip
 //        │──────bert_norm──────► normalised text X (BertNormalizer)                               kernels/bert_norm.hip
 //        │──────nfc────────────► NFC quick check of the text; normalised text X where it fails               kernels/nfc.hip
+//        │──────precompiled────► Precompiled normalizer (charsmap trie per grapheme cluster) in front of Unigram   kernels/precompiled.hip
 //        │──────metaspace──────► "▁" text X + its pre-token starts (SentencePiece-style BPE)        kernels/metaspace.hip
 //        │──────pretok_*───────► pre-token start (/ end) bitmask: per-lane 64-bit mask algebra    kernels/pretok_{gpt2,llama3,local}.hip
 //        │──────scan_emit──────► pt_start[P+1]   (byte offset of every pre-token = "split")       kernels/scan_emit.hip
@@ -31,6 +32,7 @@
 #include "overflow_core.hpp"
 #include "bert_norm_core.hpp"
 #include "nfc_core.hpp"
+#include "precompiled_core.hpp"
 #include "pretok_gpt2_core.hpp"
 #include "pretok_l3_core.hpp"
 #include "pretok_ds3_core.hpp"
@@ -87,6 +89,7 @@ static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)(
 #include "kernels/pretok_local.hip"
 #include "kernels/bert_norm.hip"
 #include "kernels/nfc.hip"
+#include "kernels/precompiled.hip"
 #include "kernels/metaspace.hip"
 #include "kernels/scan_emit.hip"
 #include "kernels/bpe.hip"

@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include "nfc_core.hpp"
+#include "precompiled_core.hpp"
 #include "tables.hpp"
 
 namespace tkamd {
@@ -315,7 +316,9 @@ enum : int {
     NOTE_NFC_SEEN = 32768,        // not an error: a batch behind an NFC normalizer that was run over the text as it came (k_nfc_check vouches for almost all text) holds
                                   // a lane the quick check cannot vouch for: the host runs it again through the normalizer's kernels and pauses the speculation
     ERR_NFC_SEGMENT = 65536,      // NFC: a starter with more than 48 chars of combining marks (and other chars that may compose) behind it; such a segment is not normalized on the device
-    NOTE_BITS = NOTE_REORDER_SEEN | NOTE_ADDED_SEEN | NOTE_NFC_SEEN,
+    NOTE_PC_LOST = 131072,        // not an error: behind a Precompiled normalizer a piece's first chars became nothing (U+FEFF in front of a document): with offsets
+                                  // k_pc_lost_fix then moves that piece's alignments the way the reference loses those chars
+    NOTE_BITS = NOTE_REORDER_SEEN | NOTE_ADDED_SEEN | NOTE_NFC_SEEN | NOTE_PC_LOST,
     ERR_QUEUE_FULL_PAD = 0,          // a work queue / the row area was too small for this batch: the host grows it and runs the batch again
 };
 
@@ -436,7 +439,15 @@ void launch_mask_or2(hipStream_t st, unsigned long long* dst, const unsigned lon
 void launch_emit_boundaries(hipStream_t st, const unsigned long long* mask, const uint32_t* wprefix, int64_t n_bytes, const int64_t* len_dev, const int64_t* total, int64_t* out);
 void launch_metaspace(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* doc_off, int64_t n_docs, const unsigned long long* pstart,
                       const unsigned long long* dstart, const unsigned long long* mmask, const unsigned long long* smask, uint32_t prepend, uint8_t* olen,
-                      uint32_t* wsum, uint32_t* bsum, uint32_t* wbase, int64_t* x_len, uint8_t* xtext, uint32_t* nos, int64_t* xdoc_off);
+                      uint32_t* wsum, uint32_t* bsum, uint32_t* wbase, int64_t* x_len, uint8_t* xtext, uint32_t* nos, int64_t* xdoc_off,
+                      const int64_t* len_dev = nullptr, const uint32_t* map = nullptr);      // behind a normalizer: the text's length on the device, the original byte of its bytes
+// Precompiled (kernels/precompiled.hip): text -> normalized text (*x_len bytes) + the source char of every byte (nos, or null) + the document CSR in it.
+// olen: n_bytes + 80 bytes, ltot: a uint16 per 16-byte lane; bound: the piece starts (launch_nfc_bound).  NOTE_PC_LOST into *err where a piece's first chars became nothing.
+void launch_precompiled(hipStream_t st, const PcTables& pt, const uint8_t* text, int64_t n_bytes, const int64_t* doc_off, int64_t n_docs, const unsigned long long* verbatim,
+                        const unsigned long long* bound, uint8_t* olen, uint16_t* ltot, uint32_t* wsum, uint32_t* bsum, uint32_t* wbase, int64_t* x_len, uint8_t* ntext,
+                        uint32_t* nos, int64_t* ndoc_off, int* err, int grid, int64_t out_cap);      // out_cap: what ntext / nos hold; a longer text fails the batch (ERR_INTERNAL), unwritten
+void launch_pc_translate_matches(hipStream_t st, uint32_t* list, const uint32_t* n_list, const uint8_t* olen, const uint16_t* ltot, const uint32_t* wbase, int64_t n_bytes,
+                                 const int64_t* x_len);
 void launch_ms_units(hipStream_t st, const uint8_t* xtext, int64_t n_x, const int64_t* x_len, const unsigned long long* pmask, unsigned long long* startmask,
                      int64_t n_words, bool split);
 void launch_ms_piece_rank(hipStream_t st, const unsigned long long* startmask, const uint32_t* wprefix, const unsigned long long* pmask, const uint32_t* pprefix,

@@ -159,11 +159,12 @@ void launch_nfc_normalize(hipStream_t st, const NfcTables& nt, const uint8_t* te
 // the "▁" front (kernels/metaspace.hip): count -> scan of the 64-byte words -> write, then the document CSR in X (the BertNormalizer's)
 void launch_metaspace(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* doc_off, int64_t n_docs, const unsigned long long* pstart,
                       const unsigned long long* dstart, const unsigned long long* mmask, const unsigned long long* smask, uint32_t prepend, uint8_t* olen,
-                      uint32_t* wsum, uint32_t* bsum, uint32_t* wbase, int64_t* x_len, uint8_t* xtext, uint32_t* nos, int64_t* xdoc_off) {
+                      uint32_t* wsum, uint32_t* bsum, uint32_t* wbase, int64_t* x_len, uint8_t* xtext, uint32_t* nos, int64_t* xdoc_off, const int64_t* len_dev,
+                      const uint32_t* map) {
     const int64_t n_words = (n_bytes >> 6) + 1;
     uint8_t* const ltot = bn_ltot_of(olen, n_bytes);
     const BnOlen ol{olen, ltot};
-    const MsArgs a{text, n_bytes, pstart, dstart, mmask, smask, prepend};
+    const MsArgs a{text, n_bytes, pstart, dstart, mmask, smask, prepend, len_dev, map};
     hipLaunchKernelGGL(k_ms_count, dim3(blocks_for(n_bytes + 1, 256 * BN_LANE)), dim3(256), 0, st, a, olen, ltot, wsum);
     unsigned nb = blocks_for(n_words, 256);
     hipLaunchKernelGGL(k_u32_reduce, dim3(nb), dim3(256), 0, st, (const uint32_t*)wsum, n_words, bsum);
@@ -172,6 +173,28 @@ void launch_metaspace(hipStream_t st, const uint8_t* text, int64_t n_bytes, cons
     hipLaunchKernelGGL(k_ms_write, dim3(blocks_for(n_bytes, 256 * BN_LANE)), dim3(256), 0, st, a, ol, (const uint32_t*)wbase, xtext, nos);
     hipLaunchKernelGGL(k_bn_doc_offsets, dim3(blocks_for(n_docs + 1, 256)), dim3(256), 0, st, doc_off, n_docs, n_bytes, ol,
                        (const uint32_t*)wbase, (const int64_t*)x_len, xdoc_off);
+}
+// Precompiled (kernels/precompiled.hip): count -> scan of the 64-byte words -> write (-> the lost chars' fix, with offsets), then the document CSR
+void launch_precompiled(hipStream_t st, const PcTables& pt, const uint8_t* text, int64_t n_bytes, const int64_t* doc_off, int64_t n_docs, const unsigned long long* verbatim,
+                        const unsigned long long* bound, uint8_t* olen, uint16_t* ltot, uint32_t* wsum, uint32_t* bsum, uint32_t* wbase, int64_t* x_len, uint8_t* ntext,
+                        uint32_t* nos, int64_t* ndoc_off, int* err, int grid, int64_t out_cap) {
+    const int64_t n_words = (n_bytes >> 6) + 1;
+    const PcOlen ol{olen, ltot};
+    const PcArgs a{pt, text, n_bytes, verbatim, bound};
+    hipLaunchKernelGGL(k_pc_count, dim3(blocks_for(n_bytes + 1, 256 * PC_LANE)), dim3(256), 0, st, a, olen, ltot, wsum, err);
+    unsigned nb = blocks_for(n_words, 256);
+    hipLaunchKernelGGL(k_u32_reduce, dim3(nb), dim3(256), 0, st, (const uint32_t*)wsum, n_words, bsum);
+    hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, st, bsum, (int64_t)nb, (const int64_t*)nullptr, (int64_t)1, x_len);
+    hipLaunchKernelGGL(k_u32_down, dim3(nb), dim3(256), 0, st, (const uint32_t*)wsum, n_words, (const uint32_t*)bsum, wbase);
+    hipLaunchKernelGGL(k_pc_check_len, dim3(1), dim3(64), 0, st, x_len, out_cap, err);
+    hipLaunchKernelGGL(k_pc_write, dim3(blocks_for(n_bytes, 256 * PC_LANE)), dim3(256), 0, st, a, ol, (const uint32_t*)wbase, (const int64_t*)x_len, ntext, nos);
+    if (nos) hipLaunchKernelGGL(k_pc_lost_fix, dim3(std::min<unsigned>(blocks_for(n_words, 256), (unsigned)std::max(1, grid))), dim3(256), 0, st, a, ol, (const uint32_t*)wbase,
+                                (const int64_t*)x_len, (const int*)err, nos);
+    hipLaunchKernelGGL(k_pc_doc_offsets, dim3(blocks_for(n_docs + 1, 256)), dim3(256), 0, st, doc_off, n_docs, n_bytes, ol, (const uint32_t*)wbase, (const int64_t*)x_len, ndoc_off);
+}
+void launch_pc_translate_matches(hipStream_t st, uint32_t* list, const uint32_t* n_list, const uint8_t* olen, const uint16_t* ltot, const uint32_t* wbase, int64_t n_bytes,
+                                 const int64_t* x_len) {
+    hipLaunchKernelGGL(k_pc_translate_matches, dim3(256), dim3(256), 0, st, list, n_list, PcOlen{olen, ltot}, wbase, n_bytes, x_len);
 }
 void launch_ms_units(hipStream_t st, const uint8_t* xtext, int64_t n_x, const int64_t* x_len, const unsigned long long* pmask, unsigned long long* startmask,
                      int64_t n_words, bool split) {

@@ -21,10 +21,43 @@ struct MsArgs {
     const unsigned long long* mmask;      // added-token matches: first bytes, and the bytes inside them (null: no matches)
     const unsigned long long* smask;
     uint32_t prepend;                     // MsPrepend
+    const int64_t* len_dev;               // behind a normalizer: the text is its output, *len_dev bytes of the n_bytes the host bounds it by (null: n_bytes)
+    const uint32_t* map;                  // ... and this is the original byte of every byte of it: the source map is composed with it (null: the raw text)
 };
 
 __device__ __forceinline__ bool ms_bit(const unsigned long long* __restrict__ m, int64_t i) { return (m[i >> 6] >> (i & 63)) & 1ull; }
 __device__ __forceinline__ bool ms_is_bar(const uint8_t* __restrict__ p) { return p[0] == 0xE2u && p[1] == 0x96u && p[2] == 0x81u; }
+
+// char::is_whitespace (the White_Space property) as UTF-8: the length of the whitespace char that starts at p, or 0
+__device__ __forceinline__ uint32_t ms_ws_len(const uint8_t* __restrict__ p) {
+    const uint32_t b = p[0];
+    if (b < 0x80u) return (b == 0x20u || b - 9u < 5u) ? 1u : 0u;
+    if (b == 0xC2u) return (p[1] == 0x85u || p[1] == 0xA0u) ? 2u : 0u;
+    if (b == 0xE1u) return (p[1] == 0x9Au && p[2] == 0x80u) ? 3u : 0u;
+    if (b == 0xE2u) return ((p[1] == 0x80u && (p[2] - 0x80u < 11u || p[2] == 0xA8u || p[2] == 0xA9u || p[2] == 0xAFu)) || (p[1] == 0x81u && p[2] == 0x9Fu)) ? 3u : 0u;
+    if (b == 0xE3u) return (p[1] == 0x80u && p[2] == 0x80u) ? 3u : 0u;
+    return 0u;
+}
+// is byte i (i > 0) behind a whitespace char
+__device__ __forceinline__ bool ms_behind_ws(const uint8_t* __restrict__ text, int64_t i) {
+    const uint32_t b = text[i - 1];
+    if (b < 0x80u) return b == 0x20u || b - 9u < 5u;
+    return (i >= 2 && ms_ws_len(text + i - 2) == 2u) || (i >= 3 && ms_ws_len(text + i - 3) == 3u);
+}
+// MS_WORD (Sequence[WhitespaceSplit, Metaspace "always"]): whitespace chars are dropped; the first char of a word -- behind whitespace, or
+// at a piece start -- takes a "▁" in front unless it is one
+__device__ __forceinline__ uint32_t ms_word_count(const MsArgs& a, int64_t i, uint32_t b, bool piece_start) {
+    if ((b & 0xC0u) == 0x80u) {                                       // a continuation byte: nothing if its char is whitespace
+        for (int k = 1; k <= 2 && i - k >= 0; ++k) {
+            const uint32_t c = a.text[i - k];
+            if ((c & 0xC0u) == 0x80u) continue;
+            return ms_ws_len(a.text + i - k) > (uint32_t)k ? 0u : 1u;
+        }
+        return 1u;
+    }
+    if (ms_ws_len(a.text + i)) return 0u;
+    return 1u + (((piece_start || ms_behind_ws(a.text, i)) && !ms_is_bar(a.text + i)) ? 3u : 0u);
+}
 
 // does the piece that starts at source byte i (b = text[i]) take a "▁" in front
 __device__ __forceinline__ bool ms_takes_prepend(const MsArgs& a, int64_t i, uint32_t b) {
@@ -37,27 +70,31 @@ __device__ __forceinline__ bool ms_takes_prepend(const MsArgs& a, int64_t i, uin
 // output bytes of source byte i, the per-byte way
 __device__ __forceinline__ uint32_t ms_count_byte(const MsArgs& a, int64_t i, uint32_t b, bool verbatim, bool piece_start) {
     if (verbatim) return 1u;
+    if (a.prepend == MS_WORD) return ms_word_count(a, i, b, piece_start);
     return (b == 0x20u ? 3u : 1u) + ((piece_start && ms_takes_prepend(a, i, b)) ? 3u : 0u);
 }
 
 __global__ __launch_bounds__(256) void k_ms_count(MsArgs a, uint8_t* __restrict__ olen, uint8_t* __restrict__ ltot, uint32_t* __restrict__ wsum) {
     const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * BN_LANE;
+    const int64_t n = a.len_dev ? *a.len_dev : a.n_bytes;         // (lanes between the text's end and its bound leave zeros: the scan covers the bound)
     uint32_t o[4] = {0u, 0u, 0u, 0u};
     bool plain = false;                                             // sixteen ASCII bytes, no space, no piece start, no match: one output byte each
-    if (i0 < a.n_bytes) {
+    if (i0 < n) {
         const Unaligned16 t = *(const Unaligned16*)(a.text + i0);   // (readable TEXT_PAD bytes past the end)
         const uint32_t x[4] = {t.a, t.b, t.c, t.d};
         const uint32_t vb = a.mmask ? (mask16(a.mmask, i0) | mask16(a.smask, i0)) : 0u;
         const uint32_t pb = mask16(a.pstart, i0);
         uint32_t sp = 0u;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) sp |= sw_eq(x[k], 0x20u);
-        if (((t.a | t.b | t.c | t.d) & SW_H) == 0u && sp == 0u && (vb | pb) == 0u && i0 + BN_LANE <= a.n_bytes) {
+        for (int k = 0; k < 4; ++k) sp |= a.prepend == MS_WORD ? sw_lt(x[k], 0x21u) : sw_eq(x[k], 0x20u);
+        // (MS_WORD: no whitespace in the lane, and an ASCII char that is none in front of it -- else the first byte may open a word)
+        if (a.prepend == MS_WORD && i0 > 0 && a.text[i0 - 1] - 0x21u >= 0x5Fu) sp = 1u;
+        if (((t.a | t.b | t.c | t.d) & SW_H) == 0u && sp == 0u && (vb | pb) == 0u && i0 + BN_LANE <= n) {
             plain = true;
 #pragma unroll
             for (int k = 0; k < 4; ++k) o[k] = SW_1;
         } else {
-            const int nv = (int)min((int64_t)BN_LANE, a.n_bytes - i0);
+            const int nv = (int)min((int64_t)BN_LANE, n - i0);
             for (int j = 0; j < nv; ++j)
                 o[j >> 2] |= ms_count_byte(a, i0 + j, (x[j >> 2] >> (8 * (j & 3))) & 0xFFu, (vb >> j) & 1u, (pb >> j) & 1u) << (8 * (j & 3));
             *(uint4*)(olen + i0) = make_uint4(o[0], o[1], o[2], o[3]);
@@ -82,29 +119,53 @@ __global__ __launch_bounds__(256) void k_ms_write(MsArgs a, BnOlen olen, const u
     const Unaligned16 t = *(const Unaligned16*)(a.text + i0);
     if (lt & BN_LTOT_PLAIN) {
         *(Unaligned16*)(xtext + pos) = t;
-        if (nos) {
+        if (nos && a.map) {
+#pragma unroll
+            for (int j = 0; j < BN_LANE; j += 4) *(Unaligned16*)(nos + pos + j) = *(const Unaligned16*)(a.map + i0 + j);
+        } else if (nos) {
             const uint32_t b0 = (uint32_t)i0;
 #pragma unroll
             for (int j = 0; j < BN_LANE; j += 4) *(Unaligned16*)(nos + pos + j) = Unaligned16{b0 + j, b0 + j + 1u, b0 + j + 2u, b0 + j + 3u};
         }
         return;
     }
+    const int64_t n = a.len_dev ? *a.len_dev : a.n_bytes;
     const uint32_t x[4] = {t.a, t.b, t.c, t.d};
     const uint32_t vb = a.mmask ? (mask16(a.mmask, i0) | mask16(a.smask, i0)) : 0u;
     const uint32_t pb = mask16(a.pstart, i0);
-    const int nv = (int)min((int64_t)BN_LANE, a.n_bytes - i0);
+    const int nv = (int)min((int64_t)BN_LANE, n - i0);
     for (int j = 0; j < nv; ++j) {
         const int64_t i = i0 + j;
         const uint32_t b = (x[j >> 2] >> (8 * (j & 3))) & 0xFFu;
         if ((vb >> j) & 1u) {                                       // a match byte: verbatim, its own original byte
             xtext[pos] = (uint8_t)b;
-            if (nos) nos[pos] = (uint32_t)i;
+            if (nos) nos[pos] = a.map ? a.map[i] : (uint32_t)i;
+            ++pos;
+            continue;
+        }
+        if (a.prepend == MS_WORD) {                                 // whitespace dropped, a "▁" in front of a word's first char
+            const uint32_t c = ms_word_count(a, i, b, (pb >> j) & 1u);
+            if (!c) continue;
+            uint32_t cs = (uint32_t)i;
+            if (nos) {
+                if ((b & 0xC0u) == 0x80u) { int k = 0; while (k < 3 && cs > 0u && (a.text[cs] & 0xC0u) == 0x80u) { --cs; ++k; } }
+                if (a.map) cs = a.map[cs];
+            }
+            if (c > 1u) {
+                xtext[pos] = 0xE2u; xtext[pos + 1] = 0x96u; xtext[pos + 2] = 0x81u;
+                if (nos) { nos[pos] = cs; nos[pos + 1] = cs; nos[pos + 2] = cs; }
+                pos += 3;
+            }
+            xtext[pos] = (uint8_t)b;
+            if (nos) nos[pos] = cs;
             ++pos;
             continue;
         }
         // the start of the source char (a continuation byte belongs to the char in front of it: its alignment is that char's whole range)
         uint32_t cs = (uint32_t)i;
         if (nos && (b & 0xC0u) == 0x80u) { int k = 0; while (k < 3 && cs > 0u && (a.text[cs] & 0xC0u) == 0x80u) { --cs; ++k; } }
+        const uint32_t ci = (nos && a.map) ? a.map[i] : (uint32_t)i;
+        if (nos && a.map) cs = a.map[cs];
         if (((pb >> j) & 1u) && ms_takes_prepend(a, i, b)) {
             xtext[pos] = 0xE2u; xtext[pos + 1] = 0x96u; xtext[pos + 2] = 0x81u;
             if (nos) { nos[pos] = cs; nos[pos + 1] = cs; nos[pos + 2] = cs; }
@@ -112,7 +173,7 @@ __global__ __launch_bounds__(256) void k_ms_write(MsArgs a, BnOlen olen, const u
         }
         if (b == 0x20u) {
             xtext[pos] = 0xE2u; xtext[pos + 1] = 0x96u; xtext[pos + 2] = 0x81u;
-            if (nos) { nos[pos] = (uint32_t)i; nos[pos + 1] = (uint32_t)i; nos[pos + 2] = (uint32_t)i; }
+            if (nos) { nos[pos] = ci; nos[pos + 1] = ci; nos[pos + 2] = ci; }
             pos += 3;
         } else {
             xtext[pos] = (uint8_t)b;

@@ -197,13 +197,16 @@ enum PretokKind {
 };
 // NORM_METASPACE: Sequence[Prepend("▁"), Replace(" " -> "▁")] or Replace(" " -> "▁") alone (prepend.rs:16-24, replace.rs:83)
 // NORM_NFC: NFC alone or Sequence[NFC] (normalizers/unicode.rs), in front of byte-level BPE (nfc_core.hpp, kernels/nfc.hip)
-enum NormKind { NORM_NONE = 0, NORM_BERT = 1, NORM_METASPACE = 2, NORM_NFC = 3 };
+// NORM_PRECOMPILED: Precompiled alone, Sequence[Precompiled] or Sequence[Precompiled, Replace(Regex " {2,}" -> " ")] in front of Unigram
+// behind the "▁" front (normalizers/precompiled.rs; precompiled_core.hpp, kernels/precompiled.hip)
+enum NormKind { NORM_NONE = 0, NORM_BERT = 1, NORM_METASPACE = 2, NORM_NFC = 3, NORM_PRECOMPILED = 4 };
 // where the "▁" front puts a "▁" in front of a piece (the raw text between document edges and added-token matches)
 enum MsPrepend {
     MS_NEVER = 0,      // Metaspace prepend_scheme "never"; Replace alone
     MS_ALWAYS = 1,     // Metaspace "always": unless the piece starts with ' ' or "▁"
     MS_FIRST = 2,      // Metaspace "first": the same, only for a piece at its sequence's offset 0 (a document start)
     MS_PIECE = 3,      // the Prepend normalizer: every non-empty piece, whatever it starts with
+    MS_WORD = 4,       // Sequence[WhitespaceSplit, Metaspace "always"]: whitespace is dropped and every word gets one unless it starts with "▁"
 };
 
 // ---- the tiktoken family of Split patterns (pre_tokenizers/split.rs:76-105 with a SysRegex, tokenizer/pattern.rs:63-83) -------
