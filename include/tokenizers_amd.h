@@ -100,7 +100,8 @@ typedef struct tkamd_info {
     int32_t pre_tokenizer;  /* 1 ByteLevel(GPT-2 regex; also that regex spelled as a Split), 2 Split(a pattern of the tiktoken family:
                                Llama-3 / cl100k, Qwen2, o200k, tekken ...; pre_tokenizers/split.rs:76-105) + ByteLevel, 3 Whitespace,
                                4 WhitespaceSplit, 5 BertPreTokenizer, 6 ByteLevel(use_regex=false), 7 the U+2581 front of SentencePiece-style BPE,
-                               8 the chain of three Splits of DeepSeek-V3 / R1 + ByteLevel(use_regex=false) */
+                               8 the chain of three Splits of DeepSeek-V3 / R1 + ByteLevel(use_regex=false),
+                               9 Sequence[Digits, ByteLevel(GPT-2 regex)]: StarCoder / StarCoder2 / SantaCoder, Granite code, Command-R */
     int32_t normalizer;     /* 0 none, 1 BertNormalizer                                         */
     int32_t vocab_size;
     int32_t n_merges;

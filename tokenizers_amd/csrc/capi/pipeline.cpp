@@ -183,7 +183,8 @@ void Batch::check_request() {
           : metaspace ? 3 * n_p + 3 * (n_docs + 2 * (int64_t)mcap + 1) + 64
           : n_bytes + (prefix_space ? n_docs + (int64_t)mcap : 0);
     if (n_x >= (int64_t)0xFFFFFF00ll) throw Invalid("batch larger than 4 GiB: split it (byte offsets are 32-bit on the device)");
-    const bool bpe_path = hm.model == MODEL_BPE && !hm.char_bpe && (hm.pretok == PT_BYTELEVEL_GPT2 || hm.pretok == PT_LLAMA3 || hm.pretok == PT_SPLIT_CHAIN || hm.pretok == PT_BYTELEVEL_NOREGEX);
+    const bool bpe_path = hm.model == MODEL_BPE && !hm.char_bpe && (hm.pretok == PT_BYTELEVEL_GPT2 || hm.pretok == PT_LLAMA3 || hm.pretok == PT_SPLIT_CHAIN || hm.pretok == PT_DIGITS_GPT2 ||
+                                                                      hm.pretok == PT_BYTELEVEL_NOREGEX);
     const bool local_pretok = hm.pretok == PT_WHITESPACE || hm.pretok == PT_WHITESPACE_SPLIT || hm.pretok == PT_BERT;
     const bool word_models = (hm.model == MODEL_WORDLEVEL || hm.model == MODEL_WORDPIECE) && local_pretok;
     const bool char_bpe = hm.model == MODEL_BPE && hm.char_bpe && (local_pretok || metaspace);      // BPE over characters rides the word models' pre-tokenizers, or the "▁" front
@@ -691,6 +692,16 @@ void Batch::pretokenize() {
         launch_pretok_ds3(st, x_text, n_x, x_len_dev, w->w_docmask.as<ull>(), t->dt.uc1, t->dt.uc2, t->t_ucc1.as<uint16_t>(), t->t_ucc2.as<uint8_t>(),
                           w->w_startmask.as<ull>(), w->w_endmask.as<ull>(), piece_off ? piece_off : x_doc_off, piece_off ? (int64_t)seg_cap : n_docs, piece_n_dev,
                           w->w_slow_docs.as<uint32_t>(), d_counters + CNT_SLOW_DOCS, lead_done ? w->w_leadmask.as<ull>() : nullptr);
+        pf.end();
+    } else if (hm.pretok == PT_DIGITS_GPT2) {
+        // Sequence[Digits, ByteLevel] of the StarCoder family: the GPT-2 rule inside the pieces Digits cuts, one lane kernel
+        if (off_mode == TKAMD_OFFSETS_CHAR && x_text == d_text && !x_len_dev && n_x == n_bytes) {
+            w->w_leadmask.reserve((size_t)(W0 + 1) * 8);
+            lead_done = true;
+        }
+        pf.begin("pretok_digits");
+        launch_pretok_digits(st, x_text, n_x, x_len_dev, w->w_docmask.as<ull>(), t->dt.uc1, t->dt.uc2, hm.digits_individual, w->w_startmask.as<ull>(),
+                             lead_done ? w->w_leadmask.as<ull>() : nullptr);
         pf.end();
     } else if (metaspace) {
         // every piece start (the document mask holds the match edges now) and every "▁" behind another char (or every "▁": split)

@@ -91,6 +91,9 @@ const UcRun kUcCaseRuns[] = {      // (flags: UCC_UPPER / UCC_LOWER, tables.hpp)
 const UcRun kUcPsmRuns[] = {       // (flags: UC2_P / UC2_S / UC2_M / UC2_CJK, tables.hpp)
 #include "unicode_psm_ranges.inc"
 };
+const UcRun kUcNumericRuns[] = {   // (flags: UC_RUST_N, tables.hpp)
+#include "unicode_numeric_ranges.inc"
+};
 
 const UcRun kGcRuns[] = {          // (flags: GC_* of precompiled_core.hpp)
 #include "grapheme_tables.inc"
@@ -193,6 +196,10 @@ void build_unicode(HostModel& m) {
     std::vector<uint8_t> flat(0x110000, 0);
     for (const UcRun& r : kUcRuns)
         for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
+    // char::is_numeric, the class the Digits pre-tokenizer splits on: one more flag of the same byte, only where a kernel reads it
+    if (m.pretok == PT_DIGITS_GPT2)
+        for (const UcRun& r : kUcNumericRuns)
+            for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] |= r.flags;
     m.uc_stage1.assign(UC_STAGE1_LEN, 0);
     m.uc_stage2.clear();
     std::unordered_map<std::string, uint16_t> seen;
@@ -628,6 +635,40 @@ bool parse_split_chain(const JsonValue* seq, HostModel& m) {
     return true;
 }
 
+// ---- Sequence[Digits(individual_digits), ByteLevel(use_regex=true)]: StarCoder / StarCoder2 / SantaCoder, Granite code, Command-R --------
+// (pretok_digits_core.hpp).  True for that Sequence; false for a Sequence that holds no Digits; every other place of a Digits is refused
+// with its reason.
+bool parse_digits_bytelevel(const JsonValue* seq, HostModel& m) {
+    const size_t n = seq->arr.size();
+    size_t at = n;
+    for (size_t k = 0; k < n; ++k)
+        if (seq->arr[k] && seq->arr[k]->get_str("type") == "Digits") { at = k; break; }
+    if (at == n) return false;
+    bool bytelevel_in_front = false;
+    for (size_t k = 0; k < at; ++k) bytelevel_in_front |= seq->arr[k] && seq->arr[k]->get_str("type") == "ByteLevel";
+    // behind ByteLevel the text is the byte-level alphabet, where six byte values (0xB2 0xB3 0xB9 0xBC 0xBD 0xBE) are numeric chars: Digits
+    // then splits inside code points
+    if (bytelevel_in_front)
+        throw Unsupported("pre_tokenizer: this Sequence is outside the hot path: Digits behind ByteLevel reads the byte-level alphabet and splits inside code points "
+                          "(Falcon's Sequence[Punctuation, ByteLevel, Digits, Split] chain)");
+    if (n != 2 || at != 0)
+        throw Unsupported("pre_tokenizer: this Sequence is outside the hot path: Digits in a chain of " + std::to_string(n) + " pre-tokenizers (Falcon's "
+                          "Sequence[Punctuation, ByteLevel, Digits, Split] chain is one); only Sequence[Digits, ByteLevel] is on it");
+    const JsonValue* b = seq->arr[1].get();
+    if (!b || b->get_str("type") != "ByteLevel")
+        throw Unsupported("pre_tokenizer: Sequence[Digits, " + (b ? b->get_str("type") : std::string("null")) + "]: only Sequence[Digits, ByteLevel] is on the path");
+    if (!b->get_bool("use_regex", true))
+        throw Unsupported("pre_tokenizer: Sequence[Digits, ByteLevel(use_regex=false)] is outside the hot path (only use_regex=true behind Digits is on it)");
+    // ByteLevel::pre_tokenize puts its prefix space in front of every piece it is handed (byte_level.rs:122-125): behind Digits in front of
+    // every digit
+    if (b->get_bool("add_prefix_space", true))
+        throw Unsupported("pre_tokenizer: Sequence[Digits, ByteLevel(add_prefix_space=true)] (a prefix space in front of every piece Digits cuts)");
+    m.digits_individual = seq->arr[0]->get_bool("individual_digits", false);
+    m.byte_level = true;
+    m.add_prefix_space = false;
+    return true;
+}
+
 const char* const kMetaspace = "\xE2\x96\x81";     // U+2581, the "▁" of SentencePiece
 
 // A JSON number as serde_json reads it into an f64 WITHOUT its float_roundtrip feature -- how the reference is built (tokenizers/Cargo.toml:
@@ -774,6 +815,7 @@ PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
     if (type == "Whitespace") return PT_WHITESPACE;
     if (type == "WhitespaceSplit") return PT_WHITESPACE_SPLIT;
     if (type == "BertPreTokenizer") return PT_BERT;
+    if (type == "Digits") throw Unsupported("pre_tokenizer: Digits alone is outside the hot path (only Sequence[Digits, ByteLevel] in front of byte-level BPE is on it)");
     if (type == "Sequence") {
         const JsonValue* seq = pt->get("pretokenizers");
         if (seq && seq->is_array() && seq->arr.size() == 2) {
@@ -821,6 +863,7 @@ PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
             return PT_METASPACE;
         }
         if (seq && seq->is_array() && parse_split_chain(seq, m)) return PT_SPLIT_CHAIN;
+        if (seq && seq->is_array() && parse_digits_bytelevel(seq, m)) return PT_DIGITS_GPT2;
         throw Unsupported("pre_tokenizer: this Sequence is outside the hot path");
     }
     throw Unsupported("pre_tokenizer: type '" + type + "' is outside the hot path");
@@ -1226,6 +1269,9 @@ HostModel HostModel::from_json(const char* json, size_t len) {
         two_stage(flat, &m.ucc_stage1, &m.ucc_stage2);
     }
 
+    if (m.pretok == PT_DIGITS_GPT2 && m.norm != NORM_NONE && m.norm != NORM_NFC)
+        throw Unsupported("pre_tokenizer: Sequence[Digits, ByteLevel] behind a normalizer other than NFC");
+
     // ---- post-processor: offset trimming + the special tokens it puts around a single sequence ----
     {
         std::function<void(const JsonValue*)> apply = [&](const JsonValue* pp) {
@@ -1376,6 +1422,8 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     // Unigram keeps its vocabulary as an ARRAY of [piece, score], id = index (models/unigram/serialization.rs:13-30); every other model
     // as an object piece -> id.  Both fill the same map `v` that added tokens, templates, padding and the decode tables read.
     const bool unigram = mtype == "Unigram";
+    if (m.pretok == PT_DIGITS_GPT2 && mtype != "BPE")
+        throw Unsupported("pre_tokenizer: Sequence[Digits, ByteLevel] in front of a " + mtype + " model (only in front of byte-level BPE is it on the path)");
     if (unigram ? !(vocab && vocab->is_array()) : !(vocab && vocab->is_object())) throw Invalid("tokenizer.json: model.vocab missing");
 
     std::unordered_map<std::string, uint32_t> v;
@@ -1660,7 +1708,8 @@ HostModel HostModel::from_json(const char* json, size_t len) {
         }
     }
     if (m.norm == NORM_NFC &&
-        !(m.model == MODEL_BPE && !m.char_bpe && (m.pretok == PT_BYTELEVEL_GPT2 || m.pretok == PT_LLAMA3 || m.pretok == PT_SPLIT_CHAIN || m.pretok == PT_BYTELEVEL_NOREGEX)))
+        !(m.model == MODEL_BPE && !m.char_bpe && (m.pretok == PT_BYTELEVEL_GPT2 || m.pretok == PT_LLAMA3 || m.pretok == PT_SPLIT_CHAIN || m.pretok == PT_DIGITS_GPT2 ||
+                                                  m.pretok == PT_BYTELEVEL_NOREGEX)))
         throw Unsupported("normalizer: NFC is only on the path in front of byte-level BPE (ByteLevel, or a Split of the tiktoken family + ByteLevel); "
                           "in front of BPE over characters, WordPiece, WordLevel or the U+2581 front it is not");
     // (the same refusal every encode call makes for any normalizer, made at load for this one: the file can never encode)

@@ -202,6 +202,7 @@ struct HostModel {
 
     std::vector<uint16_t> uc_stage1;    // [UC_STAGE1_LEN]
     std::vector<uint8_t> uc_stage2;     // [n_blocks*256]
+    bool digits_individual = false;     // PT_DIGITS_GPT2: Digits(individual_digits) -- every numeric char a piece, else every run of them
     SplitRule split_rule = SPLIT_RULE_LLAMA3;   // PT_LLAMA3: which member of the tiktoken family the Split pattern is (tables.hpp)
     std::vector<uint16_t> ucc_stage1;   // the pre-tokenizer's second class table, same two stages: the case classes of the case-split letter alternatives
                                         // (split_rule.letters == 2), or UC2_* of the chained Split (PT_SPLIT_CHAIN); else empty

@@ -405,6 +405,10 @@ inline size_t l3_tileflag_words(int64_t n_bytes) { return (size_t)((n_bytes + 1)
 void launch_pretok_ds3(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* docmask,
                        const uint16_t* uc1, const uint8_t* uc2, const uint16_t* ps1, const uint8_t* ps2, unsigned long long* startmask, unsigned long long* slowmask,
                        const int64_t* doc_off, int64_t n_docs, const int64_t* n_docs_dev, uint32_t* slow_docs, uint32_t* n_slow_docs, unsigned long long* leadmask = nullptr);
+// Sequence[Digits, ByteLevel(use_regex=true)] of the StarCoder family (PT_DIGITS_GPT2, pretok_digits_core.hpp): the arguments of launch_pretok_gpt2;
+// uc2 carries UC_RUST_N; individual: Digits(individual_digits)
+void launch_pretok_digits(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* docmask,
+                          const uint16_t* uc1, const uint8_t* uc2, bool individual, unsigned long long* startmask, unsigned long long* leadmask = nullptr);
 void launch_leadmask(hipStream_t st, const uint8_t* text, int64_t n_bytes, unsigned long long* leadmask);
 void launch_seq_regroup(hipStream_t st, const int64_t* seq_off, int64_t n_seqs, int64_t n_words, const int64_t* word_tok_off, int64_t* seq_tok_off, uint32_t* widx,
                         int64_t* first_tok);

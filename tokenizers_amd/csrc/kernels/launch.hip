@@ -272,6 +272,15 @@ void launch_pretok_ds3(hipStream_t st, const uint8_t* text, int64_t n_bytes, con
     hipLaunchKernelGGL(k_l3_slow_docs, dim3(doc_blocks), dim3(256), 0, st, (const unsigned long long*)slowmask, doc_off, n_docs, n_docs_dev, slow_docs, n_slow_docs);
     hipLaunchKernelGGL(k_pretok_ds3_slow, dim3(1024), dim3(64), 0, st, text, doc_off, (const uint32_t*)slow_docs, (const uint32_t*)n_slow_docs, q, startmask);
 }
+void launch_pretok_digits(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* docmask,
+                          const uint16_t* uc1, const uint8_t* uc2, bool individual, unsigned long long* startmask, unsigned long long* leadmask) {
+    const dim3 grid(blocks_for((n_bytes >> 6) + 1, G2_WORDS_PER_BLOCK));
+    unsigned long long* const none = nullptr;
+    if (individual && leadmask) hipLaunchKernelGGL((k_pretok_digits<true, true>), grid, dim3(256), 0, st, text, n_bytes, len_dev, docmask, uc1, uc2, startmask, leadmask);
+    else if (individual) hipLaunchKernelGGL((k_pretok_digits<true, false>), grid, dim3(256), 0, st, text, n_bytes, len_dev, docmask, uc1, uc2, startmask, none);
+    else if (leadmask) hipLaunchKernelGGL((k_pretok_digits<false, true>), grid, dim3(256), 0, st, text, n_bytes, len_dev, docmask, uc1, uc2, startmask, leadmask);
+    else hipLaunchKernelGGL((k_pretok_digits<false, false>), grid, dim3(256), 0, st, text, n_bytes, len_dev, docmask, uc1, uc2, startmask, none);
+}
 void launch_leadmask(hipStream_t st, const uint8_t* text, int64_t n_bytes, unsigned long long* leadmask) {
     hipLaunchKernelGGL(k_leadmask, dim3(blocks_for(n_bytes + 64, 256 * 16)), dim3(256), 0, st, text, n_bytes, leadmask);
 }
