@@ -49,7 +49,7 @@ void reserve_workspace(tkamd_tokenizer* t, Workspace* w, int64_t n_bytes, int64_
     const QueueSizes z = queue_sizes(N, t->q16_div, lookup_grid(t));
     w->w_rows.reserve(z.total * 16);
     w->w_queues.reserve(z.total * 8);
-    w->w_cstate.reserve((N / COMPACT_CHUNK + 4) * 8 + 16);
+    w->w_cstate.reserve(lb_state_words(N / COMPACT_CHUNK + 4) * 8 + 16);
     w->w_chunk_lo.reserve((N / COMPACT_CHUNK + 4) * 4);
     w->w_qcount.reserve((size_t)QCNT_WORDS * 4);
     w->w_pt_tokoff.reserve((N + 4) * 4);
@@ -235,7 +235,7 @@ void Batch::zero_batch_state() {
         if (p > 0) use_claims = false;
     }
     w->last_used_claims = use_claims;
-    const size_t cstate_bytes = (((size_t)n_x / (size_t)COMPACT_CHUNK + 4) * 8 + 15) & ~(size_t)15;
+    const size_t cstate_bytes = (lb_state_words((size_t)n_x / (size_t)COMPACT_CHUNK + 4) * 8 + 15) & ~(size_t)15;      // (the chunks' words and the groups')
     ZeroRegions z{};
     z.add(sc, SC_SLOTS * 8);
     // (behind BertNormalizer the mask covers the bound of the normalised text, three times the input: the words that text really has

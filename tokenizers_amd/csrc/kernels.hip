@@ -15,7 +15,7 @@
 //        │──────word_models────► WordPiece trie walk of the queued words                          kernels/word_models.hip
 //        │──────unigram────────► Unigram Viterbi of the queued words (f64 scores, state in LDS)    kernels/unigram.hip
 //        │──────scan_emit──────► pt_start[P+1] only when offsets / word ids are requested          kernels/scan_emit.hip
-//        │──────output─────────► ids[T] (single-pass look-back compaction), per-document CSR,      kernels/output.hip, results.hip
+//        │──────output─────────► ids[T] (single-pass compaction over published chunk totals), per-document CSR,      kernels/output.hip, results.hip
 //        │                       offsets, word ids, specials
 //   ids ────────decode─────────► text (decode_batch)                                              kernels/decode.hip
 //

@@ -479,7 +479,8 @@ void launch_bpe_merge_long(hipStream_t st, int grid, const DevTables& t, const u
 // kernels cannot run)
 void launch_bpe_merge_long_only(hipStream_t st, int grid, const DevTables& t, const uint8_t* text, const QView& v, void* rows, uint32_t* tmp_ids, uint32_t* tmp_end,
                                 uint32_t* list_huge, uint32_t* n_huge);
-// single-pass compaction; `state` (8 bytes per chunk of COMPACT_CHUNK pre-tokens) must be zero on entry; pt_tokoff may be null.
+// single-pass compaction; `state` (lb_state_words(chunks) 64-bit words: one per chunk of COMPACT_CHUNK pre-tokens and, behind them, one
+// per group of 64 chunks) must be zero on entry; pt_tokoff may be null.
 // Any grid makes progress (a look-back that runs out of patience computes the missing totals itself: kernels/output.hip);
 // compact_grid(n_cu) -- what is resident at once -- is the one that never has to.
 void launch_word_cache_insert(hipStream_t st, int grid, const DevTables& t, const uint8_t* text, const QView& v, const void* rows, const WordCache& wc);
@@ -491,6 +492,13 @@ void launch_zero_regions(hipStream_t st, int grid, const ZeroRegions& z);
 void launch_zero_tail(hipStream_t st, uint8_t* p, const int64_t* len_dev, int n, unsigned long long* mask = nullptr, int64_t mask_words = 0, int grid = 1);      // n <= 256 zero bytes at p[*len_dev ..]; mask: its words below (*len_dev >> 6) + 3 zeroed too
 constexpr int CP_ITEMS_PER_LANE = 4;                // pre-tokens per lane of k_compact (0.145 ms on C2 against 0.187 with eight; two: deleted in round 6, HISTORY.md)
 constexpr int COMPACT_CHUNK = 256 * CP_ITEMS_PER_LANE;   // pre-tokens per compaction chunk (and per tile of k_token_meta)
+// the compaction's state (kernels/results.hip): a word per chunk, then -- from a 128-byte boundary on -- a word per group of
+// LB_GROUP_CHUNKS chunks with their totals summed, LB_GROUP_STRIDE words (256 bytes) apart: the owners of a group's chunks add to its
+// word with device-scope atomics, which the memory side executes one after the other per 64-byte block.  The kernel places the group
+// words by the batch's own chunk count, the host sizes and zeroes by its bound: both through these two.
+constexpr int LB_GROUP_CHUNKS = 64, LB_GROUP_STRIDE = 32;
+constexpr size_t lb_group_base(size_t n_chunks) { return (n_chunks + 15) & ~(size_t)15; }
+constexpr size_t lb_state_words(size_t max_chunks) { return lb_group_base(max_chunks) + (max_chunks / LB_GROUP_CHUNKS + 1) * LB_GROUP_STRIDE; }
 // test hooks: environment switches the TESTS alone use (a compaction grid no launch would pick, a look-back without patience, ...), read
 // only when TKAMD_TEST_HOOKS=1 is set as well (capi.cpp)
 const char* test_hook(const char* name);

@@ -5,11 +5,11 @@
 // Token compaction: tok0[P] (+ rows) -> ids[T], the running token offset of every pre-token, the total.
 // Replaces: PreTokenizedString::into_encoding + Encoding::from_iter (tokenizer/pre_tokenizer.rs:198-263,
 // tokenizer/encoding.rs:541-562) for the whole batch at once.
-// ONE pass over the data with decoupled look-back (results.hip), software-pipelined so that nobody waits for it:
+// ONE pass over the data, single-pass prefix sums over published chunk totals (results.hip), software-pipelined so that nobody waits for them:
 //   front(c)   load the chunk's tok0 words and result rows, count, scan, PUBLISH the chunk's total, and assemble the chunk's
 //              ids (and chunk-local token offsets) in LDS -- none of which needs the tokens in front of the chunk;
-//   back(c)    resolve the look-back (by now the predecessors have long published), then LDS -> ids[] / pt_tokoff[] as whole
-//              wavefront-wide stores.
+//   back(c)    the chunk's place: the workgroup's own running prefix + the totals of the chunks since its previous one (by now
+//              long published), then LDS -> ids[] / pt_tokoff[] as whole wavefront-wide stores.
 // A workgroup runs front(c_next) before back(c): the look-back round trips hide behind a whole chunk of work (measured: the
 // un-pipelined kernel spent 45 % of its time in them).  Two LDS buffers alternate.  A chunk whose tokens do not fit the buffer
 // (> CP_STAGE: only text made of many-token pre-tokens) is scattered straight from its rows in back().
@@ -20,7 +20,7 @@
 // of the chunks in front of c, and a total is a pure function of tok0 and the rows, which are final before this kernel starts: a
 // wavefront that has polled an unpublished predecessor lb `patience` times (its owner may not have been scheduled yet, and may
 // not be until this workgroup gets out of the way) computes that chunk's total itself and publishes it on the owner's behalf
-// (results.hip lb_resolve; the owner later stores the same value and does its own copy-out, which nobody waits for).  Every missing
+// (results.hip lb_window; the owner later stores the same value and does its own copy-out, which nobody waits for).  Every missing
 // total is therefore finite work for whoever waits for it: every wait ends, at any grid and any residency.
 // (Round 4 first handed the chunks out by a global ticket, which gives the same guarantee by construction: an atomic on one address
 // resolves at ~12 ns apiece at the memory side, 19 k tickets a C2 batch, and the kernel went from 0.14 to 0.26 ms -- profiles/r4a_*.)
@@ -155,8 +155,8 @@ __device__ __forceinline__ uint32_t cp_load(const uint32_t* __restrict__ tok0, c
 // allow it; the helper of the look-back must not cost the main path its occupancy)
 // (Session Q also ran a shape with the rows of a chunk gathered a chunk ahead -- issued at the top of an iteration for the chunk after
 // next, settled at the top of the next one, 94 VGPRs: level, 0.1266 against 0.1250 ms -- the front's round trip is not what a chunk waits for.)
-// EARLY: the look-back's first read -- the 128 chunks in front -- goes out at the TOP of the iteration and is looked at behind front()
-// of the next chunk (results.hip lb_prefetch / lb_resolve_pre).
+// EARLY: the first read of the totals in front of a chunk goes out at the TOP of the iteration and is looked at behind front()
+// of the next chunk (results.hip lb_prefetch / lb_resolve).
 template <int CP_ITEMS, bool PROF = false, bool EARLY = true>
 __global__ __launch_bounds__(CP_NT, CP_ITEMS == 8 ? 2 : 5) void k_compact(const uint32_t* __restrict__ tok0, const uint4* __restrict__ rows, const uint4* __restrict__ crows,
                                                    const uint32_t* __restrict__ tmp_ids, const int64_t* __restrict__ n_pretok,
@@ -167,11 +167,17 @@ __global__ __launch_bounds__(CP_NT, CP_ITEMS == 8 ? 2 : 5) void k_compact(const 
                                                    uint8_t* __restrict__ tok_b8) {
     // tok_b8 (with offsets only, else null): per token, the boundary byte in front of it that its row carried (results.hip row_boundary)
     constexpr int CP_CHUNK = CpShape<CP_ITEMS>::CHUNK, CP_STAGE = CpShape<CP_ITEMS>::STAGE;
-    unsigned long long ph_t = 0ull, ph_t0 = 0ull, ph_acc[4] = {0ull, 0ull, 0ull, 0ull};
+    // (the phase sums and the first stamp [4] live in LDS: five 64-bit values in registers, live across the whole loop in every lane,
+    // spilled the diagnostic instantiation)
+    __shared__ unsigned long long s_ph[PROF ? 5 : 1];
+    unsigned long long ph_t = 0ull;
     auto tick = [&](int k) {
-        if (PROF && threadIdx.x == 0) { const unsigned long long now = __builtin_amdgcn_s_memtime(); ph_acc[k] += now - ph_t; ph_t = now; }
+        if (PROF && threadIdx.x == 0) { const unsigned long long now = __builtin_amdgcn_s_memtime(); s_ph[k] += now - ph_t; ph_t = now; }
     };
-    if (PROF && threadIdx.x == 0) ph_t = ph_t0 = __builtin_amdgcn_s_memtime();
+    if (PROF && threadIdx.x == 0) {
+        for (int k = 0; k < 4; ++k) s_ph[k] = 0ull;
+        s_ph[4] = ph_t = __builtin_amdgcn_s_memtime();
+    }
     __shared__ uint32_t sm[4];
     __shared__ uint32_t s_dlo[2], s_dhi[2];              // documents [dlo, dhi) start in the chunk
     __shared__ uint32_t s_docpt[2][CP_NT];               // doc_pt of the first CP_NT of them, loaded with the chunk
@@ -182,6 +188,7 @@ __global__ __launch_bounds__(CP_NT, CP_ITEMS == 8 ? 2 : 5) void k_compact(const 
     const int64_t P = uniform_i64(*n_pretok);           // (scalar registers: the chunk count and every chunk's bounds follow it)
     const int64_t n_chunks = (P + CP_CHUNK - 1) / CP_CHUNK;
     const int tid = (int)threadIdx.x;
+    unsigned long long* const groups = lb_groups(state, n_chunks);     // the totals of 64 chunks in one word (results.hip)
     if (n_chunks == 0) {                                  // no pre-token at all: every document is empty
         if (blockIdx.x == 0)
             for (int64_t d = tid; d <= n_docs; d += CP_NT) tok_offsets[d] = 0;
@@ -203,7 +210,7 @@ __global__ __launch_bounds__(CP_NT, CP_ITEMS == 8 ? 2 : 5) void k_compact(const 
         if (has_doc) my_docpt = doc_pt[dlo + (uint32_t)tid];
         uint32_t tot;
         const uint32_t ex = block256_excl_scan(v, sm, &tot);
-        if (tid == 0) { lb_publish(state, ch, (unsigned long long)tot); s_tot[b] = tot; }
+        if (tid == 0) { lb_publish(state, groups, ch, (unsigned long long)tot); s_tot[b] = tot; }
         if (has_doc) s_docpt[b][tid] = my_docpt;
         if (tid == 0) { s_dlo[b] = dlo; s_dhi[b] = dhi; }
         tick(0);
@@ -248,32 +255,36 @@ __global__ __launch_bounds__(CP_NT, CP_ITEMS == 8 ? 2 : 5) void k_compact(const 
         ahead_of((int64_t)blockIdx.x + gridDim.x, aa);
         if ((int64_t)blockIdx.x < n_chunks) front(blockIdx.x, 0, a0);
     }
+    unsigned long long carry = 0ull;                       // tokens up to and including this workgroup's previous chunk
     for (int64_t ch = blockIdx.x; ch < n_chunks; ch += gridDim.x, b ^= 1) {
         const int64_t nxt = ch + gridDim.x;
-        // EARLY: wavefront 0 asks for the states of the 128 chunks in front of `ch` NOW and looks at them behind front(nxt).  Every
-        // workgroup's look-back finds its predecessors' prefixes just in time -- the workgroups fell into step at the kernel's start, 64
-        // of them a round trip behind the 64 before -- so the read that starts when back() starts always costs its whole round trip
-        // (31..36 % of the kernel, three wavefronts at a barrier meanwhile); the prefixes some 64 to 128 chunks back are older:
-        // a read two windows wide often finds one of them, every total in between has long been published, and the answer is there when
-        // front(nxt) is done (compact 0.1245 -> 0.115 ms at C2, profiles/r5r_*, r5t_*).  What it does not settle, lb_resolve_pre goes on polling for like lb_resolve.
+        const int64_t prev = ch == (int64_t)blockIdx.x ? -1 : ch - (int64_t)gridDim.x;
+        // The chunk's place in the token stream is `carry` + the totals of the chunks between this workgroup's previous chunk and this one
+        // (results.hip): totals that other workgroups' front() published about an iteration ago, read through the group words -- no
+        // workgroup waits for another one's look-back.  (Rounds 4 to 6 walked back to the nearest published PREFIX instead, which only
+        // exists once its chunk has itself resolved: the workgroups fell into step, 64 of them a round trip behind the 64 before, and
+        // every look-back found its prefix just in time -- 31..36 % of the kernel, three wavefronts at a barrier meanwhile.)
+        // EARLY: wavefront 0 asks for them NOW, three loads a lane, and looks at them behind front(nxt); what they do not settle
+        // lb_resolve reads again.
         // (behind ahead_of: the compiler drains every memory operation of the last iteration in there -- the registers of `an` are the
         // loop's own -- and a read issued in front of that would be waited for at once; from here it returns with front(nxt)'s gathers)
         LbPre pre;
         CpAhead<CP_ITEMS> an;                              // ... and those of the one after it: in flight while front(nxt) works
         ahead_of(nxt + gridDim.x, an);
-        if (EARLY && tid < 64) lb_prefetch(state, ch, pre);
+        if (EARLY && tid < 64) lb_prefetch(state, groups, prev, ch, pre);
         if (nxt < n_chunks) front(nxt, b ^ 1, aa);        // (its two barriers also order this chunk's LDS writes before the reads below)
         else __syncthreads();
         aa = an;
         const uint32_t tot = s_tot[b];
-        // the chunk's place in the token stream: wavefront 0 looks back (results.hip), the others wait at the barrier
+        // wavefront 0 adds the totals up (results.hip), the others wait at the barrier
         if (tid < 64) {
-            const unsigned long long r = EARLY ? lb_resolve_pre(state, ch, (unsigned long long)tot, patience, chunk_total, pre)
-                                               : lb_resolve(state, ch, (unsigned long long)tot, patience, chunk_total);
+            if (!EARLY) lb_prefetch(state, groups, prev, ch, pre);
+            const unsigned long long r = carry + lb_resolve(state, groups, prev, ch, patience, chunk_total, pre);
             if (tid == 0) s_lbw = r;
         }
         __syncthreads();
         const unsigned long long base = s_lbw;
+        carry = (unsigned long long)uniform_i64((int64_t)(base + tot));
         tick(2);
         if (ch == n_chunks - 1 && tid == 0) *n_tok = (int64_t)(base + tot);
         const int64_t pc = ch * CP_CHUNK;
@@ -320,8 +331,8 @@ __global__ __launch_bounds__(CP_NT, CP_ITEMS == 8 ? 2 : 5) void k_compact(const 
     }
     if (PROF && tid == 0 && phases) {
         unsigned long long* const o = phases + (size_t)blockIdx.x * 8;
-        for (int k = 0; k < 4; ++k) o[k] += ph_acc[k];
-        o[7] += ph_t - ph_t0;
+        for (int k = 0; k < 4; ++k) o[k] += s_ph[k];
+        o[7] += ph_t - s_ph[4];
     }
 }
 #undef TKAMD_CP_SCATTER

@@ -98,15 +98,29 @@ __device__ __forceinline__ uint4 make_row(uint32_t count, uint32_t s, uint32_t i
 }
 
 // =================================================================================================
-// Single-pass prefix sums (decoupled look-back): chunk c publishes its own total as soon as it knows it, then adds up the
-// published totals of its predecessors until it meets one that already carries a full prefix.  One 64-bit word per chunk
-// holds the state and the value together, so a reader never sees one without the other; all accesses are device-scope
-// atomics (the L2 of one XCD is not coherent with the others').  A wait never depends on another workgroup being scheduled: a
-// chunk's total is a pure function of data that is final before the kernel starts, so a wavefront that has polled an unpublished
-// predecessor `patience` times computes that total itself (`help`) and publishes it on the owner's behalf -- compare-and-swap from
-// "nothing", so an owner that got there first wins, and either way the word holds the same value.
+// Single-pass prefix sums from published TOTALS: chunk c publishes its own total as soon as it knows it; whoever needs the sum of a
+// range of chunks adds up their published totals.  Nothing else is ever published -- no inclusive prefix that only exists once its
+// chunk has itself resolved, so no chain of device-scope round trips down the chunks (rounds 3 to 6 walked back to the nearest such
+// prefix: HISTORY.md).  A workgroup that takes the chunks c, c + G, c + 2G, ... in order carries its own inclusive prefix forward:
+//   base(c + G) = incl(c) + sum of total(j), c < j < c + G,
+// every term of which a front() published long before it is asked for.
+// Two kinds of word, all accesses device-scope atomics (the L2 of one XCD is not coherent with the others'):
+//   state[c]     LB_AGG | total of chunk c; 0 = not yet published.  State and value in ONE word: a reader never sees one without the other.
+//   group word g (lb_group_word) count << 56 | sum of the totals of the chunks [64 g, 64 g + 64) whose OWNERS have published.  A reader
+//                takes it only when the count is 64 (the whole group in one load: G - 1 totals are G / 64 of these and two partial
+//                windows of state[] -- three loads a lane at any grid up to 4,096); otherwise it reads the group's 64 state words.
+// A wait never depends on another workgroup being scheduled: a chunk's total is a pure function of data that is final before the
+// kernel starts, so a wavefront that has polled an unpublished total `patience` times computes it itself (`help`) and publishes it on
+// the owner's behalf -- into state[] ALONE, by compare-and-swap from "nothing", so an owner that got there first wins, and either way
+// the word holds the same value.  Only owners add to a group word: it is never counted twice.
+// The group words are LB_GROUP_STRIDE words apart (kernels.hpp): device-scope atomics execute at the memory side, those on one 64-byte
+// block one after the other (~11 ns each, MI355X), and the ~20 groups in flight at once take 18 k adds a C2 batch between them.
+// (Measured: the words packed eight to a block, k_compact 0.315 ms at C2 against 0.0915 -- profiles/compact_carry_ab_c2.txt.)
 // =================================================================================================
-constexpr unsigned long long LB_AGG = 1ull << 62, LB_PREFIX = 2ull << 62, LB_FLAGS = 3ull << 62, LB_VALUE = ~LB_FLAGS;
+constexpr unsigned long long LB_AGG = 1ull << 62, LB_VALUE = LB_AGG - 1ull;
+constexpr int LB_GCOUNT_SHIFT = 56;                 // a group's sum stays below 2^40: 64 totals of less than 2^32
+constexpr unsigned long long LB_GSUM = (1ull << LB_GCOUNT_SHIFT) - 1ull;
+static_assert(LB_GROUP_CHUNKS == 64, "one wavefront-wide load reads a group's states");
 
 __device__ __forceinline__ void lb_store(unsigned long long* p, unsigned long long v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -114,111 +128,96 @@ __device__ __forceinline__ void lb_store(unsigned long long* p, unsigned long lo
 __device__ __forceinline__ unsigned long long lb_load(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// Two halves, so that a workgroup can publish a chunk's total early and come back for its prefix after other work:
-//   lb_publish(state, ch, total)   one lane: total of chunk ch is known
-//   lb_resolve(state, ch, total, patience, help)
-//                                  ONE whole wavefront: returns, in every lane, the sum of all chunks before `ch`, and publishes the
-//                                  inclusive prefix of `ch`.  help(c): called by the whole wavefront, returns chunk c's total in every lane.
-__device__ __forceinline__ void lb_publish(unsigned long long* __restrict__ state, int64_t ch, unsigned long long total) {
-    lb_store(&state[ch], (ch == 0 ? LB_PREFIX : LB_AGG) | total);
+// the group words of a batch of n_chunks chunks: behind its state words, in the same allocation (the host sizes and zeroes both: lb_state_words)
+__device__ __forceinline__ unsigned long long* lb_groups(unsigned long long* state, int64_t n_chunks) { return state + lb_group_base((size_t)n_chunks); }
+__device__ __forceinline__ unsigned long long* lb_group_word(unsigned long long* groups, int64_t g) { return groups + g * LB_GROUP_STRIDE; }
+// Two halves, so that a workgroup can publish a chunk's total early and come back for its place after other work:
+//   lb_publish(state, groups, ch, total)   one lane, the chunk's OWNER: total of chunk ch is known
+//   lb_resolve(state, groups, prev, ch, patience, help, pre)
+//                                  ONE whole wavefront: returns, in every lane, the sum of the totals of the chunks prev < j < ch (prev = -1:
+//                                  of all chunks before ch).  help(c): called by the whole wavefront, returns chunk c's total in every lane.
+__device__ __forceinline__ void lb_publish(unsigned long long* __restrict__ state, unsigned long long* __restrict__ groups, int64_t ch, unsigned long long total) {
+    lb_store(&state[ch], LB_AGG | total);
+    atomicAdd(lb_group_word(groups, ch / LB_GROUP_CHUNKS), (1ull << LB_GCOUNT_SHIFT) | total);      // (result unused: a no-return add, nobody waits for it)
 }
-constexpr uint32_t LB_PATIENCE = 1024;              // polls of an unpublished predecessor before its total is computed here (about half a millisecond; TKAMD_LB_PATIENCE)
-// (lb_resolve_from: the walk from chunk i downwards with `run` already summed -- lb_resolve starts it at ch - 1 with nothing)
-template <class Help>
-__device__ __forceinline__ unsigned long long lb_resolve_from(unsigned long long* __restrict__ state, int64_t ch, int64_t i, unsigned long long run, unsigned long long total,
-                                                              uint32_t patience, Help&& help) {
-    const int lane = lane_id();
-    uint32_t polls = 0u;
-    while (true) {
-        const int64_t idx = i - lane;
-        unsigned long long st;
-        uint64_t empty, pref;
-        do {                                                        // wait until the window holds no unpublished chunk in front of the first full prefix
-            st = idx >= 0 ? lb_load(&state[idx]) : LB_PREFIX;
-            empty = __ballot((st & LB_FLAGS) == 0ull);
-            pref = __ballot((st & LB_FLAGS) == LB_PREFIX);
-            if (pref) {
-                const int first = __ffsll((unsigned long long)pref) - 1;          // nearest predecessor with a full prefix
-                empty &= (first >= 63) ? ~0ull : ((2ull << first) - 1ull);
-            }
-            if (empty && ++polls > patience) {                      // (wavefront-uniform) out of patience: one of the missing totals is computed here
-                // (different workgroups pick different ones; having helped once, this wait goes on helping without the long pause)
-                int k = (int)((blockIdx.x + polls) % (uint32_t)__popcll((unsigned long long)empty));
-                uint64_t e = empty;
-                for (; k > 0; --k) e &= e - 1ull;
-                const int64_t hc = i - (int64_t)(__ffsll((unsigned long long)e) - 1);
-                const unsigned long long t = help(hc);
-                if (lane == 0) atomicCAS(&state[hc], 0ull, (hc == 0 ? LB_PREFIX : LB_AGG) | t);
-                patience = 8u;
-                polls = 0u;
-            }
-        } while (empty);
-        const int first = pref ? __ffsll((unsigned long long)pref) - 1 : 63;
-        unsigned long long v = (lane <= first) ? (st & LB_VALUE) : 0ull;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-        run += v;
-        if (pref) break;
-        i -= 64;
-    }
-    if (lane == 0) lb_store(&state[ch], LB_PREFIX | (run + total));
-    return run;
-}
-template <class Help>
-__device__ __forceinline__ unsigned long long lb_resolve(unsigned long long* __restrict__ state, int64_t ch, unsigned long long total, uint32_t patience, Help&& help) {
-    if (ch == 0) return 0ull;
-    return lb_resolve_from(state, ch, ch - 1, 0ull, total, patience, help);
-}
+constexpr uint32_t LB_PATIENCE = 1024;              // polls of an unpublished total before it is computed here (about half a millisecond; TKAMD_LB_PATIENCE)
 
-// The same look-back with its first read taken EARLY: lb_prefetch asks for the states of the LB_PRE_W * 64 = 128 chunks in front of `ch` (one
-// load per window and lane, all in flight together, no wait), lb_resolve_pre looks at them -- window by window, nearest first -- and
-// returns at the first full prefix if every chunk in front of it had published; anything else (an unpublished chunk, no prefix in
-// reach) goes on from there through lb_resolve's own loop, fresh reads and helping included.  A state word only ever goes from
-// nothing to a total to a prefix, so a value read early is still true when it is used.
-// (How wide: sessions S / T, profiles/r5s_*, r5t_*: two, three and four windows level -- compact 0.1152 .. 0.1178 ms against 0.1245 without
-// the early read --, eight windows slower than none, 0.1375: eight device-scope loads a chunk are traffic of their own.)
-constexpr int LB_PRE_W = 2;
-struct LbPre { unsigned long long st[LB_PRE_W]; };
-__device__ __forceinline__ void lb_prefetch(const unsigned long long* __restrict__ state, int64_t ch, LbPre& p) {
+// The range (prev, ch) cut at the multiples of 64: a partial group at the front [lo, fe), whole groups [gl, gh), a partial group at the
+// back [64 gh, hi).  (No multiple of 64 inside the range: everything is "front".)
+struct LbCut { int64_t lo, fe, gl, gh, hi; };
+__device__ __forceinline__ LbCut lb_cut(int64_t prev, int64_t ch) {
+    LbCut c;
+    c.lo = prev + 1;
+    c.hi = ch;
+    c.gl = (c.lo + LB_GROUP_CHUNKS - 1) / LB_GROUP_CHUNKS;
+    c.gh = max(ch / LB_GROUP_CHUNKS, c.gl);
+    c.fe = min(c.gl * LB_GROUP_CHUNKS, ch);
+    return c;
+}
+// The first read of all three parts, taken EARLY: one load per part and lane, all in flight together, no wait -- the front window upwards
+// from lo, the first 64 group words, the back window downwards from hi - 1.  A state word goes from nothing to a total and never changes
+// after that, and a group word is used only when its count is 64 -- complete, it never changes again either --, so a value read early is
+// still true when it is used; what the early read does not settle, lb_resolve reads again fresh.
+// (How wide an early read may be: sessions S / T, profiles/r5s_*, r5t_*, on the look-back of rounds 4 to 6: two, three and four loads a
+// lane level, eight slower than none -- eight device-scope loads a chunk are traffic of their own.)
+struct LbPre { unsigned long long a, g, b; };
+__device__ __forceinline__ void lb_prefetch(unsigned long long* __restrict__ state, unsigned long long* __restrict__ groups, int64_t prev, int64_t ch, LbPre& p) {
     const int lane = lane_id();
-#pragma unroll
-    for (int r = 0; r < LB_PRE_W; ++r) {
-        const int64_t idx = ch - 1 - 64 * r - lane;
-        p.st[r] = idx >= 0 ? lb_load(&state[idx]) : LB_PREFIX;
+    const LbCut c = lb_cut(prev, ch);
+    p.a = c.lo + lane < c.fe ? lb_load(&state[c.lo + lane]) : 0ull;
+    p.g = c.gl + lane < c.gh ? lb_load(lb_group_word(groups, c.gl + lane)) : 0ull;
+    p.b = c.hi - 1 - lane >= c.gh * LB_GROUP_CHUNKS ? lb_load(&state[c.hi - 1 - lane]) : 0ull;
+}
+// One window of up to 64 state words -- lane l: chunk first + step * l, l < n; `st`: that word as last read (0: not published then).
+// Returns the lane's total once every chunk of the window has one: polls the missing ones, and out of patience computes one of them here.
+struct LbWait { uint32_t patience, polls; };
+template <class Help>
+__device__ __forceinline__ unsigned long long lb_window(unsigned long long* __restrict__ state, int64_t first, int step, int n, unsigned long long st, LbWait& w, Help&& help) {
+    const int lane = lane_id();
+    const bool want = lane < n;
+    const int64_t idx = first + (int64_t)step * lane;
+    uint64_t empty;
+    while ((empty = __ballot(want && st == 0ull)) != 0ull) {
+        if (++w.polls > w.patience) {                               // (wavefront-uniform) out of patience: one of the missing totals is computed here
+            // (different workgroups pick different ones; having helped once, this look-back goes on helping without the long pause)
+            int k = (int)((blockIdx.x + w.polls) % (uint32_t)__popcll((unsigned long long)empty));
+            uint64_t e = empty;
+            for (; k > 0; --k) e &= e - 1ull;
+            const int64_t hc = first + (int64_t)step * (__ffsll((unsigned long long)e) - 1);
+            const unsigned long long t = help(hc);
+            if (lane == 0) atomicCAS(&state[hc], 0ull, LB_AGG | t);
+            w.patience = 8u;
+            w.polls = 0u;
+        }
+        if (want && st == 0ull) st = lb_load(&state[idx]);
     }
+    return want ? (st & LB_VALUE) : 0ull;
 }
 template <class Help>
-__device__ __forceinline__ unsigned long long lb_resolve_pre(unsigned long long* __restrict__ state, int64_t ch, unsigned long long total, uint32_t patience, Help&& help,
-                                                             const LbPre& p) {
+__device__ __forceinline__ unsigned long long lb_resolve(unsigned long long* __restrict__ state, unsigned long long* __restrict__ groups, int64_t prev, int64_t ch,
+                                                         uint32_t patience, Help&& help, const LbPre& p) {
     const int lane = lane_id();
-    if (ch == 0) return 0ull;
-    // every window's share of this lane first, ONE sum over the lanes behind them (the branches are wavefront-uniform)
-    unsigned long long acc = 0ull;
-    bool done = false;
-    int used = 0;                                                   // windows taken whole (or up to their first full prefix)
-#pragma unroll
-    for (int r = 0; r < LB_PRE_W; ++r) {
-        if (!done && used == r) {
-            const unsigned long long st = p.st[r];
-            uint64_t empty = __ballot((st & LB_FLAGS) == 0ull);
-            const uint64_t pref = __ballot((st & LB_FLAGS) == LB_PREFIX);
-            const int first = pref ? __ffsll((unsigned long long)pref) - 1 : 63;
-            if (pref) empty &= (first >= 63) ? ~0ull : ((2ull << first) - 1ull);
-            if (!empty) {                                           // (an unpublished chunk in front of the prefix: fresh reads from this window on)
-                acc += (lane <= first) ? (st & LB_VALUE) : 0ull;
-                used = r + 1;
-                done = pref != 0ull;
-            }
+    const LbCut c = lb_cut(prev, ch);
+    LbWait w{patience, 0u};
+    // every part's share of this lane first, ONE sum over the lanes behind them (the branches are wavefront-uniform)
+    unsigned long long acc = lb_window(state, c.lo, 1, (int)(c.fe - c.lo), p.a, w, help);
+    acc += lb_window(state, c.hi - 1, -1, (int)(c.hi - c.gh * LB_GROUP_CHUNKS), p.b, w, help);
+    for (int64_t g0 = c.gl; g0 < c.gh; g0 += 64) {                  // (one round up to a grid of 4,096; the early read is the first round's)
+        const bool want = g0 + lane < c.gh;
+        unsigned long long gw = g0 == c.gl ? p.g : 0ull;
+        if (want && (gw >> LB_GCOUNT_SHIFT) != (unsigned long long)LB_GROUP_CHUNKS) gw = lb_load(lb_group_word(groups, g0 + lane));      // not complete when read early: once more, fresh
+        const bool whole = (gw >> LB_GCOUNT_SHIFT) == (unsigned long long)LB_GROUP_CHUNKS;
+        acc += want && whole ? (gw & LB_GSUM) : 0ull;
+        // still short of an owner (or it never will be complete in time: its owners are not resident): the group's 64 state words, helpers' included
+        for (uint64_t m = __ballot(want && !whole); m; m &= m - 1ull) {
+            const int64_t gx = g0 + (__ffsll((unsigned long long)m) - 1);
+            const unsigned long long st = lb_load(&state[gx * LB_GROUP_CHUNKS + lane]);
+            acc += lb_window(state, gx * LB_GROUP_CHUNKS, 1, LB_GROUP_CHUNKS, st, w, help);
         }
     }
-    unsigned long long run = acc;
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) run += __shfl_xor(run, d, 64);
-    if (done) {
-        if (lane == 0) lb_store(&state[ch], LB_PREFIX | (run + total));
-        return run;
-    }
-    return lb_resolve_from(state, ch, ch - 1 - 64 * (int64_t)used, run, total, patience, help);
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    return acc;
 }
 
 // (Round 4 also tried the look-back by the whole 256-lane workgroup, four windows of 64 predecessors a round: two barriers a round
