@@ -102,7 +102,8 @@ typedef struct tkamd_info {
                                4 WhitespaceSplit, 5 BertPreTokenizer, 6 ByteLevel(use_regex=false), 7 the U+2581 front of SentencePiece-style BPE,
                                8 the chain of three Splits of DeepSeek-V3 / R1 + ByteLevel(use_regex=false),
                                9 Sequence[Digits, ByteLevel(GPT-2 regex)]: StarCoder / StarCoder2 / SantaCoder, Granite code, Command-R */
-    int32_t normalizer;     /* 0 none, 1 BertNormalizer                                         */
+    int32_t normalizer;     /* 0 none, 1 BertNormalizer, 2 the U+2581 normalizers, 3 NFC, 4 Precompiled,
+                               5 NFD / Lowercase / StripAccents, alone or chained in a Sequence */
     int32_t vocab_size;
     int32_t n_merges;
     int32_t add_prefix_space;
@@ -335,6 +336,10 @@ int tkamd_probe_bert_norm(const tkamd_tokenizer* tok, uint32_t cp, uint32_t* out
  * src[k] the first byte of the source char that byte k is aligned to (the chars the reference loses at a piece's start included).
  * cap: what out and src hold; *n_out is set even when it is too small (TKAMD_ERR_INVALID then). */
 int tkamd_probe_precompiled(const tkamd_tokenizer* tok, const uint8_t* text, int64_t n, uint8_t* out, uint32_t* src, int64_t cap, int64_t* n_out);
+/* A chain of NFD / Lowercase / StripAccents (info.normalizer == 5) over ONE piece -- text[0 .. n) -- by the host run of what the kernels
+ * read, the per-char expansions composed at load: out[0 .. *n_out) the normalized bytes, src[k] the first byte of the source char
+ * that byte k is aligned to.  cap: what out and src hold; *n_out is set even when it is too small (TKAMD_ERR_INVALID then). */
+int tkamd_probe_norm_chain(const tkamd_tokenizer* tok, const uint8_t* text, int64_t n, uint8_t* out, uint32_t* src, int64_t cap, int64_t* n_out);
 /* BertNormalizer strip_accents on the character whose lead byte is text[pos] (text[0 .. n) = one piece handed to the normalizer: a
  * document, or what lies between two added-token matches): *reorder = 1 if it survives the Mn filter with a non-zero combining
  * class (NFD's canonical ordering could move it), *alone = 1 if it is alone in its run of non-starters -- nothing moves; 0: the

@@ -174,12 +174,13 @@ void Batch::check_request() {
             nfc_general = p > 0;
         }
     }
+    if (hm.nfd_mode()) nfc_general = true;          // (a chain that leaves NFD in the text: the normalizer's kernels for every batch, no quick check)
     // (Precompiled: a source byte stands for at most pc_growth output bytes, found at load; the "▁" front then reads that text)
     precomp = hm.norm == NORM_PRECOMPILED;
     n_p = precomp ? (int64_t)hm.pc_growth * n_bytes + 64 : n_bytes;
     // (behind the normalizer only: every other tokenizer's text is bounded by the check of n_x below, as before)
     if (precomp && n_p >= (int64_t)0x55555500ll) throw Invalid("batch larger than 4 GiB behind the normalizer's bound: split it (byte offsets are 32-bit on the device)");
-    n_x = (hm.norm == NORM_BERT || nfc_general) ? 3 * n_bytes + 64
+    n_x = (hm.norm == NORM_BERT || hm.norm == NORM_CHAIN || nfc_general) ? 3 * n_bytes + 64
           : metaspace ? 3 * n_p + 3 * (n_docs + 2 * (int64_t)mcap + 1) + 64
           : n_bytes + (prefix_space ? n_docs + (int64_t)mcap : 0);
     if (n_x >= (int64_t)0xFFFFFF00ll) throw Invalid("batch larger than 4 GiB: split it (byte offsets are 32-bit on the device)");
@@ -241,7 +242,7 @@ void Batch::zero_batch_state() {
     // (behind BertNormalizer the mask covers the bound of the normalised text, three times the input: the words that text really has
     // are zeroed behind the normaliser, next to the slack of the text -- launch_zero_tail below)
     // (behind NFC's general path the whole bound is zeroed all the same: the byte-level pre-tokenizers walk the mask words of the bound, and that path is the rare one)
-    if (!(hm.norm == NORM_BERT || metaspace)) z.add(w->w_docmask.p, (size_t)(W + 1) * 8);
+    if (!(hm.norm == NORM_BERT || (hm.norm == NORM_CHAIN && !hm.nfd_mode()) || metaspace)) z.add(w->w_docmask.p, (size_t)(W + 1) * 8);
     z.add(w->w_qcount.p, (size_t)QCNT_WORDS * 4);
     z.add(w->w_cstate.p, cstate_bytes);
     if (hm.pretok == PT_LLAMA3 && split_rule_fast(hm.split_rule)) {
@@ -374,6 +375,8 @@ void Batch::normalize_bert() {
     w->w_wbase.reserve((size_t)(W0 + 1) * 4);
     BnTables bt{t->t_bn1.as<uint16_t>(), t->t_bn2.as<uint8_t>(), t->t_bn_map.as<MergeSlot>(), hm.bn_mask, hm.bn_seed,
                 hm.bn_clean_text, hm.bn_handle_chinese, hm.bn_strip_accents, hm.bn_lowercase};
+    // (a chain of NFD / Lowercase / StripAccents: the same kernels over the chain's own tables, none of the BertNormalizer's steps)
+    if (hm.norm == NORM_CHAIN) { bt.clean = bt.cjk = bt.strip = bt.lower = 0u; bt.chain = 1u | (hm.chain_has(CHAIN_LOWERCASE) ? 2u : 0u); }
     const ull* verbatim = nullptr;
     if (have_raw) {
         scatter_masks(n_bytes, nullptr, false);
@@ -406,7 +409,11 @@ void Batch::normalize_nfc() {
         verbatim = w->w_boundmask.as<ull>();
         launch_nfc_bound(st, w->w_ms_dmask.as<ull>(), verbatim, W0 + 1);
     }
-    const NfcTables nt{t->t_nfc1.as<uint16_t>(), t->t_nfc2.as<uint8_t>(), t->t_nfc_map.as<MergeSlot>(), hm.nfc_mask, hm.nfc_seed};
+    NfcTables nt{t->t_nfc1.as<uint16_t>(), t->t_nfc2.as<uint8_t>(), t->t_nfc_map.as<MergeSlot>(), hm.nfc_mask, hm.nfc_seed};
+    if ((nt.mode = hm.nfd_mode()) & NFD_LOWER) {        // (to_lowercase rides in the BertNormalizer tables' place)
+        nt.l1 = t->t_bn1.as<uint16_t>(); nt.l2 = t->t_bn2.as<uint8_t>(); nt.lmap = t->t_bn_map.as<MergeSlot>();
+        nt.lmap_mask = hm.bn_mask; nt.lmap_seed = hm.bn_seed;
+    }
     pf.begin("nfc_normalize");
     launch_nfc_normalize(st, nt, d_text, n_bytes, d_doc_off, n_docs, verbatim, w->w_ms_dmask.as<ull>(), w->w_keepmask.as<uint8_t>(), w->w_kprefix.as<uint32_t>(),
                          w->w_bsum.as<uint32_t>(), w->w_wbase.as<uint32_t>(), d_xlen, w->w_ntext.as<uint8_t>(), (uint32_t*)norig, w->w_ndoc_off.as<int64_t>(), d_err);
@@ -573,7 +580,7 @@ void Batch::build_x_text() {
     }
     x_text = d_text;
     x_doc_off = d_doc_off;
-    const bool normalized = hm.norm == NORM_BERT || nfc_general;      // X is a normaliser's output (the BnOlen layout, norig without ends)
+    const bool normalized = hm.norm == NORM_BERT || hm.norm == NORM_CHAIN || nfc_general;      // X is a normaliser's output (the BnOlen layout, norig without ends)
     if (normalized || prefix_space || metaspace) {
         w->w_ntext.reserve((size_t)n_x + TKAMD_TEXT_PAD);
         w->w_ndoc_off.reserve((size_t)(n_docs + 2) * 8);
@@ -603,7 +610,8 @@ void Batch::build_x_text() {
             }
         }
     }
-    if (hm.norm == NORM_BERT) normalize_bert();
+    if (hm.norm == NORM_BERT || (hm.norm == NORM_CHAIN && !hm.nfd_mode())) normalize_bert();
+    if (hm.nfd_mode()) normalize_nfc();
     if (hm.norm == NORM_NFC) {
         if (nfc_general) normalize_nfc();
         else {
@@ -1136,7 +1144,7 @@ int error_from_bits(int bits) {
                                                 "on the device");
     if (bits & ERR_NFC_SEGMENT)
         return set_error(TKAMD_ERR_UNSUPPORTED, "NFC: a character is followed by more than 48 combining characters (or other characters that may compose with it); "
-                                                "the normalization of such a run is not built on the device");
+                                                "the normalization of such a run (NFC, or the NFD of a normalizer chain) is not built on the device");
     if (bits & ERR_ADDED_SPLIT) return set_error(TKAMD_ERR_INVALID, "AddedVocabulary bad split");
     if (bits & ERR_INTERNAL) return set_error(TKAMD_ERR_DEVICE, "internal invariant violated");
     if (bits & ERR_QUEUE_FULL) return set_error(TKAMD_ERR_DEVICE, "work queues still too small after growing them");

@@ -91,6 +91,9 @@ const UcRun kUcCaseRuns[] = {      // (flags: UCC_UPPER / UCC_LOWER, tables.hpp)
 const UcRun kUcPsmRuns[] = {       // (flags: UC2_P / UC2_S / UC2_M / UC2_CJK, tables.hpp)
 #include "unicode_psm_ranges.inc"
 };
+const UcRun kUcMarkRuns[] = {      // (flags: 1 = StripAccents removes the char)
+#include "unicode_mark_ranges.inc"
+};
 const UcRun kUcNumericRuns[] = {   // (flags: UC_RUST_N, tables.hpp)
 #include "unicode_numeric_ranges.inc"
 };
@@ -370,6 +373,14 @@ void build_trie(HostModel& m, const std::vector<std::pair<std::string, uint32_t>
 
 void build_pair_table(const std::vector<MergeSlot>& items, std::vector<MergeSlot>* out, uint32_t* out_mask, uint32_t* out_seed);
 
+// the members a normalizer chain is made of (tables.hpp ChainMember); -1: not one of them
+int chain_member(const std::string& type) { return type == "NFD" ? CHAIN_NFD : type == "Lowercase" ? CHAIN_LOWERCASE : type == "StripAccents" ? CHAIN_STRIP_ACCENTS : -1; }
+// a chain that reads well but stands in front of something it is not built for: refused in the words the section was always refused by
+std::string chain_refusal(const HostModel& m, const std::string& what) {
+    return "normalizer: " + m.chain_spelling + " is outside the hot path in front of " + what + " (NFD / Lowercase / StripAccents are on it in front of WordPiece, "
+           "WordLevel and BPE over characters, behind Whitespace, WhitespaceSplit or BertPreTokenizer)";
+}
+
 // BertNormalizer data: flags as a 2-stage table, the NFD+strip (kind 0) and lowercase (kind 1) maps as one
 // cuckoo table keyed (cp, kind) with the up-to-3 output code points packed 21 bits each
 void build_bert_norm(HostModel& m) {
@@ -385,6 +396,59 @@ void build_bert_norm(HostModel& m) {
     for (const BnMapRow& r : kBnD) add(r, 0);
     for (const BnMapRow& r : kBnLC) add(r, 1);
     for (const BnNfdRow& r : kBnNFD) items.push_back(MergeSlot{r.cp, 2u, r.packed, 0u});      // kind 2: classes of the NFD pieces (bert_norm_core.hpp)
+    build_pair_table(items, &m.bn_map, &m.bn_mask, &m.bn_seed);
+}
+
+// NORM_CHAIN data: every member is a map of single chars (NFD: the full canonical decomposition, nfc_tables.inc; Lowercase:
+// char::to_lowercase, the kind-1 rows of bert_norm_tables.inc; StripAccents: drop the marks of unicode_mark_ranges.inc), and with
+// StripAccents behind NFD nothing NFD's canonical ordering could move is left (tools/gen_mark_tables.py asserts it of the wheel), so the
+// chain is the composition of its members per SOURCE char.  Composed here for every scalar: flag 1 on each char the chain changes, its
+// expansion (<= 3 code points, 0x1FFFFF-filled; none: the char disappears) in the cuckoo table under (cp, 0) -- the BertNormalizer's layout.
+void build_norm_chain(HostModel& m, const std::vector<uint8_t>& members) {
+    constexpr uint32_t FILL = 0x1FFFFFu, S_BASE = 0xAC00u, S_N = 11172u;
+    std::vector<uint8_t> prim(0x110000, 0);                   // 1 decomposes (table), 2 lowercases, 4 a mark
+    std::unordered_map<uint32_t, const NfcDecompRow*> dec;
+    std::unordered_map<uint32_t, const BnMapRow*> lc;
+    for (const NfcDecompRow& r : kNfcDecomp) { dec[r.cp] = &r; prim[r.cp] |= 1; }
+    for (const BnMapRow& r : kBnLC) { lc[r.cp] = &r; prim[r.cp] |= 2; }
+    for (const UcRun& r : kUcMarkRuns)
+        for (uint32_t cp = r.first; cp <= r.last; ++cp) prim[cp] |= 4;
+    std::vector<uint8_t> flat(0x110000, 0);
+    std::vector<MergeSlot> items;
+    std::vector<uint32_t> cur, nxt;
+    for (uint32_t cp = 0; cp < 0x110000u; ++cp) {
+        if (cp >= 0xD800u && cp < 0xE000u) continue;
+        if (!prim[cp] && !(cp - S_BASE < S_N)) continue;      // no member touches it
+        cur.assign(1, cp);
+        for (uint8_t member : members) {
+            nxt.clear();
+            for (uint32_t c : cur) {
+                if (member == CHAIN_NFD && c - S_BASE < S_N) {              // Hangul syllables: arithmetic
+                    const uint32_t s = c - S_BASE;
+                    nxt.push_back(0x1100u + s / 588u);
+                    nxt.push_back(0x1161u + (s % 588u) / 28u);
+                    if (s % 28u) nxt.push_back(0x11A7u + s % 28u);
+                } else if (member == CHAIN_NFD && (prim[c] & 1)) {
+                    for (uint32_t d : dec[c]->d) if (d != FILL) nxt.push_back(d);
+                } else if (member == CHAIN_LOWERCASE && (prim[c] & 2)) {
+                    const BnMapRow& r = *lc[c];
+                    for (uint32_t d : {r.a, r.b, r.c}) if (d != FILL) nxt.push_back(d);
+                } else if (member == CHAIN_STRIP_ACCENTS && (prim[c] & 4)) {
+                } else nxt.push_back(c);
+            }
+            cur.swap(nxt);
+        }
+        if (cur.size() == 1 && cur[0] == cp) continue;
+        uint32_t ob = 0;                                          // (the X text is bounded by three times the input, a lane's output by 7 bits)
+        for (uint32_t c : cur) ob += bn_core_utf8_len(c);
+        if (ob > 3u * bn_core_utf8_len(cp)) throw Invalid("normalizer chain: code point " + std::to_string(cp) + " grows more than three times in UTF-8");
+        if (cur.size() > 3) throw Invalid("normalizer chain: code point " + std::to_string(cp) + " expands to more than three code points");
+        cur.resize(3, FILL);
+        const uint64_t v = (uint64_t)cur[0] | ((uint64_t)cur[1] << 21) | ((uint64_t)cur[2] << 42);
+        items.push_back(MergeSlot{cp, 0u, (uint32_t)v, (uint32_t)(v >> 32)});
+        flat[cp] = 1;
+    }
+    two_stage(flat, &m.bn_stage1, &m.bn_stage2);
     build_pair_table(items, &m.bn_map, &m.bn_mask, &m.bn_seed);
 }
 
@@ -1225,6 +1289,25 @@ HostModel HostModel::from_json(const char* json, size_t len) {
             if (norm->get("normalizers")->arr.size() != 1)
                 throw Unsupported("normalizer: NFC inside a longer Sequence is outside the hot path (only NFC alone, or Sequence[NFC], is on it)");
             m.norm = NORM_NFC;
+        } else if (chain_member(t) >= 0 || (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() &&
+                                            std::any_of(norm->get("normalizers")->arr.begin(), norm->get("normalizers")->arr.end(),
+                                                        [](const JsonPtr& v) { return v && v->is_object() && chain_member(v->get_str("type")) >= 0; }))) {
+            // NFD, Lowercase, StripAccents: alone, or a Sequence of them.  What the file says is read here; whether it is on the path in
+            // front of this file's model and pre-tokenizer is decided below, once they are known, in the words this section was refused by
+            m.chain_spelling = t == "Sequence" ? "this Sequence" : "type '" + t + "'";
+            if (t == "Sequence") {
+                for (const JsonPtr& v : norm->get("normalizers")->arr) {
+                    const std::string mt = (v && v->is_object()) ? v->get_str("type") : "?";
+                    const int k = chain_member(mt);
+                    if (k < 0) throw Unsupported("normalizer: '" + mt + "' next to NFD / Lowercase / StripAccents in a Sequence is outside the hot path (only these three chain)");
+                    if (m.chain_has((uint8_t)k)) throw Unsupported("normalizer: '" + mt + "' twice in a Sequence is outside the hot path");
+                    if (k == CHAIN_NFD && m.chain_has(CHAIN_STRIP_ACCENTS))
+                        throw Unsupported("normalizer: 'StripAccents' in front of 'NFD' in a Sequence is outside the hot path (the marks NFD splits off afterwards stay, "
+                                          "in the order the text around them decides)");
+                    m.chain.push_back((uint8_t)k);
+                }
+            } else m.chain.push_back((uint8_t)chain_member(t));
+            m.norm = NORM_CHAIN;
         } else if (t == "Sequence" || t == "Replace" || t == "Prepend") {
             // the "▁" normalizers of SentencePiece conversions: Sequence[Prepend("▁"), Replace(" " -> "▁")] (Llama-2, Mistral) or
             // Replace(" " -> "▁") alone (Gemma-style); anything else of these types is outside the path
@@ -1253,6 +1336,11 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     }
 
     // ---- pre-tokenizer ----
+    if (m.norm == NORM_CHAIN) {                                        // (asked of the file before the pre-tokenizers' own refusals of a normalizer)
+        const JsonValue* pt = root->get("pre_tokenizer");
+        const std::string ptype = (pt && pt->is_object()) ? pt->get_str("type") : "null";
+        if (ptype != "Whitespace" && ptype != "WhitespaceSplit" && ptype != "BertPreTokenizer") throw Unsupported(chain_refusal(m, "pre_tokenizer '" + ptype + "'"));
+    }
     m.pretok = parse_pretok(root->get("pre_tokenizer"), m);
     if (m.pretok == PT_LLAMA3 && m.split_rule.letters == 2) {         // the case classes of the case-split letter alternatives
         std::vector<uint8_t> flat(0x110000, 0);
@@ -1712,6 +1800,8 @@ HostModel HostModel::from_json(const char* json, size_t len) {
                                                   m.pretok == PT_BYTELEVEL_NOREGEX)))
         throw Unsupported("normalizer: NFC is only on the path in front of byte-level BPE (ByteLevel, or a Split of the tiktoken family + ByteLevel); "
                           "in front of BPE over characters, WordPiece, WordLevel or the U+2581 front it is not");
+    if (m.norm == NORM_CHAIN && !(m.model == MODEL_WORDPIECE || m.model == MODEL_WORDLEVEL || (m.model == MODEL_BPE && m.char_bpe)))
+        throw Unsupported(chain_refusal(m, "this model"));
     // (the same refusal every encode call makes for any normalizer, made at load for this one: the file can never encode)
     if (m.norm == NORM_NFC && m.byte_level && m.add_prefix_space) throw Unsupported("ByteLevel add_prefix_space behind a normalizer (NFC)");
     if (m.norm == NORM_PRECOMPILED) {
@@ -1793,6 +1883,11 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     build_unicode(m);
     if (m.norm == NORM_BERT) build_bert_norm(m);
     if (m.norm == NORM_NFC) build_nfc_tables(m);
+    if (m.norm == NORM_CHAIN && !m.nfd_mode()) build_norm_chain(m, m.chain);
+    if (m.nfd_mode()) {                                      // (the NFC normalizer's tables, and to_lowercase alone in the chain's layout)
+        build_nfc_tables(m);
+        if (m.chain_has(CHAIN_LOWERCASE)) build_norm_chain(m, {CHAIN_LOWERCASE});
+    }
 
     // ---- AddedVocabulary pattern sets (needs the normalizer tables: normalized tokens match by their normalized form) ----
     {
@@ -1814,6 +1909,12 @@ HostModel HostModel::from_json(const char* json, size_t len) {
                 pat = m.bert_normalize(a.content, &refused);
                 if (refused) throw Unsupported("added token '" + a.content + "' holds a character whose NFD reordering is context dependent");
                 if (pat.empty()) continue;                         // normalizes to nothing: the automaton has nothing to match
+            }
+            if (a.normalized && m.norm == NORM_CHAIN) {
+                bool refused = false;
+                pat = m.chain_normalize(a.content, nullptr, &refused);
+                if (refused) throw Unsupported("added token '" + a.content + "' holds a run of more than 48 combining characters (NFD of such a run is not built)");
+                if (pat.empty()) continue;
             }
             if (a.normalized && m.norm == NORM_NFC) {
                 bool refused = false;
@@ -1882,6 +1983,46 @@ int HostModel::bn_expand_cp(uint32_t cp, uint32_t* out, int* refused) const {
     }
     if (cjk) out[k++] = ' ';
     return k;
+}
+
+int HostModel::chain_expand_cp(uint32_t cp, uint32_t* out) const {
+    if (!(bn_core_flags(bn_stage1.data(), bn_stage2.data(), cp) & 1u)) { out[0] = cp; return 1; }
+    const BnCoreTables ct{bn_stage1.data(), bn_stage2.data(), bn_map.data(), bn_mask, bn_seed, false};
+    uint32_t lo = 0, hi = 0;
+    if (!bn_core_map(ct, cp, 0u, &lo, &hi)) { out[0] = cp; return 1; }
+    const unsigned long long v = ((unsigned long long)hi << 32) | lo;
+    int k = 0;
+    for (int q = 0; q < 3; ++q) {
+        const uint32_t c = (uint32_t)((v >> (21 * q)) & 0x1FFFFFu);
+        if (c != 0x1FFFFFu) out[k++] = c;
+    }
+    return k;
+}
+
+std::string HostModel::chain_normalize(const std::string& s, std::vector<uint32_t>* norig, bool* refused) const {
+    if (nfd_mode()) return nfc_normalize(s, norig, refused);
+    std::string out;
+    int64_t i = 0;
+    const int64_t n = (int64_t)s.size();
+    while (i < n) {
+        uint32_t len;
+        const uint32_t cp = bn_core_decode((const uint8_t*)s.data(), i, n, &len);
+        uint32_t o[3];
+        const int k = ((uint8_t)s[i] & 0xC0u) == 0x80u ? 0 : chain_expand_cp(cp, o);      // (a stray continuation byte has no output, as in k_bn_count)
+        const size_t before = out.size();
+        for (int q = 0; q < k; ++q) {
+            uint8_t b[4];
+            const uint32_t c = o[q], l = bn_core_utf8_len(c);
+            if (l == 1u) b[0] = (uint8_t)c;
+            else if (l == 2u) { b[0] = (uint8_t)(0xC0u | (c >> 6)); b[1] = (uint8_t)(0x80u | (c & 0x3Fu)); }
+            else if (l == 3u) { b[0] = (uint8_t)(0xE0u | (c >> 12)); b[1] = (uint8_t)(0x80u | ((c >> 6) & 0x3Fu)); b[2] = (uint8_t)(0x80u | (c & 0x3Fu)); }
+            else { b[0] = (uint8_t)(0xF0u | (c >> 18)); b[1] = (uint8_t)(0x80u | ((c >> 12) & 0x3Fu)); b[2] = (uint8_t)(0x80u | ((c >> 6) & 0x3Fu)); b[3] = (uint8_t)(0x80u | (c & 0x3Fu)); }
+            out.append((const char*)b, l);
+        }
+        if (norig) norig->insert(norig->end(), out.size() - before, (uint32_t)i);
+        i += len;
+    }
+    return out;
 }
 
 void HostModel::build_nfc() { build_nfc_tables(*this); }
@@ -1989,7 +2130,8 @@ std::string HostModel::precompiled_normalize(const std::string& s, std::vector<u
 }
 
 std::string HostModel::nfc_normalize(const std::string& s, std::vector<uint32_t>* norig, bool* refused) const {
-    const NfcTables t{nfc_stage1.data(), nfc_stage2.data(), nfc_map.data(), nfc_mask, nfc_seed};
+    NfcTables t{nfc_stage1.data(), nfc_stage2.data(), nfc_map.data(), nfc_mask, nfc_seed};
+    if ((t.mode = nfd_mode()) & NFD_LOWER) { t.l1 = bn_stage1.data(); t.l2 = bn_stage2.data(); t.lmap = bn_map.data(); t.lmap_mask = bn_mask; t.lmap_seed = bn_seed; }
     const int64_t n = (int64_t)s.size();
     std::vector<nfc_mask_t> bound((size_t)(n >> 6) + 2, 0ull);
     bound[0] = 1ull;                                       // one piece

@@ -57,6 +57,17 @@ struct HostModel {
     bool pp_add_prefix_space = true;  // the post-processor's own add_prefix_space (process_offsets argument)
     // BertNormalizer options (normalizers/bert.rs:62-90)
     bool bn_clean_text = true, bn_handle_chinese = true, bn_strip_accents = true, bn_lowercase = true;
+    // NORM_CHAIN: the members in the file's order (tables.hpp ChainMember), and how the file spells the section ("type 'NFD'", "this
+    // Sequence") for the refusals made once the model and the pre-tokenizer are known
+    std::vector<uint8_t> chain;
+    std::string chain_spelling;
+    bool chain_has(uint8_t member) const { for (uint8_t c : chain) if (c == member) return true; return false; }
+    // NFD with no StripAccents behind it: the canonical ordering of marks stays in the text, so the chain is no map of single chars -- it
+    // runs on the NFC normalizer's segments in their NFD mode (nfc_core.hpp; the mode bits: NFD_MODE | where Lowercase stands)
+    uint32_t nfd_mode() const {
+        if (norm != NORM_CHAIN || !chain_has(CHAIN_NFD) || chain_has(CHAIN_STRIP_ACCENTS)) return 0u;
+        return 1u | (!chain_has(CHAIN_LOWERCASE) ? 0u : chain[0] == CHAIN_LOWERCASE ? 2u : 4u);
+    }
 
     // the "▁" front (PT_METASPACE): where a piece gets its "▁" (tables.hpp MsPrepend), and whether every "▁" starts a pre-token
     // (Metaspace split = true) or the device cuts a piece into units at every "▁" behind a char other than "▁" (proved exact at load)
@@ -126,6 +137,11 @@ struct HostModel {
     // pattern normalization at load, tkamd_probe_bert_norm); *refused = a character whose NFD reordering is context dependent
     int bn_expand_cp(uint32_t cp, uint32_t* out, int* refused) const;
     std::string bert_normalize(const std::string& s, bool* refused) const;
+    // NORM_CHAIN: what the chain makes of one code point / of a string that is one piece, from the host copy of the tables the kernels read
+    // and by the core they run (pattern normalization at load, tkamd_probe_norm_chain); norig (or null): per output byte, the first byte of
+    // its source char; *refused: NFD mode met a segment beyond NFC_SEG_MAX
+    int chain_expand_cp(uint32_t cp, uint32_t* out) const;
+    std::string chain_normalize(const std::string& s, std::vector<uint32_t>* norig, bool* refused = nullptr) const;
     // NFC of a string that is one piece, by the core the device runs (nfc_core.hpp; host side: pattern normalization at load, the test
     // harness); norig (or null): per output byte, the first byte of the source char it is aligned to; *refused = a segment beyond NFC_SEG_MAX
     std::string nfc_normalize(const std::string& s, std::vector<uint32_t>* norig, bool* refused) const;
@@ -168,6 +184,7 @@ struct HostModel {
     bool uni_bytes = false;
 
     // BertNormalizer per-code-point data (bert_norm_tables.inc): 2-stage flag table + cuckoo map (cp, kind) -> 3 x 21-bit cps
+    // (NORM_CHAIN: the chain's own data in the same layout -- flag 1 on every char the chain changes, (cp, 0) -> its expansion)
     std::vector<uint16_t> bn_stage1;
     std::vector<uint8_t> bn_stage2;
     std::vector<MergeSlot> bn_map;

@@ -61,6 +61,9 @@ struct BnTables {
     const MergeSlot* map;             // (cp, kind) -> up to 3 code points, 21 bits each in (rank, new_id)
     uint32_t map_mask, map_seed;
     uint32_t clean, cjk, strip, lower;
+    // NORM_CHAIN (tables.hpp): bn1 / bn2 / map are the chain's own tables -- flag BN_CHAIN_X on every char the chain changes, its whole
+    // expansion under (cp, 0) -- and clean / cjk / strip / lower are all off.  Bit 0: a chain; bit 1: Lowercase is a member (ASCII lanes)
+    uint32_t chain = 0;
 };
 
 // one queued pre-token (kernels/results.hip); a queue = NSQ sub-queues of sq_cap entries, one per lookup workgroup, each with its

@@ -17,6 +17,11 @@
 // =================================================================================================
 constexpr uint32_t BN_DROP = 1, BN_WS = 2, BN_CJK = 4, BN_REORDER = 8, BN_D = 16, BN_LC = 32;
 constexpr int BN_MAX_OUT = 12;
+// The chains of NFD / Lowercase / StripAccents (NORM_CHAIN, tables.hpp) run through the same two kernels over tables of their own:
+// bt.chain is set, the flag table says BN_CHAIN_X for every char the chain changes and the map holds its whole expansion (0..3 code
+// points) under (cp, 0), composed from the members at load (host_model.cpp build_norm_chain).  Nothing of such a chain looks across
+// chars, so k_bn_reorder_fix is not launched for it.
+constexpr uint32_t BN_CHAIN_X = 1, BN_CHAIN_ON = 1, BN_CHAIN_LOWER = 2;
 
 
 __device__ __forceinline__ uint32_t bn_flags(const BnTables& b, uint32_t cp) {
@@ -38,6 +43,11 @@ __device__ __forceinline__ int bn_lookup(const BnTables& b, uint32_t cp, uint32_
 // expansion of one source code point; returns the number of output code points (*reorder set for refused chars)
 __device__ __forceinline__ int bn_expand(const BnTables& b, uint32_t cp, uint32_t* out, bool* reorder) {
     uint32_t f = bn_flags(b, cp);
+    if (b.chain) {
+        if (f & BN_CHAIN_X) return bn_lookup(b, cp, 0, out);
+        out[0] = cp;
+        return 1;
+    }
     if (b.clean) {
         if (f & BN_DROP) return 0;
         if (f & BN_WS) { cp = ' '; f = 0; }
@@ -180,7 +190,7 @@ __device__ __forceinline__ void bn_write_byte(const BnTables& bt, const uint8_t*
     if (b < 0x80u) {
         uint32_t c = b;
         if (bt.clean && (c == '\t' || c == '\n' || c == '\r')) c = ' ';
-        if (bt.lower && c - 'A' < 26u) c += 32u;
+        if ((bt.lower || (bt.chain & BN_CHAIN_LOWER)) && c - 'A' < 26u) c += 32u;
         ntext[pos] = (uint8_t)c;
         if (nos) { nos[pos] = (uint32_t)i; if (noe) noe[pos] = (uint32_t)i + 1u; }
         return;
@@ -221,7 +231,7 @@ __global__ __launch_bounds__(256) void k_bn_write(BnTables bt, const uint8_t* __
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (bt.clean) { const uint32_t m = (sw_ascii_ws(x[k]) >> 7) * 0xFFu; x[k] = (x[k] & ~m) | (0x20202020u & m); }
-            if (bt.lower) x[k] += (~sw_lt(x[k], 0x41u) & sw_lt(x[k], 0x5Bu) & SW_H) >> 2;
+            if (bt.lower || (bt.chain & BN_CHAIN_LOWER)) x[k] += (~sw_lt(x[k], 0x41u) & sw_lt(x[k], 0x5Bu) & SW_H) >> 2;
         }
         *(Unaligned16*)(ntext + pos) = Unaligned16{x[0], x[1], x[2], x[3]};
         if (nos) {

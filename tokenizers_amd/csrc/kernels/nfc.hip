@@ -50,7 +50,9 @@ __device__ __forceinline__ bool nfc_lane_plain(const NfcArgs& a, int64_t i0, boo
         p = nfc_unit_start(a.text, a.n_bytes, i0);
         while (p < i1) {
             uint32_t l;
-            if (nfc_flags(a.nt, nfc_decode(a.text, a.n_bytes, p, &l)) & NFC_F_ACTIVE) return false;
+            const uint32_t cp = nfc_decode(a.text, a.n_bytes, p, &l), f = nfc_flags(a.nt, cp);
+            if (f & NFC_F_ACTIVE) return false;
+            if (a.nt.mode && nfd_changes(a.nt, cp, f)) return false;      // (NFD mode: an upper-case ASCII letter among them too -- only all-ASCII lanes are lowercased on the copy)
             p += l;
         }
     }
@@ -175,10 +177,16 @@ __global__ __launch_bounds__(256) void k_nfc_write(NfcArgs a, BnOlen olen, const
     const uint32_t pos = wbase[i0 >> 6] + (sub >= 1 ? t1 : 0u) + (sub >= 2 ? t2 : 0u) + (sub >= 3 ? t3 : 0u);
     if (lt & BN_LTOT_PLAIN) {
         const Unaligned16 t = *(const Unaligned16*)(a.text + i0);
-        *(Unaligned16*)(ntext + pos) = t;
+        const bool ascii = ((t.a | t.b | t.c | t.d) & SW_H) == 0u;
+        if (ascii && (a.nt.mode & NFD_LOWER)) {                // (Lowercase is a member: A-Z -> a-z on the copy, as in k_bn_write)
+            uint32_t x[4] = {t.a, t.b, t.c, t.d};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[k] += (~sw_lt(x[k], 0x41u) & sw_lt(x[k], 0x5Bu) & SW_H) >> 2;
+            *(Unaligned16*)(ntext + pos) = Unaligned16{x[0], x[1], x[2], x[3]};
+        } else *(Unaligned16*)(ntext + pos) = t;
         if (nos) {
             const uint32_t b0 = (uint32_t)i0;
-            if (((t.a | t.b | t.c | t.d) & SW_H) == 0u) {
+            if (ascii) {
 #pragma unroll
                 for (int j = 0; j < NFC_LANE; j += 4) *(Unaligned16*)(nos + pos + j) = Unaligned16{b0 + j, b0 + j + 1u, b0 + j + 2u, b0 + j + 3u};
             } else {

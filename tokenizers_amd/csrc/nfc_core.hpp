@@ -39,11 +39,23 @@ constexpr uint32_t NFC_S_BASE = 0xAC00u, NFC_L_BASE = 0x1100u, NFC_V_BASE = 0x11
                    NFC_S_N = 19u * 21u * 28u;
 constexpr uint32_t NFC_FILL = 0x1FFFFFu;
 
+// NFD mode (a normalizer chain of NFD and Lowercase with no StripAccents, tables.hpp NORM_CHAIN): the same segments, decomposed and
+// ordered but not composed; Lowercase, a map of single chars, is applied to every source char in front of its decomposition
+// (Sequence[Lowercase, NFD]: a char it makes two of is two source chars to NFD, both aligned to the one) or to every piece behind the
+// ordering (Sequence[NFD, Lowercase]: one char each there -- the one char to_lowercase makes two of, U+0130, decomposes first).
+constexpr uint32_t NFD_MODE = 1u, NFD_LOWER_FIRST = 2u, NFD_LOWER_LAST = 4u, NFD_LOWER = NFD_LOWER_FIRST | NFD_LOWER_LAST;
+
 struct NfcTables {
     const uint16_t* n1;
     const uint8_t* n2;
     const MergeSlot* map;
     uint32_t map_mask, map_seed;
+    uint32_t mode = 0u;                  // 0: NFC
+    // NFD_LOWER_*: to_lowercase in the BertNormalizer's layout -- flag 1 on every char it changes, (cp, 0) -> up to three code points
+    const uint16_t* l1 = nullptr;
+    const uint8_t* l2 = nullptr;
+    const MergeSlot* lmap = nullptr;
+    uint32_t lmap_mask = 0u, lmap_seed = 0u;
 };
 using nfc_mask_t = unsigned long long;
 
@@ -58,6 +70,25 @@ TK_HD bool nfc_map(const NfcTables& t, uint32_t a, uint32_t b, uint32_t* lo, uin
     *hi = h->new_id;
     return true;
 }
+TK_HD bool nfd_lowercases(const NfcTables& t, uint32_t cp) { return cp < 0x110000u && (t.l2[((uint32_t)t.l1[cp >> 8] << 8) | (cp & 255u)] & 1u) != 0u; }
+// to_lowercase of cp: out[0 .. returned) (the char itself where it has none)
+TK_HD int nfd_lower(const NfcTables& t, uint32_t cp, uint32_t* out) {
+    out[0] = cp;
+    if (!nfd_lowercases(t, cp)) return 1;
+    const MergeSlot& x = t.lmap[merge_hash1(cp, 0u, t.lmap_seed) & t.lmap_mask];
+    const MergeSlot& y = t.lmap[merge_hash2(cp, 0u, t.lmap_seed) & t.lmap_mask];
+    const MergeSlot* h = (x.a == cp && x.b == 0u) ? &x : (y.a == cp && y.b == 0u) ? &y : nullptr;
+    if (!h) return 1;
+    const unsigned long long v = ((unsigned long long)h->new_id << 32) | h->rank;
+    int k = 0;
+    for (int q = 0; q < 3; ++q) {
+        const uint32_t c = (uint32_t)((v >> (21 * q)) & 0x1FFFFFu);
+        if (c != 0x1FFFFFu) out[k++] = c;
+    }
+    return k;
+}
+// NFD mode: does the char (flags f) change on its own -- a decomposition, a lowercase form?
+TK_HD bool nfd_changes(const NfcTables& t, uint32_t cp, uint32_t f) { return (f & 0x40u) != 0u || ((t.mode & NFD_LOWER) && nfd_lowercases(t, cp)); }
 TK_HD uint32_t nfc_utf8_len(uint32_t cp) { return cp < 0x80u ? 1u : cp < 0x800u ? 2u : cp < 0x10000u ? 3u : 4u; }
 TK_HD uint32_t nfc_utf8_put(uint8_t* o, uint32_t c) {
     if (c < 0x80u) { o[0] = (uint8_t)c; return 1u; }
@@ -146,6 +177,10 @@ TK_HD int64_t nfc_seg_start(const NfcTables& t, const uint8_t* text, int64_t n, 
 // the unit at s (flags f, length l) is a segment head: is the segment that unit alone, unchanged?
 TK_HD bool nfc_trivial(const NfcTables& t, const uint8_t* text, int64_t n, const nfc_mask_t* bound, int64_t s, uint32_t f, uint32_t l) {
     if (f & NFC_F_ACTIVE) return false;
+    if (t.mode) {                                           // (NFD mode: a char that decomposes or lowercases is a segment to normalize)
+        uint32_t l0;
+        if (nfd_changes(t, nfc_decode(text, n, s, &l0), f)) return false;
+    }
     const int64_t p = s + l;
     if (p >= n || nfc_bit(bound, p)) return true;
     if (text[p] < 0x80u) return true;
@@ -190,31 +225,37 @@ TK_HD_OUTLINE bool nfc_segment(const NfcTables& t, const uint8_t* text, int64_t 
         const uint32_t cp = nfc_decode(text, n, p, &l);
         const uint32_t f = nfc_flags(t, cp);
         if (nsrc && !(f & NFC_F_ACTIVE)) break;
-        if (nsrc == NFC_SEG_MAX) return false;
-        uint32_t d[4] = {cp, NFC_FILL, NFC_FILL, NFC_FILL};
-        if (f & NFC_F_DECOMP) {
-            if (cp - NFC_S_BASE < NFC_S_N) {
-                const uint32_t x = cp - NFC_S_BASE;
-                d[0] = NFC_L_BASE + x / (NFC_V_N * NFC_T_N);
-                d[1] = NFC_V_BASE + (x % (NFC_V_N * NFC_T_N)) / NFC_T_N;
-                if (x % NFC_T_N) d[2] = NFC_T_BASE + x % NFC_T_N;
-            } else {
-                uint32_t lo, hi;
-                if (nfc_map(t, cp, 0u, &lo, &hi)) {
-                    const unsigned long long v = ((unsigned long long)hi << 32) | lo;
-                    d[0] = (uint32_t)(v & NFC_FILL); d[1] = (uint32_t)((v >> 21) & NFC_FILL); d[2] = (uint32_t)((v >> 42) & NFC_FILL);
-                    if (d[2] != NFC_FILL && nfc_map(t, cp, 1u, &lo, &hi)) d[3] = lo;
+        // (Lowercase in front of NFD: what it makes of the char are the source chars NFD sees, each aligned to the char)
+        uint32_t lc[3] = {cp, 0u, 0u};
+        const int nl = (t.mode & NFD_LOWER_FIRST) ? nfd_lower(t, cp, lc) : 1;
+        for (int u = 0; u < nl; ++u) {
+            if (nsrc == NFC_SEG_MAX) return false;
+            const uint32_t c = lc[u], fc = c == cp ? f : nfc_flags(t, c);
+            uint32_t d[4] = {c, NFC_FILL, NFC_FILL, NFC_FILL};
+            if (fc & NFC_F_DECOMP) {
+                if (c - NFC_S_BASE < NFC_S_N) {
+                    const uint32_t x = c - NFC_S_BASE;
+                    d[0] = NFC_L_BASE + x / (NFC_V_N * NFC_T_N);
+                    d[1] = NFC_V_BASE + (x % (NFC_V_N * NFC_T_N)) / NFC_T_N;
+                    if (x % NFC_T_N) d[2] = NFC_T_BASE + x % NFC_T_N;
+                } else {
+                    uint32_t lo, hi;
+                    if (nfc_map(t, c, 0u, &lo, &hi)) {
+                        const unsigned long long v = ((unsigned long long)hi << 32) | lo;
+                        d[0] = (uint32_t)(v & NFC_FILL); d[1] = (uint32_t)((v >> 21) & NFC_FILL); d[2] = (uint32_t)((v >> 42) & NFC_FILL);
+                        if (d[2] != NFC_FILL && nfc_map(t, c, 1u, &lo, &hi)) d[3] = lo;
+                    }
                 }
             }
+            for (int q = 0; q < 4 && d[q] != NFC_FILL; ++q) {
+                if (np == NFC_SEG_MAX) return false;
+                g.cp[np] = d[q];
+                g.rank[np] = (uint8_t)(((fc & NFC_F_DECOMP) ? nfc_flags(t, d[q]) : fc) & NFC_F_RANK);
+                g.chg[np] = (int8_t)(q ? 1 : 0);
+                ++np;
+            }
+            g.src[nsrc++] = (uint8_t)(p - s);
         }
-        for (int q = 0; q < 4 && d[q] != NFC_FILL; ++q) {
-            if (np == NFC_SEG_MAX) return false;
-            g.cp[np] = d[q];
-            g.rank[np] = (uint8_t)(((f & NFC_F_DECOMP) ? nfc_flags(t, d[q]) : f) & NFC_F_RANK);
-            g.chg[np] = (int8_t)(q ? 1 : 0);
-            ++np;
-        }
-        g.src[nsrc++] = (uint8_t)(p - s);
         p += l;
     }
     g.e = p;
@@ -233,7 +274,16 @@ TK_HD_OUTLINE bool nfc_segment(const NfcTables& t, const uint8_t* text, int64_t 
     bool have = false;
     uint32_t kc = 0, last = 0;                             // last: class of the char buffered last (0: none is buffered)
     int kh = 0;
-    for (int i = 0; i < np; ++i) {
+    if (t.mode) {                                          // NFD: the ordered pieces are the output; Lowercase behind it maps each to one char
+        no = np;
+        if (t.mode & NFD_LOWER_LAST)
+            for (int k = 0; k < np; ++k) {
+                uint32_t lc[3];
+                if (nfd_lower(t, g.cp[k], lc) != 1) return false;
+                g.cp[k] = lc[0];
+            }
+    }
+    for (int i = 0; i < np && !t.mode; ++i) {
         const uint32_t c = g.cp[i], r = g.rank[i];
         const int h = g.chg[i];
         if (!have) {

@@ -201,7 +201,11 @@ enum PretokKind {
 // NORM_NFC: NFC alone or Sequence[NFC] (normalizers/unicode.rs), in front of byte-level BPE (nfc_core.hpp, kernels/nfc.hip)
 // NORM_PRECOMPILED: Precompiled alone, Sequence[Precompiled] or Sequence[Precompiled, Replace(Regex " {2,}" -> " ")] in front of Unigram
 // behind the "▁" front (normalizers/precompiled.rs; precompiled_core.hpp, kernels/precompiled.hip)
-enum NormKind { NORM_NONE = 0, NORM_BERT = 1, NORM_METASPACE = 2, NORM_NFC = 3, NORM_PRECOMPILED = 4 };
+// NORM_CHAIN: NFD, Lowercase, StripAccents, alone or as a Sequence of them in which StripAccents stands behind NFD if both are there
+// (normalizers/unicode.rs, utils.rs, strip.rs), in front of the character-level models: context free per source char, expanded at load
+// into tables of its own that the BertNormalizer's kernels read (kernels/bert_norm.hip, BnTables::chain)
+enum NormKind { NORM_NONE = 0, NORM_BERT = 1, NORM_METASPACE = 2, NORM_NFC = 3, NORM_PRECOMPILED = 4, NORM_CHAIN = 5 };
+enum ChainMember : uint8_t { CHAIN_NFD = 0, CHAIN_LOWERCASE = 1, CHAIN_STRIP_ACCENTS = 2 };
 // where the "▁" front puts a "▁" in front of a piece (the raw text between document edges and added-token matches)
 enum MsPrepend {
     MS_NEVER = 0,      // Metaspace prepend_scheme "never"; Replace alone
