@@ -340,6 +340,11 @@ int tkamd_probe_precompiled(const tkamd_tokenizer* tok, const uint8_t* text, int
  * read, the per-char expansions composed at load: out[0 .. *n_out) the normalized bytes, src[k] the first byte of the source char
  * that byte k is aligned to.  cap: what out and src hold; *n_out is set even when it is too small (TKAMD_ERR_INVALID then). */
 int tkamd_probe_norm_chain(const tkamd_tokenizer* tok, const uint8_t* text, int64_t n, uint8_t* out, uint32_t* src, int64_t cap, int64_t* n_out);
+/* NFKC (info.normalizer == 6) over ONE piece -- text[0 .. n) -- by the host run of the very core the kernels run, the K mode of
+ * csrc/nfc_core.hpp: out[0 .. *n_out) the normalized bytes, src[k] the first byte of the source char that byte k is aligned to.  A run of
+ * more than 48 combining characters is refused (TKAMD_ERR_UNSUPPORTED), as a batch that holds one is.  cap: what out and src hold; *n_out
+ * is set even when it is too small (TKAMD_ERR_INVALID then). */
+int tkamd_probe_nfkc(const tkamd_tokenizer* tok, const uint8_t* text, int64_t n, uint8_t* out, uint32_t* src, int64_t cap, int64_t* n_out);
 /* BertNormalizer strip_accents on the character whose lead byte is text[pos] (text[0 .. n) = one piece handed to the normalizer: a
  * document, or what lies between two added-token matches): *reorder = 1 if it survives the Mn filter with a non-zero combining
  * class (NFD's canonical ordering could move it), *alone = 1 if it is alone in its run of non-starters -- nothing moves; 0: the

@@ -37,7 +37,7 @@ SYMBOLS = [
     "tkamd_encode_batch_device", "tkamd_device_sync", "tkamd_profile_enable", "tkamd_profile_read",
     "tkamd_profile_counters", "tkamd_tokenizer_specials", "tkamd_version", "tkamd_word_cache",
     "tkamd_decode_batch", "tkamd_text_n_docs", "tkamd_text_n_bytes", "tkamd_text_bytes", "tkamd_text_doc_offsets",
-    "tkamd_text_free", "tkamd_decode_token", "tkamd_probe_word", "tkamd_probe_merge", "tkamd_probe_bert_norm", "tkamd_probe_precompiled", "tkamd_probe_norm_chain", "tkamd_probe_unicode_flags", "tkamd_probe_trie",
+    "tkamd_text_free", "tkamd_decode_token", "tkamd_probe_word", "tkamd_probe_merge", "tkamd_probe_bert_norm", "tkamd_probe_precompiled", "tkamd_probe_norm_chain", "tkamd_probe_nfkc", "tkamd_probe_unicode_flags", "tkamd_probe_trie",
     "tkamd_batch_encoding_docs", "tkamd_probe_truncation", "tkamd_probe_bert_alone", "tkamd_tokenizer_pair_template", "tkamd_batch_encoding_parts", "tkamd_probe_bert_nfd", "tkamd_encode_special_tokens",
     "tkamd_tokenizer_from_json_devices", "tkamd_tokenizer_set_collect", "tkamd_tokenizer_devices", "tkamd_shard_stats", "tkamd_debug_phases",
     "tkamd_pinned_alloc", "tkamd_pinned_free", "tkamd_encode_batch_paced",
@@ -166,6 +166,8 @@ def load() -> C.CDLL:
     lib.tkamd_probe_precompiled.restype = i32
     lib.tkamd_probe_norm_chain.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     lib.tkamd_probe_norm_chain.restype = i32
+    lib.tkamd_probe_nfkc.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    lib.tkamd_probe_nfkc.restype = i32
     lib.tkamd_probe_unicode_flags.argtypes = [vp, u32, C.POINTER(u32)]
     lib.tkamd_probe_unicode_flags.restype = i32
     lib.tkamd_probe_trie.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(u32)]

@@ -94,7 +94,7 @@ struct tkamd_tokenizer {
     DevBuf t_at_id[2], t_at_flags[2], t_at_blob[2], t_at_off[2], t_at_first[2];   // AddedVocabulary patterns of the two matching passes
     DevBuf t_pp_single, t_pp_single_plain;      // the single layout as pieces (the single inputs of a mixed batch)
     DevBuf t_pp_pair, t_pp_pair_plain;   // pair template of the post-processor with / without its special tokens: [pieces][3]
-    DevBuf t_pp_prefix, t_pp_suffix, t_pp_prefix_ty, t_pp_suffix_ty, t_bn1, t_bn2, t_bn_map, t_nfc1, t_nfc2, t_nfc_map, t_pc_units, t_pc_rep, t_gc1, t_gc2, t_merge_disp, t_dec_entry, t_dec_blob, t_trie, t_uni_score, t_uni_is_byte;
+    DevBuf t_pp_prefix, t_pp_suffix, t_pp_prefix_ty, t_pp_suffix_ty, t_bn1, t_bn2, t_bn_map, t_nfc1, t_nfc2, t_nfc_map, t_nfk_map, t_nfk_flat, t_pc_units, t_pc_rep, t_gc1, t_gc2, t_merge_disp, t_dec_entry, t_dec_blob, t_trie, t_uni_score, t_uni_is_byte;
     int n_cu = 256;
     int n_direct = 0;
     int n_hot = 0;

@@ -88,7 +88,8 @@ struct Batch {
     // check_request
     bool mixed = false, want_words = false, want_meta = false, add_special = false, prefix_space = false, metaspace = false, words_in = false, pairs = false;
     bool typed_single = false, has_epilogue = false, want_overflow = false;
-    bool precomp = false;          // behind a Precompiled normalizer: the "▁" front reads its output (normalize_precompiled)
+    bool precomp = false;          // behind a Precompiled or an NFKC normalizer: the "▁" front reads its output (normalize_precompiled / normalize_nfkc)
+    bool nfkc = false;             // ... the second of the two: normalized added tokens are matched over that output (pass 2)
     int64_t n_p = 0;               // ... the host's bound of that text
     const uint8_t* p_text = nullptr; const int64_t *p_doc_off = nullptr, *d_plen = nullptr; const uint32_t* p_norig = nullptr;
     bool nfc_general = false;      // behind an NFC normalizer: this run normalizes (else X is the text as it came, behind k_nfc_check)
@@ -124,7 +125,7 @@ struct Batch {
     AddedArgs args_of(int c);
     void scatter_masks(int64_t n_text, const int64_t* len_dev, bool with_end);
     const int64_t* build_pieces(const int64_t* doc_csr, int64_t n_text, const int64_t* len_dev);
-    void normalize_bert(); void normalize_nfc(); void normalize_precompiled(); void shift_behind_prefix_spaces(); void metaspace_front(); void read_ntext();
+    void normalize_bert(); void normalize_nfc(); void normalize_precompiled(); void normalize_nfkc(); void shift_behind_prefix_spaces(); void metaspace_front(); void read_ntext();
     // helpers of run_model / compact_and_meta
     void* phases_of(int which);
     void open_word_cache();
@@ -159,7 +160,14 @@ void Batch::check_request() {
     for (int c = 0; c < 2; ++c)
         for (size_t k = 0; k + 1 < hm.at[c].off.size(); ++k) at_min_len = std::min<size_t>(at_min_len, hm.at[c].off[k + 1] - hm.at[c].off[k]);
     const bool have_added_tokens = at_min_len != (size_t)-1;
-    mcap = have_added_tokens ? (uint32_t)std::min<size_t>((size_t)n_bytes / std::max<size_t>(at_min_len, 1) + 16, 0x7FFFFFF0u) : 0u;
+    // (NFKC: every batch takes the normalizer's kernels -- no quick-check speculation yet, DESIGN section 8 -- and pass 2 runs over their output.
+    // Matches do not overlap and each covers min_len bytes of the text it was found in, so the list is bounded by the longest text a pass
+    // reads: behind NFKC the normalized text, up to NFK_GROWTH times the text as it came -- a token that occurs several times inside ONE
+    // char's expansion, "\u0644" in that of U+FDFA, is more matches than the source has bytes.  The consumers of the list loop to the
+    // count the matchers left, so the bound must hold; n_x and seg_cap below follow it.)
+    nfkc = hm.norm == NORM_NFKC;
+    const size_t match_text = nfkc ? (size_t)NFK_GROWTH * (size_t)n_bytes + 64 : (size_t)n_bytes;
+    mcap = have_added_tokens ? (uint32_t)std::min<size_t>(match_text / std::max<size_t>(at_min_len, 1) + 16, 0x7FFFFFF0u) : 0u;
     // (a prefix space goes in front of every piece: every document, and what follows every match)
     // (the "▁" front: a ' ' becomes three bytes, and a "▁" of three goes in front of a piece -- every document, and what follows every match)
     // NFC: almost all text is NFC already, so a batch runs over the text as it came with k_nfc_check reading it once; one the check cannot
@@ -176,8 +184,8 @@ void Batch::check_request() {
     }
     if (hm.nfd_mode()) nfc_general = true;          // (a chain that leaves NFD in the text: the normalizer's kernels for every batch, no quick check)
     // (Precompiled: a source byte stands for at most pc_growth output bytes, found at load; the "▁" front then reads that text)
-    precomp = hm.norm == NORM_PRECOMPILED;
-    n_p = precomp ? (int64_t)hm.pc_growth * n_bytes + 64 : n_bytes;
+    precomp = hm.norm == NORM_PRECOMPILED || nfkc;
+    n_p = precomp ? (int64_t)(nfkc ? NFK_GROWTH : hm.pc_growth) * n_bytes + 64 : n_bytes;
     // (behind the normalizer only: every other tokenizer's text is bounded by the check of n_x below, as before)
     if (precomp && n_p >= (int64_t)0x55555500ll) throw Invalid("batch larger than 4 GiB behind the normalizer's bound: split it (byte offsets are 32-bit on the device)");
     n_x = (hm.norm == NORM_BERT || hm.norm == NORM_CHAIN || nfc_general) ? 3 * n_bytes + 64
@@ -461,6 +469,48 @@ void Batch::normalize_precompiled() {
     p_norig = pnorig;
 }
 
+void Batch::normalize_nfkc() {
+    // ---- NFKC: text -> normalized text + the source char of every normalized byte (kernels/nfkc.hip, the K mode of the NFC core) in the
+    // Precompiled normalizer's arrangement: the pieces are the documents and what lies between the matches of pass 1, which are copied
+    // verbatim; pass 2 and the "▁" front read the result. ----
+    const int64_t Wp = (n_p >> 6) + 1;
+    w->w_ptext.reserve((size_t)n_p + TKAMD_TEXT_PAD);
+    w->w_pdoc_off.reserve((size_t)(n_docs + 2) * 8);
+    w->w_pc_ltot.reserve((((size_t)n_bytes >> 4) + 8) * 2);
+    w->w_keepmask.reserve(bn_olen_bytes(n_p));              // (sized for the front's pass over the normalized text too: the buffers do not move between the two)
+    w->w_kprefix.reserve((size_t)(Wp + 1) * 4);
+    w->w_wbase.reserve((size_t)(Wp + 1) * 4);
+    w->w_ms_dmask.reserve((size_t)(Wp + 2) * 8);
+    if (off_mode != TKAMD_OFFSETS_NONE) w->w_pnorig.reserve(((size_t)n_p + 4) * 4);
+    HIP_CHECK(hipMemsetAsync(w->w_ms_dmask.p, 0, (size_t)(W0 + 2) * 8, st));
+    launch_mark_doc_starts_n(st, d_doc_off, n_docs, n_bytes, nullptr, w->w_ms_dmask.as<ull>(), d_err);
+    const ull* verbatim = nullptr;
+    if (have_raw) {
+        scatter_masks(n_bytes, nullptr, false);
+        launch_mask_or2(st, w->w_boundmask.as<ull>(), w->w_matchmask.as<ull>(), w->w_spanmask.as<ull>(), W0 + 1);
+        verbatim = w->w_boundmask.as<ull>();
+        launch_nfc_bound(st, w->w_ms_dmask.as<ull>(), verbatim, W0 + 1);
+    }
+    NfcTables nt{t->t_nfc1.as<uint16_t>(), t->t_nfc2.as<uint8_t>(), t->t_nfc_map.as<MergeSlot>(), hm.nfc_mask, hm.nfc_seed};
+    nt.lmap = t->t_nfk_map.as<MergeSlot>(); nt.lmap_mask = hm.nfk_mask; nt.lmap_seed = hm.nfk_seed; nt.kflat = t->t_nfk_flat.as<uint32_t>();      // (K mode's slots, nfc_core.hpp)
+    int64_t* plen = sc + SC_PLEN;
+    uint32_t* pnorig = off_mode != TKAMD_OFFSETS_NONE ? w->w_pnorig.as<uint32_t>() : nullptr;
+    pf.begin("nfkc_normalize");
+    launch_nfkc_normalize(st, nt, d_text, n_bytes, d_doc_off, n_docs, verbatim, w->w_ms_dmask.as<ull>(), w->w_keepmask.as<uint8_t>(), w->w_pc_ltot.as<uint16_t>(),
+                          w->w_kprefix.as<uint32_t>(), w->w_bsum.as<uint32_t>(), w->w_wbase.as<uint32_t>(), plen, w->w_ptext.as<uint8_t>(), pnorig, w->w_pdoc_off.as<int64_t>(), d_err, n_p);
+    launch_zero_tail(st, w->w_ptext.as<uint8_t>(), plen, TKAMD_TEXT_PAD);
+    pf.end();
+    if (have_raw) launch_pc_translate_matches(st, mlist, n_match, w->w_keepmask.as<uint8_t>(), w->w_pc_ltot.as<uint16_t>(), w->w_wbase.as<uint32_t>(), n_bytes, plen);
+    p_text = w->w_ptext.as<uint8_t>();
+    p_doc_off = w->w_pdoc_off.as<int64_t>();
+    d_plen = plen;
+    p_norig = pnorig;
+    // (pass 2 matches the normalized patterns over this text)
+    x_text = p_text;
+    x_doc_off = p_doc_off;
+    x_len_dev = d_plen;
+}
+
 void Batch::shift_behind_prefix_spaces() {
     // ---- ByteLevel add_prefix_space: every piece shifted behind its virtual leading space (byte_level.rs:120-125) ----
     const int64_t* seg = d_doc_off;
@@ -620,8 +670,9 @@ void Batch::build_x_text() {
             pf.end();
         }
     }
-    if (precomp) normalize_precompiled();
-    n_in = normalized ? n_x : n_bytes;
+    if (nfkc) normalize_nfkc();
+    else if (precomp) normalize_precompiled();
+    n_in = normalized ? n_x : nfkc ? n_p : n_bytes;
     if (spec && setB.size() > 0) {
         pf.begin("added_token_match2");
         launch_added_detect(st, args_of(1), x_text, n_in, x_len_dev, d_err);
@@ -642,7 +693,7 @@ void Batch::build_x_text() {
         pf.begin("added_token_match2");
         launch_added_match(st, args_of(1), x_text, n_in, x_len_dev, seg, nseg_bound, nseg_dev, have_raw ? w->w_matchmask.as<ull>() : nullptr, t->dt.uc1, t->dt.uc2,
                            w->w_candmask.as<ull>(), w->w_match_docs.as<uint32_t>(), d_counters + CNT_MATCH_DOCS2, mlist, n_match, mcap,
-                           normalized ? 0u : MATCH_LEN_ORIG, d_err);
+                           (normalized || nfkc) ? 0u : MATCH_LEN_ORIG, d_err);
         pf.end();
     }
     if (have_added && !prefix_space && !metaspace) {

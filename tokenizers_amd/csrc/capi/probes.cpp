@@ -121,6 +121,21 @@ int tkamd_probe_norm_chain(const tkamd_tokenizer* t, const uint8_t* text, int64_
     return TKAMD_OK;
 }
 
+// NFKC over one piece: the host run of the K mode of nfc_core.hpp, the core k_nfkc_count / k_nfkc_write run
+int tkamd_probe_nfkc(const tkamd_tokenizer* t, const uint8_t* text, int64_t n, uint8_t* out, uint32_t* src, int64_t cap, int64_t* n_out) {
+    if (!t || (!text && n) || n < 0 || !n_out || cap < 0 || (cap && (!out || !src))) return set_error(TKAMD_ERR_INVALID, "bad argument");
+    const HostModel& hm = t->hm;
+    if (hm.norm != NORM_NFKC) return set_error(TKAMD_ERR_UNSUPPORTED, "the tokenizer has no NFKC normalizer");
+    std::vector<uint32_t> al;
+    bool refused = false;
+    const std::string o = hm.nfkc_normalize(std::string((const char*)text, (size_t)n), &al, &refused);
+    if (refused) return set_error(TKAMD_ERR_UNSUPPORTED, "NFKC: a character is followed by more than 48 combining characters; the normalization of such a run is not built");
+    *n_out = (int64_t)o.size();
+    if ((int64_t)o.size() > cap) return set_error(TKAMD_ERR_INVALID, "the output buffer is too small");
+    if (!o.empty()) { memcpy(out, o.data(), o.size()); memcpy(src, al.data(), al.size() * 4); }
+    return TKAMD_OK;
+}
+
 int tkamd_probe_bert_alone(const tkamd_tokenizer* t, const uint8_t* text, int64_t n, int64_t pos, int32_t* reorder, int32_t* alone) {
     if (!t || !text || !reorder || !alone || n < 0 || pos < 0 || pos >= n) return set_error(TKAMD_ERR_INVALID, "bad argument");
     const HostModel& hm = t->hm;

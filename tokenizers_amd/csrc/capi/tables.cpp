@@ -94,6 +94,10 @@ void upload_tables(tkamd_tokenizer* t) {
     upload(t->t_nfc1, hm.nfc_stage1);
     upload(t->t_nfc2, hm.nfc_stage2);
     upload(t->t_nfc_map, hm.nfc_map);
+    if (hm.norm == NORM_NFKC) {
+        upload(t->t_nfk_map, hm.nfk_map);
+        upload(t->t_nfk_flat, hm.nfk_flat);
+    }
     if (hm.norm == NORM_PRECOMPILED) {
         upload(t->t_pc_units, hm.pc_units);
         upload(t->t_pc_rep, hm.pc_rep);

@@ -149,6 +149,24 @@ const NfcCompRow kNfcComp[] = {
 #include "nfc_tables.inc"
 };
 #undef NFC_WANT_COMP
+struct NfkDecompRow {
+    uint32_t cp, off, len;
+};
+#define NFKC_WANT_RUNS
+const UcRun kNfkRuns[] = {
+#include "nfkc_tables.inc"
+};
+#undef NFKC_WANT_RUNS
+#define NFKC_WANT_DECOMP
+const NfkDecompRow kNfkDecomp[] = {
+#include "nfkc_tables.inc"
+};
+#undef NFKC_WANT_DECOMP
+#define NFKC_WANT_FLAT
+const uint32_t kNfkFlat[] = {
+#include "nfkc_tables.inc"
+};
+#undef NFKC_WANT_FLAT
 
 // GPT-2 bytes <-> unicode map, pre_tokenizers/byte_level.rs:15-39: printable bytes map to
 // themselves, the other 68 bytes to U+0100+n in byte order.
@@ -467,6 +485,23 @@ void build_nfc_tables(HostModel& m) {
     }
     for (const NfcCompRow& r : kNfcComp) items.push_back(MergeSlot{r.a, r.b, r.c, 0u});
     build_pair_table(items, &m.nfc_map, &m.nfc_mask, &m.nfc_seed);
+}
+
+// K mode data (nfkc_tables.inc): the K flags in the flag table's place, NFC's pair table for the primary composites, and the full
+// compatibility decompositions as one flat array behind a pair table (cp, 0) -> (offset, length)
+void build_nfkc_tables(HostModel& m) {
+    build_nfc_tables(m);
+    std::vector<uint8_t> flat(0x110000, 0);
+    for (const UcRun& r : kNfkRuns)
+        for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
+    two_stage(flat, &m.nfc_stage1, &m.nfc_stage2);
+    m.nfk_flat.assign(kNfkFlat, kNfkFlat + NFKC_N_FLAT);
+    std::vector<MergeSlot> items;
+    for (const NfkDecompRow& r : kNfkDecomp) {
+        if (r.len == 0u || r.len > (uint32_t)NFKC_MAX_DECOMP || (size_t)r.off + r.len > m.nfk_flat.size()) throw Invalid("nfkc_tables.inc: a decomposition outside the flat array");
+        items.push_back(MergeSlot{r.cp, 0u, r.off, r.len});
+    }
+    build_pair_table(items, &m.nfk_map, &m.nfk_mask, &m.nfk_seed);
 }
 
 // The top-level alternatives of a regex source: cut at every '|' outside (...) and [...]; a backslash escapes the next character.
@@ -856,7 +891,7 @@ PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
                           "' are outside the hot path (only with a null pre_tokenizer)");
     if (type == "Metaspace") {
         // pre_tokenizers/metaspace.rs:34-77 (deserialisation: split defaults to true, the legacy add_prefix_space = false means "never")
-        if (m.norm != NORM_NONE && m.norm != NORM_PRECOMPILED) throw Unsupported("pre_tokenizer: Metaspace behind a normalizer");
+        if (m.norm != NORM_NONE && m.norm != NORM_PRECOMPILED && m.norm != NORM_NFKC) throw Unsupported("pre_tokenizer: Metaspace behind a normalizer");
         // (behind bare Metaspace a run of spaces is a run of U+2581: the Replace(Regex " {2,}") member is not inert there)
         if (m.pc_space_runs) throw Unsupported("normalizer: Replace(Regex ' {2,}' -> ' ') behind Precompiled is only on the path in front of Sequence[WhitespaceSplit, Metaspace]");
         const std::string rep = pt->get_str("replacement");
@@ -1308,6 +1343,23 @@ HostModel HostModel::from_json(const char* json, size_t len) {
                 }
             } else m.chain.push_back((uint8_t)chain_member(t));
             m.norm = NORM_CHAIN;
+        } else if (t == "NFKC" || (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() &&
+                                   std::any_of(norm->get("normalizers")->arr.begin(), norm->get("normalizers")->arr.end(),
+                                               [](const JsonPtr& v) { return v && v->is_object() && v->get_str("type") == "NFKC"; }))) {
+            // NFKC alone, or alone inside a Sequence.  What the file says is read here; whether it is on the path in front of this file's
+            // pre-tokenizer and model is decided below, once they are known, in the words the type was always refused by
+            if (t == "Sequence") {
+                const auto& arr = norm->get("normalizers")->arr;
+                for (const JsonPtr& v : arr) {
+                    const std::string mt = (v && v->is_object()) ? v->get_str("type") : "?";
+                    if (mt == "NFKC") continue;
+                    m.nfkc_refusal = "normalizer: '" + mt + "' next to NFKC in a Sequence is outside the hot path (only NFKC alone, or Sequence[NFKC], is on it)";
+                    break;
+                }
+                if (m.nfkc_refusal.empty() && arr.size() != 1)
+                    m.nfkc_refusal = "normalizer: 'NFKC' twice in a Sequence is outside the hot path (only NFKC alone, or Sequence[NFKC], is on it)";
+            }
+            m.norm = NORM_NFKC;
         } else if (t == "Sequence" || t == "Replace" || t == "Prepend") {
             // the "▁" normalizers of SentencePiece conversions: Sequence[Prepend("▁"), Replace(" " -> "▁")] (Llama-2, Mistral) or
             // Replace(" " -> "▁") alone (Gemma-style); anything else of these types is outside the path
@@ -1340,6 +1392,14 @@ HostModel HostModel::from_json(const char* json, size_t len) {
         const JsonValue* pt = root->get("pre_tokenizer");
         const std::string ptype = (pt && pt->is_object()) ? pt->get_str("type") : "null";
         if (ptype != "Whitespace" && ptype != "WhitespaceSplit" && ptype != "BertPreTokenizer") throw Unsupported(chain_refusal(m, "pre_tokenizer '" + ptype + "'"));
+    }
+    if (m.norm == NORM_NFKC) {                                         // (asked of the file before the pre-tokenizers' own refusals of a normalizer)
+        const JsonValue* pt = root->get("pre_tokenizer");
+        const std::string ptype = (pt && pt->is_object()) ? pt->get_str("type") : "null";
+        if (ptype != "Metaspace") throw Unsupported("normalizer: type 'NFKC' is outside the hot path");
+        if (!m.nfkc_refusal.empty()) throw Unsupported(m.nfkc_refusal);
+        if (!pt->get_bool("split", true))
+            throw Unsupported("pre_tokenizer: Metaspace(split = false) behind NFKC is outside the hot path (only split = true is on it behind the normalizer)");
     }
     m.pretok = parse_pretok(root->get("pre_tokenizer"), m);
     if (m.pretok == PT_LLAMA3 && m.split_rule.letters == 2) {         // the case classes of the case-split letter alternatives
@@ -1747,7 +1807,7 @@ HostModel HostModel::from_json(const char* json, size_t len) {
             const std::string ptype = (pt && pt->is_object()) ? pt->get_str("type") : "null";
             throw Unsupported("model: Unigram (a vocab of scored pieces) is on the path behind Metaspace(split = true) only; pre_tokenizer '" + ptype + "' is not");
         }
-        if ((m.norm != NORM_NONE && m.norm != NORM_PRECOMPILED) || !m.ms_split)
+        if ((m.norm != NORM_NONE && m.norm != NORM_PRECOMPILED && m.norm != NORM_NFKC) || !m.ms_split)
             throw Unsupported("model: Unigram (a vocab of scored pieces) over whole pieces -- Metaspace(split = false), or a null pre_tokenizer behind the U+2581 "
                               "normalizers -- is outside the hot path: the front cuts such a piece into units, and the reference compares f64 sums of "
                               "prefix + score over the whole piece, which a unit alone can round differently (only Metaspace(split = true) is on the path)");
@@ -1804,6 +1864,9 @@ HostModel HostModel::from_json(const char* json, size_t len) {
         throw Unsupported(chain_refusal(m, "this model"));
     // (the same refusal every encode call makes for any normalizer, made at load for this one: the file can never encode)
     if (m.norm == NORM_NFC && m.byte_level && m.add_prefix_space) throw Unsupported("ByteLevel add_prefix_space behind a normalizer (NFC)");
+    // (NFKC: in front of the U+2581 front and one of its two models; everything else keeps the words the type was always refused by)
+    if (m.norm == NORM_NFKC && !(m.pretok == PT_METASPACE && (m.model == MODEL_UNIGRAM || (m.model == MODEL_BPE && m.char_bpe))))
+        throw Unsupported("normalizer: type 'NFKC' is outside the hot path");
     if (m.norm == NORM_PRECOMPILED) {
         if (m.model != MODEL_UNIGRAM) throw Unsupported("normalizer: Precompiled is only on the path in front of a Unigram model");
         for (const AddedToken& a : m.added_tokens)
@@ -1883,6 +1946,7 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     build_unicode(m);
     if (m.norm == NORM_BERT) build_bert_norm(m);
     if (m.norm == NORM_NFC) build_nfc_tables(m);
+    if (m.norm == NORM_NFKC) build_nfkc_tables(m);
     if (m.norm == NORM_CHAIN && !m.nfd_mode()) build_norm_chain(m, m.chain);
     if (m.nfd_mode()) {                                      // (the NFC normalizer's tables, and to_lowercase alone in the chain's layout)
         build_nfc_tables(m);
@@ -1920,6 +1984,12 @@ HostModel HostModel::from_json(const char* json, size_t len) {
                 bool refused = false;
                 pat = m.nfc_normalize(a.content, nullptr, &refused);
                 if (refused) throw Unsupported("added token '" + a.content + "' holds a run of more than 48 combining characters (NFC of such a run is not built)");
+            }
+            if (a.normalized && m.norm == NORM_NFKC) {
+                bool refused = false;
+                pat = m.nfkc_normalize(a.content, nullptr, &refused);
+                if (refused) throw Unsupported("added token '" + a.content + "' holds a run of more than 48 combining characters (NFKC of such a run is not built)");
+                if (pat.empty()) continue;
             }
             pats[a.normalized ? 1 : 0].push_back(Pat{pat, a.id, (a.single_word ? 1u : 0u) | (a.lstrip ? 2u : 0u) | (a.rstrip ? 4u : 0u) | (a.special ? 8u : 0u)});
         }
@@ -2026,6 +2096,7 @@ std::string HostModel::chain_normalize(const std::string& s, std::vector<uint32_
 }
 
 void HostModel::build_nfc() { build_nfc_tables(*this); }
+void HostModel::build_nfkc() { build_nfkc_tables(*this); }
 
 // The charsmap of a Precompiled normalizer (precompiled_core.hpp for the layout).  Everything the device will ever index is checked here:
 // the sizes, the replacement strings (UTF-8, NUL-terminated), and every unit a key's walk can reach from the root -- its next position,
@@ -2129,9 +2200,26 @@ std::string HostModel::precompiled_normalize(const std::string& s, std::vector<u
     return out;
 }
 
+namespace {
+template <bool K>
+std::string nfc_normalize_piece(const NfcTables& t, const std::string& s, std::vector<uint32_t>* norig, bool* refused);
+}
+
+std::string HostModel::nfkc_normalize(const std::string& s, std::vector<uint32_t>* norig, bool* refused) const {
+    NfcTables t{nfc_stage1.data(), nfc_stage2.data(), nfc_map.data(), nfc_mask, nfc_seed};
+    t.lmap = nfk_map.data(); t.lmap_mask = nfk_mask; t.lmap_seed = nfk_seed; t.kflat = nfk_flat.data();      // (K mode's slots, nfc_core.hpp)
+    return nfc_normalize_piece<true>(t, s, norig, refused);
+}
+
 std::string HostModel::nfc_normalize(const std::string& s, std::vector<uint32_t>* norig, bool* refused) const {
     NfcTables t{nfc_stage1.data(), nfc_stage2.data(), nfc_map.data(), nfc_mask, nfc_seed};
     if ((t.mode = nfd_mode()) & NFD_LOWER) { t.l1 = bn_stage1.data(); t.l2 = bn_stage2.data(); t.lmap = bn_map.data(); t.lmap_mask = bn_mask; t.lmap_seed = bn_seed; }
+    return nfc_normalize_piece<false>(t, s, norig, refused);
+}
+
+namespace {
+template <bool K>
+std::string nfc_normalize_piece(const NfcTables& t, const std::string& s, std::vector<uint32_t>* norig, bool* refused) {
     const int64_t n = (int64_t)s.size();
     std::vector<nfc_mask_t> bound((size_t)(n >> 6) + 2, 0ull);
     bound[0] = 1ull;                                       // one piece
@@ -2143,13 +2231,13 @@ std::string HostModel::nfc_normalize(const std::string& s, std::vector<uint32_t>
     while (p < n) {
         uint32_t l;
         const uint32_t f = nfc_flags(t, nfc_decode(text, n, p, &l));
-        if (nfc_trivial(t, text, n, bound.data(), p, f, l)) {
+        if (nfc_trivial<K>(t, text, n, bound.data(), p, f, l)) {
             out.append(s, (size_t)p, l);
             if (norig) norig->insert(norig->end(), l, (uint32_t)p);
             p += l;
             continue;
         }
-        if (!nfc_segment(t, text, n, bound.data(), p, g)) {
+        if (!nfc_segment<K>(t, text, n, bound.data(), p, g)) {
             if (refused) *refused = true;
             return out;
         }
@@ -2163,6 +2251,7 @@ std::string HostModel::nfc_normalize(const std::string& s, std::vector<uint32_t>
     }
     return out;
 }
+}  // namespace
 
 std::string HostModel::bert_normalize(const std::string& s, bool* refused) const {
     std::string out;

@@ -61,6 +61,7 @@ struct HostModel {
     // Sequence") for the refusals made once the model and the pre-tokenizer are known
     std::vector<uint8_t> chain;
     std::string chain_spelling;
+    std::string nfkc_refusal;           // NORM_NFKC: why the Sequence it stands in is refused ("" = NFKC alone), thrown once the pre-tokenizer is known
     bool chain_has(uint8_t member) const { for (uint8_t c : chain) if (c == member) return true; return false; }
     // NFD with no StripAccents behind it: the canonical ordering of marks stays in the text, so the chain is no map of single chars -- it
     // runs on the NFC normalizer's segments in their NFD mode (nfc_core.hpp; the mode bits: NFD_MODE | where Lowercase stands)
@@ -149,6 +150,9 @@ struct HostModel {
     // test harness); norig (or null): per output byte, the first byte of the source char it is aligned to, the lost chars at the piece's start included
     std::string precompiled_normalize(const std::string& s, std::vector<uint32_t>* norig) const;
     void set_precompiled(const std::string& blob);      // decodes and validates a charsmap (Unsupported: malformed), builds the tables below
+    // NFKC of a string that is one piece, by the K mode of the same core (pattern normalization at load, tkamd_probe_nfkc, the test harness)
+    std::string nfkc_normalize(const std::string& s, std::vector<uint32_t>* norig, bool* refused) const;
+    void build_nfkc();     // the K mode's tables alone, as build_nfc()
     void build_nfc();      // the NFC tables alone (from_json builds them behind an NFC normalizer; the test harness has no tokenizer)
 
     // ---- tables copied to the device ----
@@ -194,6 +198,11 @@ struct HostModel {
     std::vector<uint8_t> nfc_stage2;
     std::vector<MergeSlot> nfc_map;
     uint32_t nfc_mask = 0, nfc_seed = 0;
+    // K mode (NORM_NFKC, nfkc_tables.inc): nfc_stage1 / 2 then hold the K flags, nfc_map stays NFC's (the primary composites); the full
+    // compatibility decompositions are nfk_flat, found through nfk_map (cp, 0) -> (offset, length)
+    std::vector<MergeSlot> nfk_map;
+    uint32_t nfk_mask = 0, nfk_seed = 0;
+    std::vector<uint32_t> nfk_flat;
 
     // Precompiled (precompiled_core.hpp): the charsmap's double array and replacement strings as the file holds them, the bytes a key starts
     // with, the most output bytes a source byte can stand for (the bound of the normalized text), and the grapheme classes in two stages

@@ -6,6 +6,7 @@
 //        │──────bert_norm──────► normalised text X (BertNormalizer)                               kernels/bert_norm.hip
 //        │──────nfc────────────► NFC quick check of the text; normalised text X where it fails               kernels/nfc.hip
 //        │──────precompiled────► Precompiled normalizer (charsmap trie per grapheme cluster) in front of Unigram   kernels/precompiled.hip
+//        │──────nfkc───────────► NFKC (the K mode of the NFC core) in front of the "▁" front                kernels/nfkc.hip
 //        │──────metaspace──────► "▁" text X + its pre-token starts (SentencePiece-style BPE)        kernels/metaspace.hip
 //        │──────pretok_*───────► pre-token start (/ end) bitmask: per-lane 64-bit mask algebra    kernels/pretok_{gpt2,llama3,local}.hip
 //        │──────scan_emit──────► pt_start[P+1]   (byte offset of every pre-token = "split")       kernels/scan_emit.hip
@@ -92,6 +93,7 @@ static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)(
 #include "kernels/bert_norm.hip"
 #include "kernels/nfc.hip"
 #include "kernels/precompiled.hip"
+#include "kernels/nfkc.hip"
 #include "kernels/metaspace.hip"
 #include "kernels/scan_emit.hip"
 #include "kernels/bpe.hip"

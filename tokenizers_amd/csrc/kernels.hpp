@@ -453,6 +453,10 @@ void launch_metaspace(hipStream_t st, const uint8_t* text, int64_t n_bytes, cons
 void launch_precompiled(hipStream_t st, const PcTables& pt, const uint8_t* text, int64_t n_bytes, const int64_t* doc_off, int64_t n_docs, const unsigned long long* verbatim,
                         const unsigned long long* bound, uint8_t* olen, uint16_t* ltot, uint32_t* wsum, uint32_t* bsum, uint32_t* wbase, int64_t* x_len, uint8_t* ntext,
                         uint32_t* nos, int64_t* ndoc_off, int* err, int grid, int64_t out_cap);      // out_cap: what ntext / nos hold; a longer text fails the batch (ERR_INTERNAL), unwritten
+// NFKC (kernels/nfkc.hip): the K mode of the NFC core, in Precompiled's layout (16-bit lane totals, out_cap as above)
+void launch_nfkc_normalize(hipStream_t st, const NfcTables& nt, const uint8_t* text, int64_t n_bytes, const int64_t* doc_off, int64_t n_docs, const unsigned long long* verbatim,
+                           const unsigned long long* bound, uint8_t* olen, uint16_t* ltot, uint32_t* wsum, uint32_t* bsum, uint32_t* wbase, int64_t* x_len, uint8_t* ntext,
+                           uint32_t* nos, int64_t* ndoc_off, int* err, int64_t out_cap);
 void launch_pc_translate_matches(hipStream_t st, uint32_t* list, const uint32_t* n_list, const uint8_t* olen, const uint16_t* ltot, const uint32_t* wbase, int64_t n_bytes,
                                  const int64_t* x_len);
 void launch_ms_units(hipStream_t st, const uint8_t* xtext, int64_t n_x, const int64_t* x_len, const unsigned long long* pmask, unsigned long long* startmask,

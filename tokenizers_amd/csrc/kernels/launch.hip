@@ -197,6 +197,22 @@ void launch_pc_translate_matches(hipStream_t st, uint32_t* list, const uint32_t*
                                  const int64_t* x_len) {
     hipLaunchKernelGGL(k_pc_translate_matches, dim3(256), dim3(256), 0, st, list, n_list, PcOlen{olen, ltot}, wbase, n_bytes, x_len);
 }
+// NFKC (kernels/nfkc.hip): the K mode's count -> scan of the 64-byte words -> the length backstop -> write, then the document CSR (Precompiled's layout)
+void launch_nfkc_normalize(hipStream_t st, const NfcTables& nt, const uint8_t* text, int64_t n_bytes, const int64_t* doc_off, int64_t n_docs, const unsigned long long* verbatim,
+                           const unsigned long long* bound, uint8_t* olen, uint16_t* ltot, uint32_t* wsum, uint32_t* bsum, uint32_t* wbase, int64_t* x_len, uint8_t* ntext,
+                           uint32_t* nos, int64_t* ndoc_off, int* err, int64_t out_cap) {
+    const int64_t n_words = (n_bytes >> 6) + 1;
+    const PcOlen ol{olen, ltot};
+    const NfcArgs a{nt, text, n_bytes, verbatim, bound};
+    hipLaunchKernelGGL(k_nfkc_count, dim3(blocks_for(n_bytes + 1, 256 * NFC_LANE)), dim3(256), 0, st, a, olen, ltot, wsum, err);
+    unsigned nb = blocks_for(n_words, 256);
+    hipLaunchKernelGGL(k_u32_reduce, dim3(nb), dim3(256), 0, st, (const uint32_t*)wsum, n_words, bsum);
+    hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, st, bsum, (int64_t)nb, (const int64_t*)nullptr, (int64_t)1, x_len);
+    hipLaunchKernelGGL(k_u32_down, dim3(nb), dim3(256), 0, st, (const uint32_t*)wsum, n_words, (const uint32_t*)bsum, wbase);
+    hipLaunchKernelGGL(k_pc_check_len, dim3(1), dim3(64), 0, st, x_len, out_cap, err);
+    hipLaunchKernelGGL(k_nfkc_write, dim3(blocks_for(n_bytes, 256 * NFC_LANE)), dim3(256), 0, st, a, ol, (const uint32_t*)wbase, (const int64_t*)x_len, (const int*)err, ntext, nos);
+    hipLaunchKernelGGL(k_pc_doc_offsets, dim3(blocks_for(n_docs + 1, 256)), dim3(256), 0, st, doc_off, n_docs, n_bytes, ol, (const uint32_t*)wbase, (const int64_t*)x_len, ndoc_off);
+}
 void launch_ms_units(hipStream_t st, const uint8_t* xtext, int64_t n_x, const int64_t* x_len, const unsigned long long* pmask, unsigned long long* startmask,
                      int64_t n_words, bool split) {
     hipLaunchKernelGGL(k_ms_units, dim3(blocks_for(n_words, 256)), dim3(256), 0, st, xtext, n_x, x_len, pmask, startmask, n_words, split ? 1u : 0u);

@@ -13,6 +13,10 @@
 // byte, so a lane's total stays within the 7 bits of ltot), which every lane holding a byte of it works out for itself from the same
 // rules -- no lane waits for another.  The segment routine with its 48-entry arrays sits behind calls that are not inlined: lanes of
 // plain text never reach them.
+// K mode (NFKC in front of the "▁" front, nfc_core.hpp): kernels of its own, k_nfkc_count / k_nfkc_write (kernels/nfkc.hip), over the K = true instantiations
+// of the same lane routines -- no branch on it inside the NFC / NFD kernels.  A source byte may stand for NFK_GROWTH output bytes there,
+// so a lane's total is 16 bits wide: the Precompiled normalizer's layout (PcOlen, kernels/precompiled.hip), whose length backstop,
+// document CSR and match translation serve unchanged.
 // =================================================================================================
 struct NfcArgs {
     NfcTables nt;
@@ -62,13 +66,14 @@ __device__ __forceinline__ bool nfc_lane_plain(const NfcArgs& a, int64_t i0, boo
 }
 
 // the segment that holds the unit starting at cs: [*s, *e) and its output bytes; a refused one (ERR_NFC_SEGMENT) is the unit itself, unchanged
+template <bool K = false>
 __device__ __forceinline__ void nfc_segment_of(const NfcArgs& a, int64_t cs, NfcSeg& g, int64_t* s, int64_t* e, uint32_t* O, int* __restrict__ err) {
     uint32_t l;
-    const int64_t h = nfc_seg_start(a.nt, a.text, a.n_bytes, a.bound, cs);
+    const int64_t h = nfc_seg_start<K>(a.nt, a.text, a.n_bytes, a.bound, cs);
     if (h >= 0) {
         const uint32_t f = nfc_flags(a.nt, nfc_decode(a.text, a.n_bytes, h, &l));
-        if (nfc_trivial(a.nt, a.text, a.n_bytes, a.bound, h, f, l)) { *s = h; *e = h + l; *O = l; return; }
-        if (nfc_segment(a.nt, a.text, a.n_bytes, a.bound, h, g)) { *s = h; *e = g.e; *O = g.obytes; return; }
+        if (nfc_trivial<K>(a.nt, a.text, a.n_bytes, a.bound, h, f, l)) { *s = h; *e = h + l; *O = l; return; }
+        if (nfc_segment<K>(a.nt, a.text, a.n_bytes, a.bound, h, g)) { *s = h; *e = g.e; *O = g.obytes; return; }
     }
     if (err) atomicOr(err, ERR_NFC_SEGMENT);
     nfc_decode(a.text, a.n_bytes, cs, &l);
@@ -76,6 +81,7 @@ __device__ __forceinline__ void nfc_segment_of(const NfcArgs& a, int64_t cs, Nfc
 }
 
 // output bytes of each of the lane's bytes, the general way
+template <bool K = false>
 __device__ __noinline__ void nfc_count_lane(const NfcArgs& a, int64_t i0, uint32_t vb, uint32_t* __restrict__ o, int* __restrict__ err) {
     NfcSeg g;
     int64_t s = 0, e = -1;
@@ -85,8 +91,8 @@ __device__ __noinline__ void nfc_count_lane(const NfcArgs& a, int64_t i0, uint32
         const int64_t i = i0 + j;
         uint32_t c = 1u;
         if (!((vb >> j) & 1u)) {
-            if (i >= e) nfc_segment_of(a, nfc_unit_start(a.text, a.n_bytes, i), g, &s, &e, &O, err);
-            c = nfc_charge((uint32_t)(i - s), O, (uint32_t)(e - s));
+            if (i >= e) nfc_segment_of<K>(a, nfc_unit_start(a.text, a.n_bytes, i), g, &s, &e, &O, err);
+            c = K ? nfc_charge_g<NFK_GROWTH>((uint32_t)(i - s), O, (uint32_t)(e - s)) : nfc_charge((uint32_t)(i - s), O, (uint32_t)(e - s));
         }
         o[j >> 2] |= c << (8 * (j & 3));
     }
@@ -119,6 +125,7 @@ __device__ __forceinline__ void nfc_copy_unit(const uint8_t* __restrict__ text, 
 
 // writes what the lane's bytes stand for, the general way: a verbatim byte itself; the head of a segment the whole segment, at the
 // place its first byte has; every other unit nothing -- unless its segment was refused (refusals: the error bit is up), then itself
+template <bool K = false>
 __device__ __noinline__ void nfc_write_lane(const NfcArgs& a, int64_t i0, uint32_t vb, const uint32_t* __restrict__ o, uint32_t pos, bool refusals,
                                             uint8_t* __restrict__ ntext, uint32_t* __restrict__ nos) {
     NfcSeg g;
@@ -132,8 +139,10 @@ __device__ __noinline__ void nfc_write_lane(const NfcArgs& a, int64_t i0, uint32
         } else if (nfc_unit_start(a.text, a.n_bytes, i) == i) {
             uint32_t l;
             const uint32_t f = nfc_flags(a.nt, nfc_decode(a.text, a.n_bytes, i, &l));
-            if (i == 0 || nfc_bit(a.bound, i) || !(f & NFC_F_ACTIVE)) {
-                if (nfc_trivial(a.nt, a.text, a.n_bytes, a.bound, i, f, l) || !nfc_segment(a.nt, a.text, a.n_bytes, a.bound, i, g)) nfc_copy_unit(a.text, i, l, pos, ntext, nos);
+            bool head = !(f & NFC_F_ACTIVE);
+            if constexpr (K) head = nfc_head<true>(a.nt, nfc_decode(a.text, a.n_bytes, i, &l), f);
+            if (i == 0 || nfc_bit(a.bound, i) || head) {
+                if (nfc_trivial<K>(a.nt, a.text, a.n_bytes, a.bound, i, f, l) || !nfc_segment<K>(a.nt, a.text, a.n_bytes, a.bound, i, g)) nfc_copy_unit(a.text, i, l, pos, ntext, nos);
                 else {
                     uint32_t k = pos;
                     for (int q = 0; q < g.n; ++q) {
@@ -145,7 +154,7 @@ __device__ __noinline__ void nfc_write_lane(const NfcArgs& a, int64_t i0, uint32
             } else if (refusals) {
                 int64_t s, e;
                 uint32_t O;
-                nfc_segment_of(a, i, g, &s, &e, &O, nullptr);
+                nfc_segment_of<K>(a, i, g, &s, &e, &O, nullptr);
                 if (s == i && e == i + (int64_t)l && ob != 0u) nfc_copy_unit(a.text, i, l, pos, ntext, nos);      // (refused: the unit alone)
             }
         } else if (ob != 0u) {
@@ -155,7 +164,7 @@ __device__ __noinline__ void nfc_write_lane(const NfcArgs& a, int64_t i0, uint32
             if (cs < i0) {
                 uint32_t l;
                 const uint32_t f = nfc_flags(a.nt, nfc_decode(a.text, a.n_bytes, cs, &l));
-                if (nfc_trivial(a.nt, a.text, a.n_bytes, a.bound, cs, f, l)) {
+                if (nfc_trivial<K>(a.nt, a.text, a.n_bytes, a.bound, cs, f, l)) {
                     ntext[pos] = a.text[i];
                     if (nos) nos[pos] = (uint32_t)cs;
                 }

@@ -23,6 +23,7 @@
 #include <cstdint>
 
 #include "tables.hpp"
+#include "nfkc_tables.inc"          // (no NFKC_WANT_*: the generator's figures only -- NFKC_GROWTH, NFKC_MAX_DECOMP)
 
 namespace tkamd {
 
@@ -45,6 +46,18 @@ constexpr uint32_t NFC_FILL = 0x1FFFFFu;
 // ordering (Sequence[NFD, Lowercase]: one char each there -- the one char to_lowercase makes two of, U+0130, decomposes first).
 constexpr uint32_t NFD_MODE = 1u, NFD_LOWER_FIRST = 2u, NFD_LOWER_LAST = 4u, NFD_LOWER = NFD_LOWER_FIRST | NFD_LOWER_LAST;
 
+// K mode (NFKC, tables.hpp NORM_NFKC): a COMPILE-TIME mode -- template <bool K> below; NFC and NFD are the K = false instantiations and
+// read none of this.  The flags n1 / n2 are then those of nfkc_tables.inc (the same ranks, K-DECOMPOSES, "NFKC_Quick_Check is not Yes"),
+// the decompositions are the full compatibility ones, of up to NFKC_MAX_DECOMP code points: lmap (cp, 0) -> (offset, length) into
+// kflat.  The primary composites stay NFC's own (map).  A decomposition's first char has change 0 and every further one 1, as before
+// ("\uFB01" -> "fi", both aligned to the one source char).
+// The head rule is wider in K mode: thousands of chars change under NFKC on their own (every fullwidth letter, U+3000, the ligatures),
+// all ACTIVE by their quick check, and a run of them would be one segment.  There a char ALSO opens a segment when its full
+// decomposition begins with a char that is not active -- class 0, no second of a primary composite, no Hangul V / T.  That is exact:
+// such a first char is a starter that composes with nothing in front of it, so what NFKC makes of the text in front ends before it,
+// and neither the ordering nor the composition crosses it -- NFKC(p + c + s) = NFKC(p) + NFKC(c + s).
+constexpr uint32_t NFK_GROWTH = NFKC_GROWTH;      // UTF-8 bytes a source byte can stand for (U+FDFA: 3 -> 33)
+
 struct NfcTables {
     const uint16_t* n1;
     const uint8_t* n2;
@@ -52,7 +65,12 @@ struct NfcTables {
     uint32_t map_mask, map_seed;
     uint32_t mode = 0u;                  // 0: NFC
     // NFD_LOWER_*: to_lowercase in the BertNormalizer's layout -- flag 1 on every char it changes, (cp, 0) -> up to three code points
-    const uint16_t* l1 = nullptr;
+    // (K mode, which never lowercases, keeps its tables in these slots -- kflat in l1's, its pair table as lmap / lmap_mask / lmap_seed --:
+    // the struct is copied into the scratch of every lane that calls the outlined routines, and NFC's and NFD's must not grow for a mode they never run)
+    union {
+        const uint16_t* l1 = nullptr;
+        const uint32_t* kflat;           // K mode: the full compatibility decompositions, one after the other
+    };
     const uint8_t* l2 = nullptr;
     const MergeSlot* lmap = nullptr;
     uint32_t lmap_mask = 0u, lmap_seed = 0u;
@@ -69,6 +87,26 @@ TK_HD bool nfc_map(const NfcTables& t, uint32_t a, uint32_t b, uint32_t* lo, uin
     *lo = h->rank;
     *hi = h->new_id;
     return true;
+}
+// K mode: the full compatibility decomposition of cp, kflat[*off .. *off + *len)
+TK_HD bool nfk_map(const NfcTables& t, uint32_t cp, uint32_t* off, uint32_t* len) {
+    const MergeSlot& x = t.lmap[merge_hash1(cp, 0u, t.lmap_seed) & t.lmap_mask];
+    const MergeSlot& y = t.lmap[merge_hash2(cp, 0u, t.lmap_seed) & t.lmap_mask];
+    const MergeSlot* h = (x.a == cp && x.b == 0u) ? &x : (y.a == cp && y.b == 0u) ? &y : nullptr;
+    if (!h) return false;
+    *off = h->rank;
+    *len = h->new_id;
+    return true;
+}
+// does the char (flags f) open a segment wherever it stands?  One that is not active; in K mode also one whose decomposition begins with such a char
+template <bool K = false>
+TK_HD bool nfc_head(const NfcTables& t, uint32_t cp, uint32_t f) {
+    if (!(f & NFC_F_ACTIVE)) return true;
+    if constexpr (K) {
+        uint32_t off, len;
+        if ((f & NFC_F_DECOMP) && nfk_map(t, cp, &off, &len)) return !(nfc_flags(t, t.kflat[off]) & NFC_F_ACTIVE);
+    }
+    return false;
 }
 TK_HD bool nfd_lowercases(const NfcTables& t, uint32_t cp) { return cp < 0x110000u && (t.l2[((uint32_t)t.l1[cp >> 8] << 8) | (cp & 255u)] & 1u) != 0u; }
 // to_lowercase of cp: out[0 .. returned) (the char itself where it has none)
@@ -164,17 +202,20 @@ TK_HD bool nfc_check_lane(const NfcTables& t, const uint8_t* text, int64_t n, in
 
 // ---- segments
 // first byte of the segment that holds the unit starting at cs, or -1 if more than NFC_SEG_MAX chars lie between them
+template <bool K = false>
 TK_HD int64_t nfc_seg_start(const NfcTables& t, const uint8_t* text, int64_t n, const nfc_mask_t* bound, int64_t cs) {
     int64_t s = cs;
     for (int steps = 0; steps <= NFC_SEG_MAX; ++steps) {
         if (s <= 0 || nfc_bit(bound, s)) return s;
         uint32_t l;
-        if (!(nfc_flags(t, nfc_decode(text, n, s, &l)) & NFC_F_ACTIVE)) return s;
+        const uint32_t cp = nfc_decode(text, n, s, &l);
+        if (nfc_head<K>(t, cp, nfc_flags(t, cp))) return s;
         s = nfc_unit_start(text, n, s - 1);
     }
     return -1;
 }
 // the unit at s (flags f, length l) is a segment head: is the segment that unit alone, unchanged?
+template <bool K = false>
 TK_HD bool nfc_trivial(const NfcTables& t, const uint8_t* text, int64_t n, const nfc_mask_t* bound, int64_t s, uint32_t f, uint32_t l) {
     if (f & NFC_F_ACTIVE) return false;
     if (t.mode) {                                           // (NFD mode: a char that decomposes or lowercases is a segment to normalize)
@@ -185,7 +226,8 @@ TK_HD bool nfc_trivial(const NfcTables& t, const uint8_t* text, int64_t n, const
     if (p >= n || nfc_bit(bound, p)) return true;
     if (text[p] < 0x80u) return true;
     uint32_t l2;
-    return !(nfc_flags(t, nfc_decode(text, n, p, &l2)) & NFC_F_ACTIVE);
+    const uint32_t c2 = nfc_decode(text, n, p, &l2);
+    return nfc_head<K>(t, c2, nfc_flags(t, c2));
 }
 // output bytes charged to source byte k of a segment of S source bytes and O output bytes (O <= 3 S): one each as far as they go, then
 // up to two more each from the front.  A segment that keeps its length charges every byte 1, as a lane that is copied whole does.
@@ -193,6 +235,14 @@ TK_HD uint32_t nfc_charge(uint32_t k, uint32_t O, uint32_t S) {
     const uint32_t base = O < S ? O : S, extra = O - base;
     const uint32_t x = extra > 2u * k ? extra - 2u * k : 0u;
     return (k < O ? 1u : 0u) + (x > 2u ? 2u : x);
+}
+
+// the same for a growth of G a byte (K mode: NFK_GROWTH): one each as far as they go, then up to G - 1 more each from the front
+template <uint32_t G>
+TK_HD uint32_t nfc_charge_g(uint32_t k, uint32_t O, uint32_t S) {
+    const uint32_t base = O < S ? O : S, extra = O - base;
+    const uint32_t x = extra > (G - 1u) * k ? extra - (G - 1u) * k : 0u;
+    return (k < O ? 1u : 0u) + (x > G - 1u ? G - 1u : x);
 }
 
 struct NfcSeg {
@@ -215,7 +265,9 @@ TK_HD uint32_t nfc_compose(const NfcTables& t, uint32_t a, uint32_t b) {
 }
 
 // Normalizes the segment whose head is the unit at s (a char that is not active, or a piece start).  False: it holds more than
-// NFC_SEG_MAX chars or pieces (or would outgrow three times its source bytes, which no canonical decomposition does) -- nothing is valid then.
+// NFC_SEG_MAX chars or pieces (or would outgrow three times its source bytes, which no canonical decomposition does; NFK_GROWTH times in
+// K mode) -- nothing is valid then.
+template <bool K = false>
 TK_HD_OUTLINE bool nfc_segment(const NfcTables& t, const uint8_t* text, int64_t n, const nfc_mask_t* bound, int64_t s, NfcSeg& g) {
     int np = 0, nsrc = 0;
     int64_t p = s;
@@ -224,7 +276,32 @@ TK_HD_OUTLINE bool nfc_segment(const NfcTables& t, const uint8_t* text, int64_t 
         uint32_t l;
         const uint32_t cp = nfc_decode(text, n, p, &l);
         const uint32_t f = nfc_flags(t, cp);
-        if (nsrc && !(f & NFC_F_ACTIVE)) break;
+        if (nsrc && nfc_head<K>(t, cp, f)) break;
+        if constexpr (K) {                                      // (the full compatibility decomposition, of any length up to NFKC_MAX_DECOMP)
+            if (nsrc == NFC_SEG_MAX) return false;
+            uint32_t hd[3] = {cp, 0u, 0u}, off = 0u, cnt = 1u;
+            const uint32_t* dp = hd;
+            if (f & NFC_F_DECOMP) {
+                if (cp - NFC_S_BASE < NFC_S_N) {
+                    const uint32_t x = cp - NFC_S_BASE;
+                    hd[0] = NFC_L_BASE + x / (NFC_V_N * NFC_T_N);
+                    hd[1] = NFC_V_BASE + (x % (NFC_V_N * NFC_T_N)) / NFC_T_N;
+                    hd[2] = NFC_T_BASE + x % NFC_T_N;
+                    cnt = (x % NFC_T_N) ? 3u : 2u;
+                } else if (nfk_map(t, cp, &off, &cnt)) dp = t.kflat + off;
+                else cnt = 1u;
+            }
+            for (uint32_t q = 0; q < cnt; ++q) {
+                if (np == NFC_SEG_MAX) return false;
+                g.cp[np] = dp[q];
+                g.rank[np] = (uint8_t)(((f & NFC_F_DECOMP) ? nfc_flags(t, dp[q]) : f) & NFC_F_RANK);
+                g.chg[np] = (int8_t)(q ? 1 : 0);
+                ++np;
+            }
+            g.src[nsrc++] = (uint8_t)(p - s);
+            p += l;
+            continue;
+        }
         // (Lowercase in front of NFD: what it makes of the char are the source chars NFD sees, each aligned to the char)
         uint32_t lc[3] = {cp, 0u, 0u};
         const int nl = (t.mode & NFD_LOWER_FIRST) ? nfd_lower(t, cp, lc) : 1;
@@ -318,7 +395,7 @@ TK_HD_OUTLINE bool nfc_segment(const NfcTables& t, const uint8_t* text, int64_t 
     }
     g.n = no;
     g.obytes = ob;
-    return ob <= 3u * (uint32_t)(g.e - s);
+    return ob <= (K ? NFK_GROWTH : 3u) * (uint32_t)(g.e - s);
 }
 
 }  // namespace tkamd

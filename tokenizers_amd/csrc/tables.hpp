@@ -204,7 +204,10 @@ enum PretokKind {
 // NORM_CHAIN: NFD, Lowercase, StripAccents, alone or as a Sequence of them in which StripAccents stands behind NFD if both are there
 // (normalizers/unicode.rs, utils.rs, strip.rs), in front of the character-level models: context free per source char, expanded at load
 // into tables of its own that the BertNormalizer's kernels read (kernels/bert_norm.hip, BnTables::chain)
-enum NormKind { NORM_NONE = 0, NORM_BERT = 1, NORM_METASPACE = 2, NORM_NFC = 3, NORM_PRECOMPILED = 4, NORM_CHAIN = 5 };
+// NORM_NFKC: NFKC alone or Sequence[NFKC] in front of bare Metaspace (split = true) and BPE over characters or Unigram -- the reference's
+// SentencePieceBPETokenizer layout: the K mode of the NFC core (nfc_core.hpp, kernels/nfkc.hip), whose output the "▁" front reads as it
+// reads the Precompiled normalizer's
+enum NormKind { NORM_NONE = 0, NORM_BERT = 1, NORM_METASPACE = 2, NORM_NFC = 3, NORM_PRECOMPILED = 4, NORM_CHAIN = 5, NORM_NFKC = 6 };
 enum ChainMember : uint8_t { CHAIN_NFD = 0, CHAIN_LOWERCASE = 1, CHAIN_STRIP_ACCENTS = 2 };
 // where the "▁" front puts a "▁" in front of a piece (the raw text between document edges and added-token matches)
 enum MsPrepend {

@@ -546,12 +546,14 @@ class Tokenizer:
 
     def _normalized(self, text: str) -> str:
         """The normalizer's form of a short string from the host copy of the load-time tables: BertNormalizer::normalize character by
-        character, a chain of NFD / Lowercase / StripAccents (info["normalizer"] == 5) by its probe"""
-        if self.info["normalizer"] == 5:
+        character, a chain of NFD / Lowercase / StripAccents (info["normalizer"] == 5) or NFKC (6) by its probe"""
+        if self.info["normalizer"] in (5, 6):
+            nfkc = self.info["normalizer"] == 6
             raw = text.encode("utf-8")
-            cap = 3 * len(raw) + 4
+            cap = (11 if nfkc else 3) * len(raw) + 4
             buf, src, n = (C.c_uint8 * cap)(), (C.c_uint32 * cap)(), C.c_int64(0)
-            _lib.check(self._lib.tkamd_probe_norm_chain(self._h, raw, len(raw), buf, src, cap, C.byref(n)))
+            probe = self._lib.tkamd_probe_nfkc if nfkc else self._lib.tkamd_probe_norm_chain
+            _lib.check(probe(self._h, raw, len(raw), buf, src, cap, C.byref(n)))
             return bytes(buf[:n.value]).decode("utf-8")
         out, cps, n, refused = [], (C.c_uint32 * 16)(), C.c_int32(0), C.c_int32(0)
         for ch in text:
@@ -600,7 +602,7 @@ class Tokenizer:
             for a in self._effective_added(d):
                 # the token string of an added-token match is the matched slice of the NORMALIZED text (added_vocabulary.rs:497-516), i.e.
                 # the token's normalized pattern when it is matched through the normalizer
-                r[int(a["id"])] = self._normalized(a["content"]) if a.get("normalized") and self.info["normalizer"] in (1, 5) else a["content"]
+                r[int(a["id"])] = self._normalized(a["content"]) if a.get("normalized") and self.info["normalizer"] in (1, 5, 6) else a["content"]
             self._vocab_r = r
         return self._vocab_r
 
