@@ -101,9 +101,11 @@ typedef struct tkamd_info {
                                Llama-3 / cl100k, Qwen2, o200k, tekken ...; pre_tokenizers/split.rs:76-105) + ByteLevel, 3 Whitespace,
                                4 WhitespaceSplit, 5 BertPreTokenizer, 6 ByteLevel(use_regex=false), 7 the U+2581 front of SentencePiece-style BPE,
                                8 the chain of three Splits of DeepSeek-V3 / R1 + ByteLevel(use_regex=false),
-                               9 Sequence[Digits, ByteLevel(GPT-2 regex)]: StarCoder / StarCoder2 / SantaCoder, Granite code, Command-R */
+                               9 Sequence[Digits, ByteLevel(GPT-2 regex)]: StarCoder / StarCoder2 / SantaCoder, Granite code, Command-R,
+                               10 Sequence[Split(the CLIP pattern, Removed, inverted), ByteLevel]: CLIP, the text encoders of Stable Diffusion */
     int32_t normalizer;     /* 0 none, 1 BertNormalizer, 2 the U+2581 normalizers, 3 NFC, 4 Precompiled,
-                               5 NFD / Lowercase / StripAccents, alone or chained in a Sequence */
+                               5 NFD / Lowercase / StripAccents, alone or chained in a Sequence, 6 NFKC,
+                               7 Sequence[NFC, Replace(Regex "\\s+" -> " "), Lowercase] (with or without the Replace) of the CLIP files */
     int32_t vocab_size;
     int32_t n_merges;
     int32_t add_prefix_space;

@@ -151,7 +151,7 @@ int tkamd_tokenizer_info(const tkamd_tokenizer* t, tkamd_info* info) {
     const HostModel& hm = t->hm;
     info->model = (int32_t)hm.model;
     info->pre_tokenizer = (int32_t)hm.pretok;
-    info->normalizer = (int32_t)hm.norm;
+    info->normalizer = (int32_t)(hm.nfc_lower ? NORM_NFC_LOWER : hm.norm);
     info->vocab_size = (int32_t)hm.vocab_size;
     info->n_merges = (int32_t)hm.n_merges;
     info->add_prefix_space = hm.add_prefix_space;

@@ -193,7 +193,7 @@ void Batch::check_request() {
           : n_bytes + (prefix_space ? n_docs + (int64_t)mcap : 0);
     if (n_x >= (int64_t)0xFFFFFF00ll) throw Invalid("batch larger than 4 GiB: split it (byte offsets are 32-bit on the device)");
     const bool bpe_path = hm.model == MODEL_BPE && !hm.char_bpe && (hm.pretok == PT_BYTELEVEL_GPT2 || hm.pretok == PT_LLAMA3 || hm.pretok == PT_SPLIT_CHAIN || hm.pretok == PT_DIGITS_GPT2 ||
-                                                                      hm.pretok == PT_BYTELEVEL_NOREGEX);
+                                                                      hm.pretok == PT_BYTELEVEL_NOREGEX || hm.pretok == PT_CLIP);
     const bool local_pretok = hm.pretok == PT_WHITESPACE || hm.pretok == PT_WHITESPACE_SPLIT || hm.pretok == PT_BERT;
     const bool word_models = (hm.model == MODEL_WORDLEVEL || hm.model == MODEL_WORDPIECE) && local_pretok;
     const bool char_bpe = hm.model == MODEL_BPE && hm.char_bpe && (local_pretok || metaspace);      // BPE over characters rides the word models' pre-tokenizers, or the "▁" front
@@ -418,7 +418,7 @@ void Batch::normalize_nfc() {
         launch_nfc_bound(st, w->w_ms_dmask.as<ull>(), verbatim, W0 + 1);
     }
     NfcTables nt{t->t_nfc1.as<uint16_t>(), t->t_nfc2.as<uint8_t>(), t->t_nfc_map.as<MergeSlot>(), hm.nfc_mask, hm.nfc_seed};
-    if ((nt.mode = hm.nfd_mode()) & NFD_LOWER) {        // (to_lowercase rides in the BertNormalizer tables' place)
+    if ((nt.mode = hm.nfc_mode()) & NFC_ANY_LOWER) {    // (to_lowercase rides in the BertNormalizer tables' place)
         nt.l1 = t->t_bn1.as<uint16_t>(); nt.l2 = t->t_bn2.as<uint8_t>(); nt.lmap = t->t_bn_map.as<MergeSlot>();
         nt.lmap_mask = hm.bn_mask; nt.lmap_seed = hm.bn_seed;
     }
@@ -666,7 +666,12 @@ void Batch::build_x_text() {
         if (nfc_general) normalize_nfc();
         else {
             pf.begin("nfc_check");
-            launch_nfc_check(st, NfcTables{t->t_nfc1.as<uint16_t>(), t->t_nfc2.as<uint8_t>(), t->t_nfc_map.as<MergeSlot>(), hm.nfc_mask, hm.nfc_seed}, d_text, n_bytes, d_err);
+            NfcTables nt{t->t_nfc1.as<uint16_t>(), t->t_nfc2.as<uint8_t>(), t->t_nfc_map.as<MergeSlot>(), hm.nfc_mask, hm.nfc_seed};
+            if ((nt.mode = hm.nfc_mode()) & NFC_LOWER) {        // (Lowercase behind NFC: a char that lowercases is one the check does not vouch for)
+                nt.l1 = t->t_bn1.as<uint16_t>(); nt.l2 = t->t_bn2.as<uint8_t>(); nt.lmap = t->t_bn_map.as<MergeSlot>();
+                nt.lmap_mask = hm.bn_mask; nt.lmap_seed = hm.bn_seed;
+            }
+            launch_nfc_check(st, nt, d_text, n_bytes, d_err);
             pf.end();
         }
     }
@@ -761,6 +766,19 @@ void Batch::pretokenize() {
         pf.begin("pretok_digits");
         launch_pretok_digits(st, x_text, n_x, x_len_dev, w->w_docmask.as<ull>(), t->dt.uc1, t->dt.uc2, hm.digits_individual, w->w_startmask.as<ull>(),
                              lead_done ? w->w_leadmask.as<ull>() : nullptr);
+        pf.end();
+    } else if (hm.pretok == PT_CLIP) {
+        // Split(the CLIP pattern, Removed, inverted) + ByteLevel: one lane kernel writes the starts and the ends -- the \s runs belong to no
+        // pre-token -- and the lookup, the merges' queues and the offsets take the ends from the mask, as behind the word models' pre-tokenizers
+        w->w_endmask.reserve((size_t)(W + 1) * 8);
+        has_end = true;
+        if (off_mode == TKAMD_OFFSETS_CHAR && x_text == d_text && !x_len_dev && n_x == n_bytes) {
+            w->w_leadmask.reserve((size_t)(W0 + 1) * 8);
+            lead_done = true;
+        }
+        pf.begin("pretok_clip");
+        launch_pretok_clip(st, x_text, n_x, x_len_dev, w->w_docmask.as<ull>(), t->dt.uc1, t->dt.uc2, w->w_startmask.as<ull>(), w->w_endmask.as<ull>(),
+                           lead_done ? w->w_leadmask.as<ull>() : nullptr);
         pf.end();
     } else if (metaspace) {
         // every piece start (the document mask holds the match edges now) and every "▁" behind another char (or every "▁": split)

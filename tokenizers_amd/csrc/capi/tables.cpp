@@ -56,6 +56,7 @@ void upload_tables(tkamd_tokenizer* t) {
     upload(t->t_uc2, hm.uc_stage2);
     if (!hm.ucc_stage1.empty()) { upload(t->t_ucc1, hm.ucc_stage1); upload(t->t_ucc2, hm.ucc_stage2); }
     std::vector<uint32_t> bid(hm.byte_id, hm.byte_id + 256);
+    if (hm.byte_suffix) bid.insert(bid.end(), hm.byte_sfx_id, hm.byte_sfx_id + 256);      // (behind the table itself: DevTables::byte_sfx)
     upload(t->t_byte_id, bid);
     upload(t->t_merges, hm.merge_table);
     upload(t->t_merge_disp, hm.merge_disp);
@@ -115,6 +116,7 @@ void upload_tables(tkamd_tokenizer* t) {
     d.uc1 = t->t_uc1.as<uint16_t>();
     d.uc2 = t->t_uc2.as<uint8_t>();
     d.byte_id = t->t_byte_id.as<uint32_t>();
+    d.byte_sfx = hm.byte_suffix ? d.byte_id + 256 : nullptr;
     d.merges = t->t_merges.as<MergeSlot>();
     d.merge_disp = t->t_merge_disp.as<uint16_t>();
     d.merge_mask = hm.merge_mask;

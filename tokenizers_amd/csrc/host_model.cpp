@@ -769,6 +769,9 @@ bool parse_digits_bytelevel(const JsonValue* seq, HostModel& m) {
 }
 
 const char* const kMetaspace = "\xE2\x96\x81";     // U+2581, the "▁" of SentencePiece
+// the Split pattern of the CLIP files (CLIPTokenizerFast, the text encoders of Stable Diffusion / SDXL, the OpenCLIP conversions), byte for
+// byte: with behavior Removed and invert = true its matches are the pre-tokens and the \s runs between them belong to none (pretok_clip_core.hpp)
+const char* const kClipPattern = "'s|'t|'re|'ve|'m|'ll|'d|[\\p{L}]+|[\\p{N}]|[^\\s\\p{L}\\p{N}]+";
 
 // A JSON number as serde_json reads it into an f64 WITHOUT its float_roundtrip feature -- how the reference is built (tokenizers/Cargo.toml:
 // serde_json = "1.0", no features) and so what its Unigram scores are: the digits are gathered into a u64 significand (those that no
@@ -926,6 +929,24 @@ PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
                 bool invert = a->get_bool("invert", false);
                 std::string beh = a->get_str("behavior");
                 if (rx.empty()) throw Unsupported("pre_tokenizer: Split with a String pattern (only Regex patterns of the tiktoken family are on the path)");
+                if (rx == kClipPattern) {
+                    // the CLIP layout.  ByteLevel's own regex (use_regex = true, as the files have it) matches every piece this pattern can cut
+                    // as one whole, so both spellings of use_regex are the same pre-tokenizer
+                    if (!invert || beh != "Removed")
+                        throw Unsupported("pre_tokenizer: the CLIP Split pattern with behavior '" + beh + "'" + (invert ? " inverted" : ", not inverted") +
+                                          " (only Removed, inverted, is on the path: the pattern's matches are the pre-tokens)");
+                    if (b->get_bool("add_prefix_space", true))
+                        throw Unsupported("pre_tokenizer: Sequence[Split(the CLIP pattern), ByteLevel(add_prefix_space=true)] (a prefix space in front of every pre-token)");
+                    if (!m.nfc_lower)
+                        throw Unsupported("pre_tokenizer: the CLIP Split is only on the path behind the normalizer Sequence[NFC, Replace(Regex '\\s+' -> ' '), Lowercase] "
+                                          "(with or without the Replace)");
+                    m.byte_level = true;
+                    m.add_prefix_space = false;
+                    return PT_CLIP;
+                }
+                if (invert && beh == "Removed")
+                    throw Unsupported("pre_tokenizer: Split with behavior 'Removed' inverted (only Isolated is on the path; Removed, inverted, with the CLIP pattern alone, "
+                                      "which this pattern is not)");
                 if (invert || beh != "Isolated") throw Unsupported("pre_tokenizer: Split with behavior '" + beh + "'" + (invert ? " inverted" : "") + " (only Isolated is on the path)");
                 if (b->get_bool("use_regex", true)) throw Unsupported("pre_tokenizer: Sequence[Split, ByteLevel(use_regex=true)] applies two regexes");
                 // ByteLevel::pre_tokenize puts its prefix space in front of every SPLIT it is handed (byte_level.rs:122-125) -- behind a Split
@@ -1321,8 +1342,28 @@ HostModel HostModel::from_json(const char* json, size_t len) {
                    std::any_of(norm->get("normalizers")->arr.begin(), norm->get("normalizers")->arr.end(),
                                [](const JsonPtr& v) { return v && v->is_object() && v->get_str("type") == "NFC"; })) {
             // NFC alone inside a Sequence is NFC; next to any other normalizer the alignment of one is the input of the other: not on the path
-            if (norm->get("normalizers")->arr.size() != 1)
-                throw Unsupported("normalizer: NFC inside a longer Sequence is outside the hot path (only NFC alone, or Sequence[NFC], is on it)");
+            // ... but for the chain of the CLIP files, Sequence[NFC, Replace(Regex "\\s+" -> " "), Lowercase]: Lowercase is a map of single chars
+            // that the NFC core applies to what it composed (nfc_core.hpp NFC_LOWER), and the Replace only touches runs of \s chars, which the CLIP
+            // pre-tokenizer drops -- it is inert there, and no kernel runs for it.  Whether the CLIP pre-tokenizer follows is asked below.
+            const auto& arr = norm->get("normalizers")->arr;
+            if (arr.size() != 1) {
+                const std::string base = "normalizer: NFC inside a longer Sequence is outside the hot path (only NFC alone, or Sequence[NFC], is on it; and "
+                                         "Sequence[NFC, Replace(Regex '\\s+' -> ' '), Lowercase], with or without the Replace, in front of the CLIP pre-tokenizer: ";
+                auto ty = [&](size_t k) { return (arr[k] && arr[k]->is_object()) ? arr[k]->get_str("type") : std::string("?"); };
+                const bool shape = (arr.size() == 2 && ty(0) == "NFC" && ty(1) == "Lowercase") || (arr.size() == 3 && ty(0) == "NFC" && ty(1) == "Replace" && ty(2) == "Lowercase");
+                if (!shape) throw Unsupported(base + "this Sequence has other members, or these in another order)");
+                if (arr.size() == 3) {
+                    const JsonValue* pat = arr[1]->get("pattern");
+                    if (!pat || !pat->is_object() || !pat->get("Regex") || pat->get_str("Regex") != "\\s+" || arr[1]->get_str("content") != " ")
+                        throw Unsupported(base + "this Sequence's Replace is another one)");
+                }
+                const JsonValue* pt = root->get("pre_tokenizer");
+                const JsonValue* seq = (pt && pt->is_object() && pt->get_str("type") == "Sequence") ? pt->get("pretokenizers") : nullptr;
+                const JsonValue* sp = (seq && seq->is_array() && seq->arr.size() == 2 && seq->arr[0] && seq->arr[0]->is_object() && seq->arr[0]->get_str("type") == "Split")
+                                          ? seq->arr[0]->get("pattern") : nullptr;
+                if (!sp || !sp->is_object() || sp->get_str("Regex") != kClipPattern) throw Unsupported(base + "this file's pre-tokenizer is another one)");
+                m.nfc_lower = true;
+            }
             m.norm = NORM_NFC;
         } else if (chain_member(t) >= 0 || (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() &&
                                             std::any_of(norm->get("normalizers")->arr.begin(), norm->get("normalizers")->arr.end(),
@@ -1419,6 +1460,10 @@ HostModel HostModel::from_json(const char* json, size_t len) {
 
     if (m.pretok == PT_DIGITS_GPT2 && m.norm != NORM_NONE && m.norm != NORM_NFC)
         throw Unsupported("pre_tokenizer: Sequence[Digits, ByteLevel] behind a normalizer other than NFC");
+    // (the normalizer section looked at the Split's pattern alone; everything else of the CLIP pre-tokenizer was parse_pretok's to accept)
+    if (m.nfc_lower && m.pretok != PT_CLIP)
+        throw Unsupported("normalizer: NFC inside a longer Sequence is outside the hot path (only NFC alone, or Sequence[NFC], is on it; and "
+                          "Sequence[NFC, Replace(Regex '\\s+' -> ' '), Lowercase] in front of the CLIP pre-tokenizer, which this file's is not)");
 
     // ---- post-processor: offset trimming + the special tokens it puts around a single sequence ----
     {
@@ -1570,6 +1615,8 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     // Unigram keeps its vocabulary as an ARRAY of [piece, score], id = index (models/unigram/serialization.rs:13-30); every other model
     // as an object piece -> id.  Both fill the same map `v` that added tokens, templates, padding and the decode tables read.
     const bool unigram = mtype == "Unigram";
+    if (m.pretok == PT_CLIP && mtype != "BPE")
+        throw Unsupported("pre_tokenizer: the CLIP Split + ByteLevel in front of a " + mtype + " model (only in front of byte-level BPE with an end_of_word_suffix is it on the path)");
     if (m.pretok == PT_DIGITS_GPT2 && mtype != "BPE")
         throw Unsupported("pre_tokenizer: Sequence[Digits, ByteLevel] in front of a " + mtype + " model (only in front of byte-level BPE is it on the path)");
     if (unigram ? !(vocab && vocab->is_array()) : !(vocab && vocab->is_object())) throw Invalid("tokenizer.json: model.vocab missing");
@@ -1698,8 +1745,17 @@ HostModel HostModel::from_json(const char* json, size_t len) {
             if (it != v.end()) { m.has_unk = true; m.unk_id = it->second; }
         }
         m.char_bpe = !m.byte_level;
-        if (m.byte_level && (!m.bpe_prefix.empty() || !m.bpe_suffix.empty())) throw Unsupported("byte-level BPE with continuing_subword_prefix / end_of_word_suffix");
+        if (m.byte_level && (!m.bpe_prefix.empty() || !m.bpe_suffix.empty()) && (m.pretok != PT_CLIP || !m.bpe_prefix.empty()))
+            throw Unsupported("byte-level BPE with continuing_subword_prefix / end_of_word_suffix (an end_of_word_suffix is on the path behind the CLIP "
+                              "pre-tokenizer alone, with no continuing_subword_prefix)");
         if (m.byte_level && m.byte_fallback) throw Unsupported("byte-level BPE with byte_fallback");
+        if (m.pretok == PT_CLIP) {
+            if (m.bpe_suffix.empty()) throw Unsupported("pre_tokenizer: the CLIP Split + ByteLevel in front of a BPE without end_of_word_suffix is outside the hot path");
+            if (m.bpe_suffix.size() > 31) throw Unsupported("BPE continuing_subword_prefix / end_of_word_suffix longer than 31 bytes");
+            // (vocab.get(sequence) would look the text up without the suffix its entry carries: not built)
+            if (m.ignore_merges) throw Unsupported("byte-level BPE with end_of_word_suffix and ignore_merges");
+            m.byte_suffix = true;
+        }
         if (m.char_bpe) {
             // BPE over characters (BPE::merge_word, bpe/model.rs:465-550): a char's initial symbol is the vocabulary entry of the char with
             // the affixes its place in the word glues on.  Every (char, affix combination) the vocabulary knows goes into one direct
@@ -1744,8 +1800,15 @@ HostModel HostModel::from_json(const char* json, size_t len) {
             else { ch.push_back((char)(0xC0 | (cp >> 6))); ch.push_back((char)(0x80 | (cp & 0x3F))); }
             auto it = v.find(ch);
             if (it == v.end())
-                throw Unsupported("byte-level BPE vocab lacks a byte symbol (unk / byte_fallback / dropped-char paths, bpe/model.rs:501-541)");
+                throw Unsupported("byte-level BPE vocab lacks a byte symbol (unk / byte_fallback / dropped-char paths, bpe/model.rs:501-541)" +
+                                  (m.byte_suffix ? ": '" + ch + "'" : std::string()));
             m.byte_id[b] = it->second;
+            // (with all 256 chars and all 256 char + suffix entries no word ever needs the unk_token)
+            if (m.byte_suffix) {
+                it = v.find(ch + m.bpe_suffix);
+                if (it == v.end()) throw Unsupported("byte-level BPE with end_of_word_suffix: the vocab lacks '" + ch + m.bpe_suffix + "' (a byte's char with the suffix)");
+                m.byte_sfx_id[b] = it->second;
+            }
         }
         // merges (bpe/model.rs:252-275): rank = position, new_id = vocab[a+b]; duplicate pairs: last wins
         const JsonValue* mg = model->get("merges");
@@ -1857,7 +1920,7 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     }
     if (m.norm == NORM_NFC &&
         !(m.model == MODEL_BPE && !m.char_bpe && (m.pretok == PT_BYTELEVEL_GPT2 || m.pretok == PT_LLAMA3 || m.pretok == PT_SPLIT_CHAIN || m.pretok == PT_DIGITS_GPT2 ||
-                                                  m.pretok == PT_BYTELEVEL_NOREGEX)))
+                                                  m.pretok == PT_BYTELEVEL_NOREGEX || m.pretok == PT_CLIP)))
         throw Unsupported("normalizer: NFC is only on the path in front of byte-level BPE (ByteLevel, or a Split of the tiktoken family + ByteLevel); "
                           "in front of BPE over characters, WordPiece, WordLevel or the U+2581 front it is not");
     if (m.norm == NORM_CHAIN && !(m.model == MODEL_WORDPIECE || m.model == MODEL_WORDLEVEL || (m.model == MODEL_BPE && m.char_bpe)))
@@ -1881,10 +1944,14 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     // without it cannot be a word's last symbol, let alone the whole word) -- each is then run through the device's merge kernel and
     // only kept if the result is exactly its own id (capi.cpp verify_direct_words).  ignore_merges looks the TEXT up as it stands
     // (vocab.get(sequence), bpe/model.rs:559-567): no stripping there.
-    if (m.char_bpe && !m.ignore_merges && !m.bpe_suffix.empty()) {
+    // Byte-level BPE with a suffix (behind PT_CLIP) alike: raw_tokens are the entries' raw bytes, so the suffix is taken off in its raw form.
+    if ((m.char_bpe || m.byte_suffix) && !m.ignore_merges && !m.bpe_suffix.empty()) {
         (void)n_raw_plain;
+        std::string sfx = m.bpe_suffix;
+        if (m.byte_suffix && !bytelevel_to_raw(m.bpe_suffix, c2b, &sfx))
+            throw Unsupported("byte-level BPE with an end_of_word_suffix that holds a char outside the byte-level alphabet");
         for (std::string& r : m.raw_tokens) {
-            if (r.size() > m.bpe_suffix.size() && r.compare(r.size() - m.bpe_suffix.size(), m.bpe_suffix.size(), m.bpe_suffix) == 0) r.resize(r.size() - m.bpe_suffix.size());
+            if (r.size() > sfx.size() && r.compare(r.size() - sfx.size(), sfx.size(), sfx) == 0) r.resize(r.size() - sfx.size());
             else r.clear();
         }
         // (two entries may now share a text -- "ab</w>" and a stray "ab</w></w>" -- : the table wants distinct keys, the first one stays)
@@ -1946,6 +2013,7 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     build_unicode(m);
     if (m.norm == NORM_BERT) build_bert_norm(m);
     if (m.norm == NORM_NFC) build_nfc_tables(m);
+    if (m.nfc_lower) build_norm_chain(m, {CHAIN_LOWERCASE});        // (to_lowercase alone in the chain's layout, as NFD's modes have it)
     if (m.norm == NORM_NFKC) build_nfkc_tables(m);
     if (m.norm == NORM_CHAIN && !m.nfd_mode()) build_norm_chain(m, m.chain);
     if (m.nfd_mode()) {                                      // (the NFC normalizer's tables, and to_lowercase alone in the chain's layout)
@@ -2213,7 +2281,7 @@ std::string HostModel::nfkc_normalize(const std::string& s, std::vector<uint32_t
 
 std::string HostModel::nfc_normalize(const std::string& s, std::vector<uint32_t>* norig, bool* refused) const {
     NfcTables t{nfc_stage1.data(), nfc_stage2.data(), nfc_map.data(), nfc_mask, nfc_seed};
-    if ((t.mode = nfd_mode()) & NFD_LOWER) { t.l1 = bn_stage1.data(); t.l2 = bn_stage2.data(); t.lmap = bn_map.data(); t.lmap_mask = bn_mask; t.lmap_seed = bn_seed; }
+    if ((t.mode = nfc_mode()) & NFC_ANY_LOWER) { t.l1 = bn_stage1.data(); t.l2 = bn_stage2.data(); t.lmap = bn_map.data(); t.lmap_mask = bn_mask; t.lmap_seed = bn_seed; }
     return nfc_normalize_piece<false>(t, s, norig, refused);
 }
 

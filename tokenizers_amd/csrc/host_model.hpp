@@ -70,6 +70,12 @@ struct HostModel {
         return 1u | (!chain_has(CHAIN_LOWERCASE) ? 0u : chain[0] == CHAIN_LOWERCASE ? 2u : 4u);
     }
 
+    // NORM_NFC with Lowercase behind it: Sequence[NFC, Replace(Regex "\\s+" -> " "), Lowercase] of the CLIP files, or the same without the
+    // Replace (inert in front of the CLIP pre-tokenizer: no \s char ever reaches a pre-token).  tkamd_info reports NORM_NFC_LOWER
+    bool nfc_lower = false;
+    // the mode bits of the NFC core (nfc_core.hpp) this file's normalizer runs it in: 0 for NFC itself
+    uint32_t nfc_mode() const { return nfc_lower ? 8u : nfd_mode(); }
+
     // the "▁" front (PT_METASPACE): where a piece gets its "▁" (tables.hpp MsPrepend), and whether every "▁" starts a pre-token
     // (Metaspace split = true) or the device cuts a piece into units at every "▁" behind a char other than "▁" (proved exact at load)
     MsPrepend ms_prepend = MS_NEVER;
@@ -162,6 +168,10 @@ struct HostModel {
     bool unk_configured = false;        // an unk_token is set (has_unk: ... and the vocabulary holds it; else UnkTokenOutOfVocabulary when first needed)
     bool fuse_unk = false, byte_fallback = false;
     std::string bpe_prefix, bpe_suffix; // continuing_subword_prefix / end_of_word_suffix ("" = none)
+    // byte-level BPE with an end_of_word_suffix (behind PT_CLIP only): byte -> id of (its char + the suffix), the symbol a word's LAST byte
+    // starts as (BPE::merge_word glues the suffix to the last char, bpe/model.rs:486-491); byte_id[] stays every other byte's
+    bool byte_suffix = false;
+    uint32_t byte_sfx_id[256];
     // char -> id of its one-symbol token, indexed by (code point << 2 | variant), variant bit 0: the prefix is glued on (not the word's first
     // char), bit 1: the suffix (its last char); CHAR_NONE: the vocabulary has no such entry.  Direct indexed: 0x110000 x 4 words (17 MB)
     std::vector<uint32_t> char_id;

@@ -38,6 +38,7 @@
 #include "pretok_l3_core.hpp"
 #include "pretok_ds3_core.hpp"
 #include "pretok_digits_core.hpp"
+#include "pretok_clip_core.hpp"
 #include "pretok_local_core.hpp"
 #include "unigram_core.hpp"
 #include "tables.hpp"
@@ -89,6 +90,7 @@ static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)(
 #include "kernels/pretok_llama3.hip"
 #include "kernels/pretok_ds3.hip"
 #include "kernels/pretok_digits.hip"
+#include "kernels/pretok_clip.hip"
 #include "kernels/pretok_local.hip"
 #include "kernels/bert_norm.hip"
 #include "kernels/nfc.hip"

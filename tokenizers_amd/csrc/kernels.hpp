@@ -14,6 +14,7 @@ struct DevTables {
     const uint16_t* uc1;          // unicode stage 1
     const uint8_t* uc2;           // unicode stage 2
     const uint32_t* byte_id;      // [256]
+    const uint32_t* byte_sfx;     // [256] byte-level BPE with an end_of_word_suffix: the id a word's LAST byte starts as (its char + the suffix); else null
     const MergeSlot* merges;          // perfect-hash table (one slot per key)
     const uint16_t* merge_disp;       // bucket displacements
     uint32_t merge_mask, merge_seed, merge_bmask;
@@ -412,6 +413,10 @@ void launch_pretok_ds3(hipStream_t st, const uint8_t* text, int64_t n_bytes, con
 // uc2 carries UC_RUST_N; individual: Digits(individual_digits)
 void launch_pretok_digits(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* docmask,
                           const uint16_t* uc1, const uint8_t* uc2, bool individual, unsigned long long* startmask, unsigned long long* leadmask = nullptr);
+// Split(the CLIP pattern, Removed, inverted) + ByteLevel (PT_CLIP, pretok_clip_core.hpp): launch_pretok_gpt2's arguments and the end mask
+// ((n_bytes >> 6) + 1 words: an end bit can sit at byte n_bytes)
+void launch_pretok_clip(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* docmask,
+                        const uint16_t* uc1, const uint8_t* uc2, unsigned long long* startmask, unsigned long long* endmask, unsigned long long* leadmask = nullptr);
 void launch_leadmask(hipStream_t st, const uint8_t* text, int64_t n_bytes, unsigned long long* leadmask);
 void launch_seq_regroup(hipStream_t st, const int64_t* seq_off, int64_t n_seqs, int64_t n_words, const int64_t* word_tok_off, int64_t* seq_tok_off, uint32_t* widx,
                         int64_t* first_tok);

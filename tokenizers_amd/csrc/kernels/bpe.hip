@@ -128,6 +128,7 @@ __global__ __launch_bounds__(256) void k_bpe_merge(DevTables t, const uint8_t* _
         valid = valid && len != 0u;                                 // length 0: retired by k_long_vocab
         bool act = (uint32_t)c < len;
         uint32_t id = act ? t.byte_id[text[s + c]] : 0xFFFFFFFFu;
+        if (t.byte_sfx && act && (uint32_t)c + 1u == len) id = t.byte_sfx[text[s + c]];      // (uniform test) end_of_word_suffix: the last byte's symbol carries it
         uint64_t am = (len >= 64) ? ~0ull : ((1ull << len) - 1ull);   // alive symbols of my pre-token
         uint32_t rank = RANK_NONE, new_id = 0;
         {
@@ -263,6 +264,11 @@ __global__ __launch_bounds__(256) void k_bpe_merge_lane(DevTables t, const uint8
             ids[i] = s_byte_id[b];
             rk[i] = RANK_NONE;
             nd[i] = 0;
+        }
+        if (t.byte_sfx) {                                   // (uniform) end_of_word_suffix: the last byte's symbol carries it
+            const uint32_t sid = (valid && len) ? t.byte_sfx[text[s + len - 1u]] : 0u;
+#pragma unroll
+            for (int i = 0; i < S; ++i) ids[i] = (valid && (uint32_t)(i + 1) == len) ? sid : ids[i];
         }
 #pragma unroll
         for (int i = 0; i < S - 1; ++i)
@@ -443,6 +449,12 @@ __device__ __forceinline__ void bpe_merge_lds_unit(const DevTables& t, const uin
                 for (int i = 0; i < S; ++i) {
                     ids[i] = s_byte_id[TKAMD_BYTE_AT(i)];
                     if (!SYM_REGS) my_sym[i * NL] = ids[i];
+                }
+                if (t.byte_sfx) {                           // (uniform) end_of_word_suffix: the last byte's symbol carries it, in front of the first probes
+                    const uint32_t sid = (valid && len) ? t.byte_sfx[text[s + len - 1u]] : 0u;
+#pragma unroll
+                    for (int i = 0; i < S; ++i) ids[i] = (valid && (uint32_t)(i + 1) == len) ? sid : ids[i];
+                    if (!SYM_REGS && valid && len) my_sym[(len - 1u) * NL] = sid;
                 }
                 // The first probes, one per pair of neighbours: EIGHT at a time, unconditionally (a lane whose word ends earlier probes the
                 // pair of whatever its padding bytes map to and drops the answer) -- the eight loads are in flight together, where a probe
@@ -783,7 +795,7 @@ __global__ __launch_bounds__(256) void k_bpe_merge_long(DevTables t, const uint8
         __syncthreads();
         if (!(t.cb & CB_ON)) {                             // (uniform) byte-level: a symbol per byte
             for (uint32_t i = tid; i < len; i += 256) {
-                sym[i] = t.byte_id[text[s + i]];
+                sym[i] = (t.byte_sfx && i + 1 == len) ? t.byte_sfx[text[s + i]] : t.byte_id[text[s + i]];      // (end_of_word_suffix: on the last byte's symbol)
                 nxt[i] = (i + 1 < len) ? (uint16_t)(i + 1) : (uint16_t)0xFFFF;
                 prv[i] = (i > 0) ? (uint16_t)(i - 1) : (uint16_t)0xFFFF;
             }

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void k_bpe_merge_huge(DevTables t, const uint8
         unsigned long long* cmin = (unsigned long long*)(prv + len + ((base_s + 5ull * len) & 1ull));   // 8-byte aligned
         if (!(t.cb & CB_ON)) {                                       // (uniform) byte-level: a symbol per byte
             for (uint32_t i = tid; i < len; i += 256) {
-                sym[i] = t.byte_id[text[s + i]];
+                sym[i] = (t.byte_sfx && i + 1 == len) ? t.byte_sfx[text[s + i]] : t.byte_id[text[s + i]];      // (end_of_word_suffix: on the last byte's symbol)
                 nxt[i] = (i + 1 < len) ? i + 1 : 0xFFFFFFFFu;
                 prv[i] = (i > 0) ? i - 1 : 0xFFFFFFFFu;
             }

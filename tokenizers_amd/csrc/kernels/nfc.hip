@@ -32,7 +32,13 @@ __global__ __launch_bounds__(256) void k_nfc_check(NfcTables nt, const uint8_t* 
     bool bad = false;
     if (i0 < n_bytes) {
         const Unaligned16 t = *(const Unaligned16*)(text + i0);                 // (any alignment; readable TEXT_PAD bytes past the end)
-        if (((t.a | t.b | t.c | t.d) & SW_H) != 0u) bad = nfc_check_lane(nt, text, n_bytes, i0);
+        bool look = ((t.a | t.b | t.c | t.d) & SW_H) != 0u;
+        if (nt.mode & NFC_LOWER) {                            // (Lowercase behind NFC: an upper-case ASCII letter changes too)
+            const uint32_t x[4] = {t.a, t.b, t.c, t.d};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) look = look || (~sw_lt(x[k], 0x41u) & sw_lt(x[k], 0x5Bu) & SW_H) != 0u;
+        }
+        if (look) bad = nfc_check_lane(nt, text, n_bytes, i0);
     }
     if (__ballot(bad) != 0ull && lane_id() == 0) atomicOr(note, NOTE_NFC_SEEN);
 }
@@ -187,7 +193,7 @@ __global__ __launch_bounds__(256) void k_nfc_write(NfcArgs a, BnOlen olen, const
     if (lt & BN_LTOT_PLAIN) {
         const Unaligned16 t = *(const Unaligned16*)(a.text + i0);
         const bool ascii = ((t.a | t.b | t.c | t.d) & SW_H) == 0u;
-        if (ascii && (a.nt.mode & NFD_LOWER)) {                // (Lowercase is a member: A-Z -> a-z on the copy, as in k_bn_write)
+        if (ascii && (a.nt.mode & NFC_ANY_LOWER)) {                // (Lowercase is a member: A-Z -> a-z on the copy, as in k_bn_write)
             uint32_t x[4] = {t.a, t.b, t.c, t.d};
 #pragma unroll
             for (int k = 0; k < 4; ++k) x[k] += (~sw_lt(x[k], 0x41u) & sw_lt(x[k], 0x5Bu) & SW_H) >> 2;

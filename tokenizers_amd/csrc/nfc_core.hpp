@@ -45,6 +45,12 @@ constexpr uint32_t NFC_FILL = 0x1FFFFFu;
 // (Sequence[Lowercase, NFD]: a char it makes two of is two source chars to NFD, both aligned to the one) or to every piece behind the
 // ordering (Sequence[NFD, Lowercase]: one char each there -- the one char to_lowercase makes two of, U+0130, decomposes first).
 constexpr uint32_t NFD_MODE = 1u, NFD_LOWER_FIRST = 2u, NFD_LOWER_LAST = 4u, NFD_LOWER = NFD_LOWER_FIRST | NFD_LOWER_LAST;
+// NFC_LOWER (Sequence[NFC, Lowercase] of the CLIP files, tables.hpp NORM_NFC_LOWER): the segments of NFC, composed as NFC composes them,
+// and to_lowercase -- the same tables, in the same slots -- applied to every char of the composed segment.  What it makes of one char
+// (two of U+0130) is aligned to the source char that char was aligned to.  A char that lowercases changes on its own, like one that
+// decomposes in NFD mode: it is no trivial segment, no plain lane (but for all-ASCII lanes, lowercased on the copy), and the quick
+// check does not vouch for it.
+constexpr uint32_t NFC_LOWER = 8u, NFC_ANY_LOWER = NFD_LOWER | NFC_LOWER;
 
 // K mode (NFKC, tables.hpp NORM_NFKC): a COMPILE-TIME mode -- template <bool K> below; NFC and NFD are the K = false instantiations and
 // read none of this.  The flags n1 / n2 are then those of nfkc_tables.inc (the same ranks, K-DECOMPOSES, "NFKC_Quick_Check is not Yes"),
@@ -126,7 +132,10 @@ TK_HD int nfd_lower(const NfcTables& t, uint32_t cp, uint32_t* out) {
     return k;
 }
 // NFD mode: does the char (flags f) change on its own -- a decomposition, a lowercase form?
-TK_HD bool nfd_changes(const NfcTables& t, uint32_t cp, uint32_t f) { return (f & 0x40u) != 0u || ((t.mode & NFD_LOWER) && nfd_lowercases(t, cp)); }
+// (NFC_LOWER: a lowercase form alone -- a char that decomposes and composes again is NFC as it stands)
+TK_HD bool nfd_changes(const NfcTables& t, uint32_t cp, uint32_t f) {
+    return ((t.mode & NFD_MODE) && (f & 0x40u) != 0u) || ((t.mode & NFC_ANY_LOWER) && nfd_lowercases(t, cp));
+}
 TK_HD uint32_t nfc_utf8_len(uint32_t cp) { return cp < 0x80u ? 1u : cp < 0x800u ? 2u : cp < 0x10000u ? 3u : 4u; }
 TK_HD uint32_t nfc_utf8_put(uint8_t* o, uint32_t c) {
     if (c < 0x80u) { o[0] = (uint8_t)c; return 1u; }
@@ -179,11 +188,16 @@ TK_HD bool nfc_check_lane(const NfcTables& t, const uint8_t* text, int64_t n, in
     const int64_t i1 = i0 + NFC_LANE < n ? i0 + NFC_LANE : n;
     for (int64_t i = i0; i < i1; ++i) {
         const uint32_t b = text[i];
-        if (b < 0x80u) { prev = 0u; continue; }
+        if (b < 0x80u) {
+            if ((t.mode & NFC_LOWER) && b - 0x41u < 26u) return true;
+            prev = 0u;
+            continue;
+        }
         if (b < 0xC0u) continue;
         uint32_t l;
-        const uint32_t f = nfc_flags(t, nfc_decode(text, n, i, &l));
+        const uint32_t cp = nfc_decode(text, n, i, &l), f = nfc_flags(t, cp);
         if (f & NFC_F_QCN) return true;
+        if ((t.mode & NFC_LOWER) && nfd_lowercases(t, cp)) return true;
         const uint32_t r = f & NFC_F_RANK;
         if (r) {
             if (prev == 0xFFFFFFFFu) {
@@ -351,7 +365,8 @@ TK_HD_OUTLINE bool nfc_segment(const NfcTables& t, const uint8_t* text, int64_t 
     bool have = false;
     uint32_t kc = 0, last = 0;                             // last: class of the char buffered last (0: none is buffered)
     int kh = 0;
-    if (t.mode) {                                          // NFD: the ordered pieces are the output; Lowercase behind it maps each to one char
+    const bool nfd = (t.mode & NFD_MODE) != 0u;
+    if (nfd) {                                             // NFD: the ordered pieces are the output; Lowercase behind it maps each to one char
         no = np;
         if (t.mode & NFD_LOWER_LAST)
             for (int k = 0; k < np; ++k) {
@@ -360,7 +375,7 @@ TK_HD_OUTLINE bool nfc_segment(const NfcTables& t, const uint8_t* text, int64_t 
                 g.cp[k] = lc[0];
             }
     }
-    for (int i = 0; i < np && !t.mode; ++i) {
+    for (int i = 0; i < np && !nfd; ++i) {
         const uint32_t c = g.cp[i], r = g.rank[i];
         const int h = g.chg[i];
         if (!have) {
@@ -392,6 +407,20 @@ TK_HD_OUTLINE bool nfc_segment(const NfcTables& t, const uint8_t* text, int64_t 
             ptr += 1 - h;
         }
         ob += nfc_utf8_len(g.cp[k]);
+    }
+    if (t.mode & NFC_LOWER) {                              // to_lowercase of every composed char, back to front in place
+        uint32_t lc[3];
+        int add = 0;
+        for (int k = 0; k < no; ++k) add += nfd_lower(t, g.cp[k], lc) - 1;
+        if (no + add > NFC_SEG_MAX) return false;
+        ob = 0;
+        for (int k = no - 1, w = no + add; k >= 0; --k) {
+            const int nl = nfd_lower(t, g.cp[k], lc);
+            const uint8_t al = g.al[k];
+            w -= nl;
+            for (int u = 0; u < nl; ++u) { g.cp[w + u] = lc[u]; g.al[w + u] = al; ob += nfc_utf8_len(lc[u]); }
+        }
+        no += add;
     }
     g.n = no;
     g.obytes = ob;

@@ -195,7 +195,8 @@ enum PretokKind {
     PT_BYTELEVEL_NOREGEX = 6,// ByteLevel(use_regex=false): whole doc is one pre-token
     PT_METASPACE = 7,        // the "▁" front of SentencePiece-style BPE: Metaspace (metaspace.rs:122-146), or null behind NORM_METASPACE
     PT_SPLIT_CHAIN = 8,      // Sequence[Split(\p{N}{1,3}), Split(CJK class +), Split(stage 3), ByteLevel(use_regex=false)]: DeepSeek-V3 / R1 (pretok_ds3_core.hpp)
-    PT_DIGITS_GPT2 = 9       // Sequence[Digits(individual_digits), ByteLevel(use_regex=true)]: StarCoder, Granite code, Command-R (pretok_digits_core.hpp)
+    PT_DIGITS_GPT2 = 9,      // Sequence[Digits(individual_digits), ByteLevel(use_regex=true)]: StarCoder, Granite code, Command-R (pretok_digits_core.hpp)
+    PT_CLIP = 10             // Sequence[Split(the CLIP pattern, Removed, inverted), ByteLevel(add_prefix_space=false)]: CLIP, Stable Diffusion's text encoders (pretok_clip_core.hpp)
 };
 // NORM_METASPACE: Sequence[Prepend("▁"), Replace(" " -> "▁")] or Replace(" " -> "▁") alone (prepend.rs:16-24, replace.rs:83)
 // NORM_NFC: NFC alone or Sequence[NFC] (normalizers/unicode.rs), in front of byte-level BPE (nfc_core.hpp, kernels/nfc.hip)
@@ -207,7 +208,10 @@ enum PretokKind {
 // NORM_NFKC: NFKC alone or Sequence[NFKC] in front of bare Metaspace (split = true) and BPE over characters or Unigram -- the reference's
 // SentencePieceBPETokenizer layout: the K mode of the NFC core (nfc_core.hpp, kernels/nfkc.hip), whose output the "▁" front reads as it
 // reads the Precompiled normalizer's
-enum NormKind { NORM_NONE = 0, NORM_BERT = 1, NORM_METASPACE = 2, NORM_NFC = 3, NORM_PRECOMPILED = 4, NORM_CHAIN = 5, NORM_NFKC = 6 };
+// NORM_NFC_LOWER: Sequence[NFC, Replace(Regex "\\s+" -> " "), Lowercase] (or without the Replace, which is inert there) in front of the CLIP
+// pre-tokenizer: the NFC core composes, then lowercases every char of the composed segment (nfc_core.hpp NFC_LOWER).  It is what
+// tkamd_info reports; HostModel::norm stays NORM_NFC with nfc_lower set, so every path of the NFC normalizer serves it
+enum NormKind { NORM_NONE = 0, NORM_BERT = 1, NORM_METASPACE = 2, NORM_NFC = 3, NORM_PRECOMPILED = 4, NORM_CHAIN = 5, NORM_NFKC = 6, NORM_NFC_LOWER = 7 };
 enum ChainMember : uint8_t { CHAIN_NFD = 0, CHAIN_LOWERCASE = 1, CHAIN_STRIP_ACCENTS = 2 };
 // where the "▁" front puts a "▁" in front of a piece (the raw text between document edges and added-token matches)
 enum MsPrepend {
