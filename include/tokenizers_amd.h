@@ -397,7 +397,8 @@ int tkamd_profile_read(tkamd_tokenizer* tok, tkamd_stage_time* stages, int max_s
  * kernel, out[1] = to the 64-lane kernel, out[2] = to the workgroup (long) kernel.  Behind the batch's counters and the handle's
  * adaptive settings (out[13..17]), the shape of the load-time tables, filled from the handle also before its first batch:
  * out[18] = slots of the short-word table, out[19] = its displacement buckets, out[20] = its largest displacement,
- * out[21] = slots of the merge table (out[18..20] are 0 on a host-only handle). */
+ * out[21] = slots of the merge table (out[18..20] are 0 on a host-only handle).  out[22] = the grid of the last batch's launch that
+ * merges both LDS queues side by side (0: the batch ran none). */
 int tkamd_profile_counters(tkamd_tokenizer* tok, uint32_t* out, int n);
 
 /* Where the two longest kernels spend their time.  With the test hook TKAMD_PHASES (TKAMD_TEST_HOOKS=1 TKAMD_PHASES=1) the whole-word

@@ -34,6 +34,7 @@ static std::unique_ptr<tkamd_tokenizer> make_tokenizer(const char* json, size_t 
         if (const char* e = test_hook("TKAMD_NFC_SPEC")) t->nfc_spec_len = std::max(0, atoi(e));      // (0: always normalize; n: the pause behind a failed quick check)
         t->cp_grid = compact_grid(t->n_cu);
         if (const char* e = test_hook("TKAMD_CP_GRID")) t->cp_grid = std::max(1, atoi(e));      // test hook: an over- / under-subscribed compaction
+        if (const char* e = test_hook("TKAMD_MERGE_PAIR_GRID")) t->pair_grid = std::max(1, atoi(e));      // test hook: a pair merge of a few workgroups, every boundary of its plan within a few thousand words
         t->devices.push_back(device);
     }
     return t;

@@ -61,6 +61,7 @@ struct Workspace {
     int64_t last_n_enc = -1;                    // encodings of the last call when it materialised overflowing ones, else -1
     int last_ntok_slot = 1;
     uint32_t last_counters[CNT_COUNT] = {0};
+    uint32_t last_pair_grid = 0;     // grid of the batch's k_bpe_merge_lds_pair launch (0: it ran none) -- tkamd_profile_counters out[22]
     bool force_general = false;                  // the next run of the pipeline does not speculate on the added tokens (it repeats a batch that met one)
     bool force_nfc = false;                      // the next run of the pipeline normalizes outright (it repeats a batch k_nfc_check could not vouch for)
     bool last_note_nfc = false;                  // the batch synchronised last was run over the text as it came and holds a lane that is not known to be NFC
@@ -99,6 +100,7 @@ struct tkamd_tokenizer {
     int n_direct = 0;
     int n_hot = 0;
     uint32_t shortw_max_disp = 0;        // the largest displacement of the short-word table (diagnostics: tkamd_profile_counters)
+    int pair_grid = 0;           // grid of k_bpe_merge_lds_pair under the test hook TKAMD_MERGE_PAIR_GRID (0: what is resident on the CUs)
     int cp_grid = 0;             // grid of k_compact: what is resident at once (any grid makes progress -- its look-back helps itself --, TKAMD_CP_GRID)
     // In-batch claims on text that shares nothing (every candidate word distinct): the claim traffic then buys nothing and costs a third
     // of the step (the claims' worst case).  Inside a batch every lookup workgroup gives the claims up by itself once

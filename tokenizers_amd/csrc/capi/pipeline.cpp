@@ -912,6 +912,7 @@ void Batch::run_model() {
         const char* const pair_hook = test_hook("TKAMD_MERGE_PAIR");
         const bool pair = can_one && !(pair_hook && pair_hook[0] == '0');
         const bool one = can_one && !pair;
+        w->last_pair_grid = 0u;
         // BPE over characters: only the kernels that know its start (kernels/bpe.hip CHARS) -- the two LDS kernels, each on its own queue,
         // and the workgroup-per-pre-token kernel for everything beyond 32 bytes (or for everything, when the vocabulary's new ids are not
         // in merge order and the LDS kernels cannot run)
@@ -951,7 +952,7 @@ void Batch::run_model() {
         } else {
             if (pair) {
                 pf.begin("bpe_merge_lds_pair");
-                launch_bpe_merge_pair(st, t->n_cu, mdt, x_text, plan.v[0], plan.v[1], w->w_rows.p, w->w_tmp_ids.as<uint32_t>(), tmp_end);
+                w->last_pair_grid = (uint32_t)launch_bpe_merge_pair(st, t->n_cu, t->pair_grid, mdt, x_text, plan.v[0], plan.v[1], w->w_rows.p, w->w_tmp_ids.as<uint32_t>(), tmp_end);
                 pf.end();
             } else {
                 pf.begin(lds ? "bpe_merge_lds32" : "bpe_merge_lane32");

@@ -260,6 +260,7 @@ int tkamd_profile_counters(tkamd_tokenizer* t, uint32_t* out, int n) {
         if (!w) return TKAMD_OK;
         for (int i = 0; i < n && i < CNT_COUNT; ++i) out[i] = w->last_counters[i];
         if (n > 13) out[13] = (uint32_t)pair_merge_occupancy();            // (workgroups of k_bpe_merge_lds_pair resident per CU: its grid is that x the CUs)
+        if (n > 22) out[22] = w->last_pair_grid;                           // (the grid the last batch launched k_bpe_merge_lds_pair on: that x the CUs, or the test hook TKAMD_MERGE_PAIR_GRID)
         if (n > 14) out[14] = (uint32_t)std::max(0, t->added_spec_pause.load());      // (batches that will not speculate on the added tokens: a batch met one)
         if (n > 15) out[15] = t->q16_div;                                  // (the <= 16-byte queue's divisor: shrinks when a batch had to be run again)
         if (n > 16) out[16] = (uint32_t)std::max(0, t->nfc_spec_pause.load());        // (batches that will run the NFC normalizer outright: a batch failed the quick check)

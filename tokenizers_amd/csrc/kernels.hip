@@ -31,6 +31,7 @@
 #include "device_utils.hpp"
 #include "kernels.hpp"
 #include "overflow_core.hpp"
+#include "merge_pair_plan_core.hpp"
 #include "bert_norm_core.hpp"
 #include "nfc_core.hpp"
 #include "precompiled_core.hpp"

@@ -360,8 +360,9 @@ void launch_lookup(hipStream_t st, int grid, const DevTables& t, const uint8_t* 
 // also (group 6 only): a second queue for the same launch
 void launch_bpe_merge(hipStream_t st, int grid, int group, const DevTables& t, const uint8_t* text, const QView& v, void* rows,
                       uint32_t* tmp_ids, uint32_t* tmp_end, const QView* also = nullptr);
-// both LDS merge queues in one launch, side by side (k_bpe_merge_lds_pair; its grid is what is resident on n_cu CUs)
-void launch_bpe_merge_pair(hipStream_t st, int n_cu, const DevTables& t, const uint8_t* text, const QView& v16, const QView& v32, void* rows,
+// both LDS merge queues in one launch, side by side (k_bpe_merge_lds_pair; its grid is what is resident on n_cu CUs, or grid_hook > 0: the
+// test hook TKAMD_MERGE_PAIR_GRID); returns the grid it launched
+int launch_bpe_merge_pair(hipStream_t st, int n_cu, int grid_hook, const DevTables& t, const uint8_t* text, const QView& v16, const QView& v32, void* rows,
                            uint32_t* tmp_ids, uint32_t* tmp_end);
 int pair_merge_occupancy();       // workgroups of k_bpe_merge_lds_pair resident per CU (after prepare_long_kernel)
 // the normaliser's count arrays share one buffer: n_bytes + 64 per-byte counts (written for the lanes that are not plain only), then

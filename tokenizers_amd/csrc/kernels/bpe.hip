@@ -352,6 +352,10 @@ __global__ __launch_bounds__(256) void k_bpe_merge_lane(DevTables t, const uint8
 template __global__ void k_bpe_merge_lane<16>(DevTables, const uint8_t*, QView, uint4*, uint32_t*, uint32_t*);
 template __global__ void k_bpe_merge_lane<32>(DevTables, const uint8_t*, QView, uint4*, uint32_t*, uint32_t*);
 
+// c ? a : b over VALUES (the select trees of the LDS merge below): `c ? ids[1] : ids[0]` written out chooses between two places of the
+// array and loads once -- a dynamic index, which sends a register array to scratch
+__device__ __forceinline__ uint32_t sel32(bool c, uint32_t a, uint32_t b) { return c ? a : b; }
+
 // =================================================================================================
 // K_bpe_merge_lds: the lane-per-pre-token merge loop with the Word in LDS instead of registers.
 // The register kernel above indexes its arrays with compile-time indices only, so every dynamic access is a
@@ -424,16 +428,27 @@ __device__ __forceinline__ void bpe_merge_lds_unit(const DevTables& t, const uin
         uint32_t* my_sym = s_sym + tid;
         // SYM_REGS: symbols stay in registers (a dynamic index is a select chain -- the ALU has the headroom) and only
         // the keys take LDS, which is what bounds the number of pre-tokens in flight per CU.  The selects are written
-        // out at every use: taking the array's address (a lambda, a helper) would send it to scratch.
+        // out at every use: taking the array's address (a lambda, a helper) would send it to scratch.  A select is a binary tree over
+        // the bits of the position (pos < S): S - 1 conditional moves under log2(S) conditions, where the linear chain of
+        // `pos == q ? ids[q] : ..` took S - 1 compares on top of its S - 1 moves.  (The CHARS start below still finds a symbol's right
+        // neighbour with the linear chain: once per symbol in front of the loop, not once per merge.)
         uint32_t ids[S];
 #define TKAMD_SYM_AT(dst, pos)                                                                 \
         do {                                                                                   \
             if (!SYM_REGS) (dst) = my_sym[(pos) * NL];                                         \
             else {                                                                             \
-                (dst) = ids[0];                                                                \
-                _Pragma("unroll") for (int q_ = 1; q_ < S; ++q_) (dst) = ((pos) == (uint32_t)q_) ? ids[q_] : (dst); \
+                const bool b0_ = ((pos) & 1u) != 0u, b1_ = ((pos) & 2u) != 0u, b2_ = ((pos) & 4u) != 0u, b3_ = ((pos) & 8u) != 0u; \
+                const uint32_t lo_ = TKAMD_SEL16(0);                                           \
+                (dst) = (S == 32) ? sel32(((pos) & 16u) != 0u, TKAMD_SEL16(16), lo_) : lo_;    \
             }                                                                                  \
         } while (0)
+        // (depth first, a subtree's few intermediate values at a time; an index beyond the array, in the instantiation that has no such
+        // subtree, names ids[0])
+#define TKAMD_SEL1(i_) ids[(i_) < S ? (i_) : 0]
+#define TKAMD_SEL2(i_) sel32(b0_, TKAMD_SEL1((i_) + 1), TKAMD_SEL1(i_))
+#define TKAMD_SEL4(i_) sel32(b1_, TKAMD_SEL2((i_) + 2), TKAMD_SEL2(i_))
+#define TKAMD_SEL8(i_) sel32(b2_, TKAMD_SEL4((i_) + 4), TKAMD_SEL4(i_))
+#define TKAMD_SEL16(i_) sel32(b3_, TKAMD_SEL8((i_) + 8), TKAMD_SEL8(i_))
         uint32_t alive0 = 0u;                                  // the positions a symbol starts at
         {
             uint64_t kb[S / 8];
@@ -468,12 +483,29 @@ __device__ __forceinline__ void bpe_merge_lds_unit(const DevTables& t, const uin
 #pragma unroll
                 for (int g = 0; g < S; g += PG) {
                     if ((uint32_t)(g + 1) < wmax) {
-                        uint32_t rk[PG];
+                        // (the slots of all eight, then their loads, then their answers, with the scheduler held to that order as in
+                        // merge_probe2_d: left alone, once the merge loop needed fewer registers than this group does, it took the
+                        // probes one or two at a time)
+                        uint32_t rk[PG], slot[PG];
+                        uint4 x[PG];
+#pragma unroll
+                        for (int q = 0; q < PG; ++q) {
+                            const int i = g + q;
+                            slot[q] = 0u;
+                            if (i < S - 1) slot[q] = ph_slot(merge_hash2(ids[i], ids[i + 1], t.merge_seed), disp[merge_hash1(ids[i], ids[i + 1], t.merge_seed) & t.merge_bmask], t.merge_mask);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int q = 0; q < PG; ++q) {
+                            x[q] = make_uint4(0u, 0u, 0u, 0u);
+                            if (g + q < S - 1) x[q] = ((const uint4*)t.merges)[slot[q]];
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                         for (int q = 0; q < PG; ++q) {
                             const int i = g + q;
                             rk[q] = RANK_NONE;
-                            if (i < S - 1) { uint32_t nd; merge_probe_d(t, disp, ids[i], ids[i + 1], &rk[q], &nd); }
+                            if (i < S - 1) rk[q] = (x[q].x == ids[i] && x[q].y == ids[i + 1]) ? x[q].z : RANK_NONE;
                         }
 #pragma unroll
                         for (int q = 0; q < PG; ++q) {
@@ -540,7 +572,13 @@ __device__ __forceinline__ void bpe_merge_lds_unit(const DevTables& t, const uin
         }
         uint32_t alive = alive0;
         bool active = valid && __popc(alive) > 1;
-        while (__any(active)) {
+        // (do .. while: a wavefront with no merge to make runs one iteration that does nothing.  With the test in front the symbols had
+        // one value for the way out and one for the next iteration, each in registers of its own)
+        do {
+            // SYM_REGS: the merge's new symbol goes into its register at the END of the iteration, for every lane (at = S: nowhere), not
+            // inside the `if`s below -- written there, each `if` left the whole array a value of its own at its end, which the compiler
+            // kept in registers of its own and copied back: two moves a register an iteration, and 32 registers more
+            uint32_t at = (uint32_t)S, at_id = 0u;
             if (active) {
                 uint32_t best = 0xFFFFFFFFu;
 #pragma unroll
@@ -558,12 +596,12 @@ __device__ __forceinline__ void bpe_merge_lds_unit(const DevTables& t, const uin
                     const uint32_t k = has_k ? (uint32_t)__ffs(above) - 1u : i;
                     const uint32_t h = has_h ? 31u - (uint32_t)__clz(below) : i;
                     uint32_t sr, sl;
+                    // (one tree after the other: interleaved, the intermediate values of both are live at once, and the 32-symbol role of
+                    // k_bpe_merge_lds_pair has 96 registers)
                     TKAMD_SYM_AT(sr, k);
                     TKAMD_SYM_AT(sl, h);
-                    if (SYM_REGS) {
-#pragma unroll
-                        for (int q = 0; q < S; ++q) ids[q] = (i == (uint32_t)q) ? nid : ids[q];
-                    } else my_sym[i * NL] = nid;
+                    if (SYM_REGS) { at = i; at_id = nid; }
+                    else my_sym[i * NL] = nid;
                     uint32_t r1, r2;
                     merge_probe2_d(t, disp, sl, nid, nid, sr, &r1, &r2);
                     my_key[j * NL] = 0xFFFFFFFFu;
@@ -572,7 +610,11 @@ __device__ __forceinline__ void bpe_merge_lds_unit(const DevTables& t, const uin
                     if (!has_k && !has_h) active = false;                 // one symbol left
                 }
             }
-        }
+            if (SYM_REGS) {
+#pragma unroll
+                for (int q = 0; q < S; ++q) ids[q] = sel32(at == (uint32_t)q, at_id, ids[q]);
+            }
+        } while (__any(active));
         if (valid) {
             // result row named by the queue position (the lookup kernel already pointed tok0 at it); beyond four tokens the
             // ids 1.. go to tmp_ids[s + j]
@@ -615,6 +657,11 @@ __device__ __forceinline__ void bpe_merge_lds_unit(const DevTables& t, const uin
     }
 }
 #undef TKAMD_SYM_AT
+#undef TKAMD_SEL16
+#undef TKAMD_SEL8
+#undef TKAMD_SEL4
+#undef TKAMD_SEL2
+#undef TKAMD_SEL1
 // the tables every unit reads, into the workgroup's LDS behind the key area: the byte alphabet and -- DISP_LDS -- the merge displacements
 template <int S, int NT, int NL, bool DISP_LDS, bool SYM_REGS>
 __device__ __forceinline__ const uint16_t* bpe_merge_lds_tables(const DevTables& t, uint32_t* lds_words) {
@@ -672,19 +719,21 @@ __global__ __launch_bounds__(NT) void k_bpe_merge_lds(DevTables t, const uint8_t
 // select chains over 32 registers, a minimum over 31 keys -- and, 768 lanes a CU, takes two rounds for C2's 285 k distinct words.  Here
 // a workgroup is 640 lanes, two to a CU (the 16-symbol kernel's shape), and runs units of either ROLE:
 //   short: the 16-symbol unit over 640 words of v16;
-//   long:  the 32-symbol unit over 320 words of v32 -- 320 x 32 keys are the same 40 KB as 640 x 16, the upper five wavefronts only
-//          meet the barriers.  Five wavefronts a SIMD leave 96 registers: without the second queue's code the role takes 94 (96 with
-//          the displacements in memory) where k_bpe_merge_lds<32, ..> takes 104, no scratch, its first probes still eight at a time
-//          (tests/test_isa_merge_pair.py holds all of that).  Tried and dropped: first probes four at a time (the same 94), and
-//          amdgpu_waves_per_eu(5, 5), under which the instantiation that reads the displacements from memory probes one at a time.
-// Nobody but the device knows the fills, so every workgroup derives the same plan from them: the fewest ROUNDS of the grid that hold
-// both queues at full units; when that is one round, its slots are split between the roles in proportion to what each needs and each
-// queue is spread evenly over its slots (a thin queue keeps a few wavefronts of every one of its workgroups busy, as in k_bpe_merge_lds).  Units are
-// numbered long role first and dealt to the workgroups round by round, the rounds alternating their direction: a second round goes
-// first to the workgroups whose first unit was a short one.  No workgroup waits for another.
+//   long:  the 32-symbol unit over up to 320 words of v32 -- 320 x 32 keys are the same 40 KB as 640 x 16, the upper five wavefronts
+//          only meet the barriers.  Five wavefronts a SIMD leave 96 registers: the kernel takes 85 (the first probes, eight at a time,
+//          are what needs them; the merge loop needs 71), no scratch (tests/test_isa_merge_pair.py holds all of that).  Tried and
+//          dropped: first probes four at a time, and amdgpu_waves_per_eu(5, 5), which changes nothing the scheduler does here.
+// Nobody but the device knows the fills, so every workgroup derives the same plan from them (merge_pair_plan_core.hpp): the fewest
+// ROUNDS of the grid that hold both queues at full units; when that is one round, the short role keeps the slots its full units need
+// and the long role spreads its queue over all the others, in units of at most 256 words where they suffice: four wavefronts, so that
+// no SIMD runs two of the 32-symbol chains that decide how long the launch lasts (C2: 99 units of 192 words where the slots split in
+// proportion gave 59 of 320; 50.4 -> 47.8 us, profiles/merge_chain_ab_c2.txt).  Units are numbered long role first and dealt to the
+// workgroups round by round, the rounds alternating their direction: a second round goes first to the workgroups whose first unit
+// was a short one.  No workgroup waits for another.  Measured, not kept: s_setprio 1 around the 32-symbol role's merge loop (48.1 us).
 // =================================================================================================
 constexpr int PAIR_NT = 640, PAIR_NL32 = 320, PAIR_WG_PER_CU = 2;
 static_assert(16 * PAIR_NT == 32 * PAIR_NL32, "one key area serves both roles");
+static_assert(PAIR_NT == (int)PAIR_TAKE_S_MAX && PAIR_NL32 == (int)PAIR_TAKE_L_MAX, "the plan's units are the kernel's");
 template <bool DISP_LDS>
 __global__ __launch_bounds__(PAIR_NT) void k_bpe_merge_lds_pair(DevTables t, const uint8_t* __restrict__ text, QView v16, QView v32, uint4* __restrict__ rows,
                                                                                       uint32_t* __restrict__ tmp_ids, uint32_t* __restrict__ tmp_end) {
@@ -696,24 +745,17 @@ __global__ __launch_bounds__(PAIR_NT) void k_bpe_merge_lds_pair(DevTables t, con
     const uint32_t n16 = qview_prefix(v16, s_qpre16), n32 = qview_prefix(v32, s_qpre32);
     if (!(n16 | n32)) return;                              // (uniform: nothing queued, nothing counted)
     const uint16_t* const disp = bpe_merge_lds_tables<16, PAIR_NT, PAIR_NT, DISP_LDS, true>(t, lds_words);
+    // (merge_pair_plan_core.hpp.  More than one round: full units, so that only the workgroups the overflow is dealt to -- the last ones,
+    // whose first unit was a short one -- run a second unit at all; every workgroup running two half-filled units measured slower than
+    // k_bpe_merge_lds<32, ..>'s two rounds on out-of-distribution text, 0.686 against 0.645 ms a step)
     const uint32_t grid = gridDim.x;
-    const uint32_t need_l = (n32 + PAIR_NL32 - 1u) / PAIR_NL32, need_s = (n16 + PAIR_NT - 1u) / PAIR_NT, need = need_l + need_s;   // full units
-    const uint32_t rounds = (need + grid - 1u) / grid;
-    const uint32_t slots = rounds * grid, spare = slots - need;                                         // (spare < grid: the product below stays in 32 bits)
-    const uint32_t slots_l = need_l + (spare * need_l + need - 1u) / need, slots_s = slots - slots_l;   // (slots_s >= need_s: the spare ones are split, never more)
-    // (more than one round: full units, so that only the workgroups the overflow is dealt to -- the last ones, whose first unit was a
-    // short one -- run a second unit at all; every workgroup running two half-filled units measured slower than k_bpe_merge_lds<32, ..>'s
-    // two rounds on out-of-distribution text, 0.686 against 0.645 ms a step)
-    const bool spread = rounds == 1u;
-    const uint32_t take_l = (n32 && spread) ? min((uint32_t)PAIR_NL32, ((n32 + slots_l - 1u) / slots_l + 63u) & ~63u) : (uint32_t)PAIR_NL32;
-    const uint32_t take_s = (n16 && spread) ? min((uint32_t)PAIR_NT, ((n16 + slots_s - 1u) / slots_s + 63u) & ~63u) : (uint32_t)PAIR_NT;
-    const uint32_t units_l = (n32 + take_l - 1u) / take_l, units = units_l + (n16 + take_s - 1u) / take_s;                       // (<= slots_l, <= slots)
-    for (uint32_t round = 0u; round < rounds; ++round) {
-        const uint32_t u = round * grid + ((round & 1u) ? (grid - 1u - blockIdx.x) : blockIdx.x);                               // (workgroup-uniform)
-        if (u < units_l)
-            bpe_merge_lds_unit<32, PAIR_NT, PAIR_NL32, true, false, false>(t, text, v32, s_qpre32, n32, v32, s_qpre32, n32, u * take_l, take_l, lds_words, disp, &s_probes, rows, tmp_ids, tmp_end);
-        else if (u < units)
-            bpe_merge_lds_unit<16, PAIR_NT, PAIR_NT, true, false, false>(t, text, v16, s_qpre16, n16, v16, s_qpre16, n16, (u - units_l) * take_s, take_s, lds_words, disp, &s_probes, rows, tmp_ids, tmp_end);
+    const PairPlan plan = pair_plan(n16, n32, grid);
+    for (uint32_t round = 0u; round < plan.rounds; ++round) {
+        const uint32_t u = pair_plan_unit(round, blockIdx.x, grid);                                                              // (workgroup-uniform)
+        if (u < plan.units_l)
+            bpe_merge_lds_unit<32, PAIR_NT, PAIR_NL32, true, false, false>(t, text, v32, s_qpre32, n32, v32, s_qpre32, n32, u * plan.take_l, plan.take_l, lds_words, disp, &s_probes, rows, tmp_ids, tmp_end);
+        else if (u < plan.units)
+            bpe_merge_lds_unit<16, PAIR_NT, PAIR_NT, true, false, false>(t, text, v16, s_qpre16, n16, v16, s_qpre16, n16, (u - plan.units_l) * plan.take_s, plan.take_s, lds_words, disp, &s_probes, rows, tmp_ids, tmp_end);
     }
     if (t.probes) {                                        // (uniform)
         __syncthreads();
@@ -752,13 +794,15 @@ static int prepare_pair_merge() {
     return rc;
 }
 int pair_merge_occupancy() { return pair_merge_wg_per_cu; }
-// grid: the resident capacity (the kernel deals its units to whatever grid it is given)
-static void launch_lds_merge_pair(hipStream_t st, int n_cu, const DevTables& t, const uint8_t* text, const QView& v16, const QView& v32, uint4* rows, uint32_t* tmp_ids, uint32_t* tmp_end) {
-    const int grid = n_cu * pair_merge_wg_per_cu;
+// grid: the resident capacity (the kernel deals its units to whatever grid it is given -- grid_hook > 0, the test hook
+// TKAMD_MERGE_PAIR_GRID: a grid small enough that a few thousand words reach every boundary of the plan).  Returns the grid it launched.
+static int launch_lds_merge_pair(hipStream_t st, int n_cu, int grid_hook, const DevTables& t, const uint8_t* text, const QView& v16, const QView& v32, uint4* rows, uint32_t* tmp_ids, uint32_t* tmp_end) {
+    const int grid = grid_hook > 0 ? grid_hook : n_cu * pair_merge_wg_per_cu;
     if (t.merge_bmask < (uint32_t)DISP_LDS_MAX)
         hipLaunchKernelGGL(k_bpe_merge_lds_pair<true>, dim3(grid), dim3(PAIR_NT), lds_merge_bytes(16, PAIR_NT, true, true), st, t, text, v16, v32, rows, tmp_ids, tmp_end);
     else
         hipLaunchKernelGGL(k_bpe_merge_lds_pair<false>, dim3(grid), dim3(PAIR_NT), lds_merge_bytes(16, PAIR_NT, false, true), st, t, text, v16, v32, rows, tmp_ids, tmp_end);
+    return grid;
 }
 
 // =================================================================================================

@@ -96,9 +96,9 @@ void launch_bpe_merge(hipStream_t st, int grid, int group, const DevTables& t, c
     else
         hipLaunchKernelGGL(k_bpe_merge<64>, dim3(grid), dim3(256), 0, st, t, text, v, r, tmp_ids, tmp_end);
 }
-void launch_bpe_merge_pair(hipStream_t st, int n_cu, const DevTables& t, const uint8_t* text, const QView& v16, const QView& v32, void* rows,
+int launch_bpe_merge_pair(hipStream_t st, int n_cu, int grid_hook, const DevTables& t, const uint8_t* text, const QView& v16, const QView& v32, void* rows,
                            uint32_t* tmp_ids, uint32_t* tmp_end) {
-    launch_lds_merge_pair(st, n_cu, t, text, v16, v32, (uint4*)rows, tmp_ids, tmp_end);
+    return launch_lds_merge_pair(st, n_cu, grid_hook, t, text, v16, v32, (uint4*)rows, tmp_ids, tmp_end);
 }
 template <int KIND>
 static void launch_pretok_local_t(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* docmask,

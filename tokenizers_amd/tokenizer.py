@@ -1121,14 +1121,15 @@ class Tokenizer:
 
     def queue_sizes(self) -> dict[str, int]:
         """Merge work-queue sizes of the last synchronised batch (diagnostics)."""
-        arr = (C.c_uint32 * 22)()
-        _lib.check(self._lib.tkamd_profile_counters(self._h, arr, 22))
+        arr = (C.c_uint32 * 23)()
+        _lib.check(self._lib.tkamd_profile_counters(self._h, arr, 23))
         out = {"merge16": arr[0], "merge32": arr[3], "merge64": arr[1], "merge_long": arr[2], "pretok_slow_docs": arr[4], "merge_huge": arr[7]}
         if arr[5]:                                       # in-batch claims: candidates the lookup looked at / how many were another pre-token's word
             out["claim_candidates"], out["claim_shared"] = arr[5], arr[6]
         out["added_spec_pause"] = arr[14]                # batches that will run the added tokens' matching passes outright (a speculative batch met a token's content)
         out["nfc_spec_pause"], out["nfc_reruns"] = arr[16], arr[17]      # behind an NFC normalizer: batches that will normalize outright / batches run again (the quick check failed)
         out["merge_pair_wg_per_cu"] = arr[13]            # resident workgroups per CU of the launch that merges both LDS queues (its grid is that x the CUs)
+        out["merge_pair_grid"] = arr[22]                # workgroups the last batch launched that kernel on (0: it ran none)
         out["q16_div"] = arr[15]                         # the <= 16-byte queue holds n_bytes / q16_div entries (a queue overflow re-runs the batch with 2, then 1)
         # the shape of the load-time tables (known before the first batch): short-word slots / displacement buckets / largest displacement, merge slots
         out["shortw_slots"], out["shortw_buckets"], out["shortw_max_disp"], out["merge_slots"] = arr[18], arr[19], arr[20], arr[21]
