@@ -308,6 +308,47 @@ int64_t         tkamd_text_n_bytes(const tkamd_text* b);
 const uint8_t*  tkamd_text_bytes(const tkamd_text* b);         /* [n_bytes]                    */
 const int64_t*  tkamd_text_doc_offsets(const tkamd_text* b);   /* [n_docs+1] CSR into bytes    */
 void            tkamd_text_free(tkamd_text* b);
+
+/* ---- decode_batch, device entry: ids already resident in HBM, the text stays in HBM ------------------
+ * For callers whose ids never were on the host -- a generation loop's padded [B, L] output tensor, rollouts decoded with one
+ * tokenizer and encoded again with another -- and who want the text where tkamd_encode_batch_device reads it.
+ *   in : d_ids[n_ids], uint32 (an int32 tensor's bit patterns are the same thing) or, with TKAMD_DECODE_IDS_I64, int64 (torch.long);
+ *        sequence d is d_ids[d_begin[d] .. d_end[d]).  The ranges may come in any order, overlap, leave gaps or be empty: a packed CSR
+ *        is d_begin = off, d_end = off + 1; row r of a right- or left-padded [B, L] tensor is begin = r * L + pad_left[r],
+ *        end = begin + len[r].  n_ids bounds them: a range with begin > end, begin < 0 or end > n_ids is found ON THE DEVICE, copies
+ *        nothing (it never causes a read outside d_ids) and fails the call with TKAMD_ERR_INVALID naming the first such sequence.
+ *        An int64 value outside [0, 2^32) decodes to nothing, like any id without a token (-100 labels, -1 fillers).
+ *   out: VALID UTF-8 -- for the ByteLevel decoder String::from_utf8_lossy (byte_level.rs:170) runs on the device, per sequence: every
+ *        maximal invalid subpart becomes one U+FFFD; a sequence that ends in E2 82 gets one, and the next one, beginning with AC, one of
+ *        its own (every other decoder emits token strings; ByteFallback writes its own U+FFFD) -- as one buffer + CSR with
+ *        TKAMD_TEXT_PAD zero bytes behind it: exactly what tkamd_encode_batch_device takes.  flags: TKAMD_SKIP_SPECIAL as above.
+ * Everything runs on `hip_stream` in the workspace keyed by that stream.  The call sizes its buffers from counts the device computes,
+ * so it WAITS for the stream: twice (the token count of the ranges, with the range check; the byte count of the text), and a third
+ * time for the ByteLevel decoder (the count of invalid subparts, with the size of the repaired text: a text without one keeps its
+ * buffer and skips the repair).  The outputs stay in HBM and are valid until the next decode call on the same handle and stream; an
+ * encode call on that handle does not move them.  The limits of the host entry hold (fewer than 2^31 tokens, less than 4 GiB of
+ * text), unsupported decoders are refused with the same messages, a host-only handle gets TKAMD_ERR_DEVICE, a multi-device handle
+ * decodes on devices[0]. */
+#define TKAMD_DECODE_IDS_I64 2u            /* d_ids holds int64 (torch.long), else uint32 / int32 bit patterns */
+typedef struct tkamd_device_text {
+    const uint8_t* d_bytes;        /* [n_bytes] valid UTF-8, followed by >= TKAMD_TEXT_PAD zero bytes */
+    const int64_t* d_doc_offsets;  /* [n_docs + 1] CSR into d_bytes                                   */
+    const int64_t* d_n_bytes;      /* [1]                                                             */
+    int64_t        n_bytes;        /* the same count, known when the call returns                     */
+} tkamd_device_text;
+int tkamd_decode_batch_device(tkamd_tokenizer* tok, const void* d_ids, int64_t n_ids,
+                              const int64_t* d_begin, const int64_t* d_end, int64_t n_docs,
+                              uint32_t flags, void* hip_stream, tkamd_device_text* out);
+/* A result of the call above copied to host memory on `hip_stream` (the call waits for it): bytes[0 .. text->n_bytes + n_slack) -- n_slack
+ * <= TKAMD_TEXT_PAD bytes of the zero slack behind the text --, doc_offsets[0 .. n_docs] and *n_bytes, the count as the device holds it.
+ * Any of the three may be NULL.  For bindings that have no HIP runtime of their own to copy with; a consumer on the device reads the
+ * pointers of tkamd_device_text directly. */
+int tkamd_device_text_read(tkamd_tokenizer* tok, const tkamd_device_text* text, int64_t n_docs, int64_t n_slack, void* hip_stream,
+                           uint8_t* bytes, int64_t* doc_offsets, int64_t* n_bytes);
+/* String::from_utf8_lossy of ONE sequence -- bytes[0 .. n) -- by the host run of the very per-byte decision the kernels make
+ * (csrc/utf8_lossy_core.hpp): out[0 .. *n_out).  Takes no handle and needs no device.  cap: what out holds; *n_out is set even when
+ * it is too small (TKAMD_ERR_INVALID then). */
+int tkamd_probe_utf8_lossy(const uint8_t* bytes, int64_t n, uint8_t* out, int64_t cap, int64_t* n_out);
 /* The byte string token `id` contributes (first_position != 0: as the first kept token of a sequence), straight from
  * the load-time decode tables; *flags = 0 ordinary, 1 special, 2 no token has this id.  Works on host-only handles. */
 int tkamd_decode_token(const tkamd_tokenizer* tok, uint32_t id, int first_position, uint8_t* out, int32_t cap,

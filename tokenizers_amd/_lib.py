@@ -26,6 +26,7 @@ PAIRS = 16
 WANT_OVERFLOW = 32
 NO_SPECULATION = 64      # device entry, results consumed stream-ordered without tkamd_device_sync: the added tokens' matching passes and the NFC normalizer outright
 SKIP_SPECIAL = 1          # tkamd_decode_batch flag
+DECODE_IDS_I64 = 2        # tkamd_decode_batch_device: the ids are int64
 TEXT_PAD = 64
 MAX_STAGES = 24
 
@@ -41,6 +42,7 @@ SYMBOLS = [
     "tkamd_batch_encoding_docs", "tkamd_probe_truncation", "tkamd_probe_bert_alone", "tkamd_tokenizer_pair_template", "tkamd_batch_encoding_parts", "tkamd_probe_bert_nfd", "tkamd_encode_special_tokens",
     "tkamd_tokenizer_from_json_devices", "tkamd_tokenizer_set_collect", "tkamd_tokenizer_devices", "tkamd_shard_stats", "tkamd_debug_phases",
     "tkamd_pinned_alloc", "tkamd_pinned_free", "tkamd_encode_batch_paced",
+    "tkamd_decode_batch_device", "tkamd_device_text_read", "tkamd_probe_utf8_lossy",
 ]
 COLLECT_HOST, COLLECT_ROOT_P2P, COLLECT_ROOT_RCCL = 0, 1, 2
 
@@ -57,6 +59,10 @@ class DeviceResult(C.Structure):
                 ("d_word_ids", C.c_void_p), ("d_n_tokens", C.c_void_p), ("d_n_pretokens", C.c_void_p), ("d_pad_counts", C.c_void_p),
                 ("d_type_ids", C.c_void_p), ("d_seq_ids", C.c_void_p), ("d_enc_docs", C.c_void_p), ("d_n_encodings", C.c_void_p), ("d_enc_parts", C.c_void_p),
                 ("ids_capacity", C.c_int64)]
+
+
+class DeviceText(C.Structure):
+    _fields_ = [("d_bytes", C.c_void_p), ("d_doc_offsets", C.c_void_p), ("d_n_bytes", C.c_void_p), ("n_bytes", C.c_int64)]
 
 
 class StageTime(C.Structure):
@@ -154,6 +160,12 @@ def load() -> C.CDLL:
         f.restype = rt
     lib.tkamd_text_free.argtypes = [vp]
     lib.tkamd_text_free.restype = None
+    lib.tkamd_decode_batch_device.argtypes = [vp, vp, i64, vp, vp, i64, u32, vp, C.POINTER(DeviceText)]
+    lib.tkamd_decode_batch_device.restype = i32
+    lib.tkamd_device_text_read.argtypes = [vp, C.POINTER(DeviceText), i64, i64, vp, vp, vp, C.POINTER(i64)]
+    lib.tkamd_device_text_read.restype = i32
+    lib.tkamd_probe_utf8_lossy.argtypes = [vp, i64, vp, i64, C.POINTER(i64)]
+    lib.tkamd_probe_utf8_lossy.restype = i32
     lib.tkamd_decode_token.argtypes = [vp, u32, i32, vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.tkamd_decode_token.restype = i32
     lib.tkamd_probe_word.argtypes = [vp, C.c_char_p, C.c_int32, C.POINTER(u32), C.POINTER(u32)]

@@ -42,6 +42,7 @@
 #include "pretok_clip_core.hpp"
 #include "pretok_local_core.hpp"
 #include "unigram_core.hpp"
+#include "utf8_lossy_core.hpp"
 #include "tables.hpp"
 
 namespace tkamd {

@@ -484,6 +484,16 @@ void launch_apply_match_ids(hipStream_t st, const uint32_t* match_list, const ui
 void launch_decode(hipStream_t st, const uint32_t* ids, const int64_t* tok_off, int64_t n_docs, int64_t n_tok, const void* entry, uint32_t n_ids,
                    const uint8_t* blob, uint32_t skip_special, uint32_t* firstmask, uint32_t* len, uint32_t* bsum, uint32_t* pos, int64_t* total,
                    int64_t* out_off, uint8_t* out_bytes_or_null, uint32_t from_end = 0, uint32_t* badmask = nullptr, uint32_t* dupmask = nullptr);      // from_end: the position mask marks the LAST kept token (BPEDecoder); badmask: ByteFallback
+// the device entry of decode_batch (kernels/decode.hip): ranges -> token CSR (scalars[1] = tokens, scalars[2] = the first bad range), the ids
+// gathered into one uint32 array; the ByteLevel decoder's from_utf8_lossy (utf8_lossy_core.hpp): count (scalars[4] = bytes of the repaired
+// text, scalars[5] = invalid subparts), repair (text -> out, doc_off rewritten in place, *total = bytes written); the zero slack behind a text
+void launch_decode_ranges(hipStream_t st, const int64_t* begin, const int64_t* end, int64_t n_docs, int64_t n_elems, uint32_t* len, uint32_t* bsum,
+                          uint32_t* pos, int64_t* tok_off, int64_t* scalars);
+void launch_decode_gather(hipStream_t st, const void* src, bool wide, const int64_t* begin, const uint32_t* pos, int64_t n_docs, int64_t n_tok, uint32_t* ids);
+void launch_utf8_lossy_count(hipStream_t st, const uint8_t* text, int64_t n, const int64_t* doc_off, int64_t n_docs, int64_t* scalars);
+void launch_utf8_lossy_repair(hipStream_t st, const uint8_t* text, int64_t n, int64_t* doc_off, int64_t n_docs, uint32_t* len, uint32_t* bsum, uint32_t* pos,
+                              int64_t* total, uint8_t* out);
+void launch_decode_zero_pad(hipStream_t st, uint8_t* text, const int64_t* n_dev);
 int prepare_long_kernel();
 void launch_bpe_merge_long(hipStream_t st, int grid, const DevTables& t, const uint8_t* text, const QView& v, void* rows,
                            uint32_t* tmp_ids, uint32_t* tmp_end, uint32_t* list_huge, uint32_t* n_huge,

@@ -178,3 +178,170 @@ void launch_decode(hipStream_t st, const uint32_t* ids, const int64_t* tok_off, 
                            (const uint32_t*)firstmask, (const uint32_t*)badmask, (const uint32_t*)dupmask, blob, (const uint32_t*)pos, out_bytes_or_null);
     }
 }
+
+// =================================================================================================
+// The device entry of decode_batch (tkamd_decode_batch_device): the ids are in HBM already, as any int32 / uint32 / int64 array and one
+// [begin, end) range per sequence -- a packed CSR, the rows of a padded [B, L] tensor, ranges in any order --, and the text stays
+// there.  Two pieces in front of and behind launch_decode, which runs unchanged between them:
+//   the range gather  lengths of the ranges (a range that is not inside [0, n_elems] counts nothing and is reported), their scan into
+//                     the token CSR launch_decode reads, and the ids copied -- one lane per id -- into the contiguous uint32 array;
+//   the lossy repair  String::from_utf8_lossy per sequence (the ByteLevel decoder only: every other decoder emits token strings, and
+//                     ByteFallback's badmask writes U+FFFD itself): utf8_lossy_core.hpp decides per byte, k_lossy_count sums what the
+//                     repaired text would hold and how many invalid subparts there are in one pass over the text, and only a text
+//                     that has one pays for the length pass, the scan and the scatter.
+// scalars (int64[8], dw_total): [0] bytes of the text (launch_decode), [1] tokens as the u32 scan has them, [2] the first bad range as
+// (n_docs - d) << 4 | why (0: none), [3] tokens summed in 64 bits (what the host's limit is held against), [4] bytes of the repaired text, [5] invalid subparts.
+// =================================================================================================
+constexpr int DECS_N_TOK = 1, DECS_BAD = 2, DECS_N_TOK64 = 3, DECS_FIXED = 4, DECS_INVALID = 5;
+
+// the last index d in [0, n] with off[d] <= x (off ascending, off[0] <= x)
+template <class T>
+__device__ __forceinline__ int64_t dec_owner(const T* __restrict__ off, int64_t n, uint64_t x) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if ((uint64_t)off[mid] <= x) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+__global__ __launch_bounds__(256) void k_decode_range_len(const int64_t* __restrict__ begin, const int64_t* __restrict__ end, int64_t n_docs, int64_t n_elems,
+                                                          uint32_t* __restrict__ len, unsigned long long* __restrict__ scalars) {
+    __shared__ uint32_t sm[4];
+    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t l = 0u;
+    if (d < n_docs) {
+        const int64_t b = begin[d], e = end[d];
+        const uint32_t why = (b > e ? 1u : 0u) | (b < 0 ? 2u : 0u) | (e > n_elems ? 4u : 0u);
+        if (why) atomicMax(&scalars[DECS_BAD], ((unsigned long long)(n_docs - d) << 4) | why);
+        else if (e - b >= ((int64_t)1 << 31)) atomicMax(&scalars[DECS_BAD], ((unsigned long long)(n_docs - d) << 4) | 8u);
+        else l = (uint32_t)(e - b);
+    }
+    if (d <= n_docs) len[d] = l;                               // (len[n_docs] = 0: its position is the token count)
+    // the token count in 64 bits, next to the u32 scan: ranges may overlap, so their lengths can sum past 2^32 over a small array and the
+    // scan's total would wrap under the host's limit.  Two 16-bit halves through the u32 block sum (256 x 65,535 fits), one add a workgroup.
+    uint32_t t_lo, t_hi;
+    block256_excl_scan(l & 0xFFFFu, sm, &t_lo);
+    block256_excl_scan(l >> 16, sm, &t_hi);
+    if (threadIdx.x == 0 && (t_lo | t_hi)) atomicAdd(&scalars[DECS_N_TOK64], ((unsigned long long)t_hi << 16) + t_lo);
+}
+__global__ __launch_bounds__(256) void k_decode_tok_off(const uint32_t* __restrict__ pos, int64_t n_docs, int64_t* __restrict__ tok_off) {
+    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (d <= n_docs) tok_off[d] = (int64_t)pos[d];
+}
+// one lane per id: the sequence it belongs to is the last one that starts at or before it (empty ones in between start where it does
+// not: they are skipped by taking the LAST), its source the same distance into that sequence's range.  WIDE: the ids are int64; a
+// value that is no uint32 becomes 0xFFFFFFFF, an id no vocabulary has.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void k_decode_gather(const void* __restrict__ src, const int64_t* __restrict__ begin, const uint32_t* __restrict__ pos,
+                                                       int64_t n_docs, int64_t n_tok, uint32_t* __restrict__ ids) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_tok) return;
+    const int64_t d = dec_owner(pos, n_docs, (uint64_t)t);     // (pos[n_docs] = n_tok > t: d < n_docs)
+    const int64_t s = begin[d] + (t - (int64_t)pos[d]);
+    if (WIDE) {
+        const int64_t v = ((const int64_t*)src)[s];
+        ids[t] = (v < 0 || v > (int64_t)0xFFFFFFFFll) ? 0xFFFFFFFFu : (uint32_t)v;
+    } else ids[t] = ((const uint32_t*)src)[s];
+}
+void launch_decode_ranges(hipStream_t st, const int64_t* begin, const int64_t* end, int64_t n_docs, int64_t n_elems, uint32_t* len, uint32_t* bsum,
+                          uint32_t* pos, int64_t* tok_off, int64_t* scalars) {
+    (void)hipMemsetAsync(scalars + 1, 0, 7 * 8, st);
+    const unsigned nb = blocks_for(n_docs + 1, 256);
+    hipLaunchKernelGGL(k_decode_range_len, dim3(nb), dim3(256), 0, st, begin, end, n_docs, n_elems, len, (unsigned long long*)scalars);
+    hipLaunchKernelGGL(k_u32_reduce, dim3(nb), dim3(256), 0, st, (const uint32_t*)len, n_docs + 1, bsum);
+    hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, st, bsum, (int64_t)nb, (const int64_t*)nullptr, (int64_t)1, scalars + DECS_N_TOK);
+    hipLaunchKernelGGL(k_u32_down, dim3(nb), dim3(256), 0, st, (const uint32_t*)len, n_docs + 1, (const uint32_t*)bsum, pos);
+    hipLaunchKernelGGL(k_decode_tok_off, dim3(nb), dim3(256), 0, st, (const uint32_t*)pos, n_docs, tok_off);
+}
+void launch_decode_gather(hipStream_t st, const void* src, bool wide, const int64_t* begin, const uint32_t* pos, int64_t n_docs, int64_t n_tok, uint32_t* ids) {
+    if (n_tok <= 0) return;
+    const unsigned nb = blocks_for(n_tok, 256);
+    if (wide) hipLaunchKernelGGL(k_decode_gather<true>, dim3(nb), dim3(256), 0, st, src, begin, pos, n_docs, n_tok, ids);
+    else hipLaunchKernelGGL(k_decode_gather<false>, dim3(nb), dim3(256), 0, st, src, begin, pos, n_docs, n_tok, ids);
+}
+
+// the sequence byte i lies in: [lo, hi) from the text's document CSR
+__device__ __forceinline__ void lossy_bounds(const int64_t* __restrict__ doc_off, int64_t n_docs, int64_t i, int64_t& lo, int64_t& hi) {
+    const int64_t d = dec_owner(doc_off, n_docs, (uint64_t)i); // (doc_off[n_docs] = n > i: d < n_docs)
+    lo = doc_off[d];
+    hi = doc_off[d + 1];
+}
+// 16 bytes a lane, one 16-byte load; a lane whose bytes are all ASCII -- nearly every lane of nearly every text -- is done with that
+__global__ __launch_bounds__(256) void k_lossy_count(const uint8_t* __restrict__ text, int64_t n, const int64_t* __restrict__ doc_off, int64_t n_docs,
+                                                     unsigned long long* __restrict__ scalars) {
+    __shared__ uint32_t sm[4];
+    const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
+    uint32_t extra = 0u, gone = 0u, invalid = 0u;             // bytes the repair adds / drops, invalid subparts
+    if (i0 < n) {
+        const uint4 w = *(const uint4*)(text + i0);           // (the buffer is 16-byte aligned and has TEXT_PAD bytes behind n)
+        if ((w.x | w.y | w.z | w.w) & 0x80808080u) {
+            const int64_t i1 = min(i0 + 16, n);
+            int64_t lo = 0, hi = -1;
+            for (int64_t i = i0; i < i1; ++i) {
+                if (text[i] < 0x80u) continue;
+                if (i >= hi) lossy_bounds(doc_off, n_docs, i, lo, hi);
+                const uint32_t l = utf8_lossy_len(text, i, lo, hi);
+                if (l == 3u) { extra += 2u; ++invalid; }
+                else if (l == 0u) ++gone;
+            }
+        }
+    }
+    // (three block sums through the one scan helper: they are off the common path's cost -- a launch over the text at 16 bytes a lane)
+    uint32_t t_extra, t_gone, t_invalid;
+    block256_excl_scan(extra, sm, &t_extra);
+    block256_excl_scan(gone, sm, &t_gone);
+    block256_excl_scan(invalid, sm, &t_invalid);
+    if (threadIdx.x == 0) {
+        const int64_t i1 = min((int64_t)(blockIdx.x + 1) * 4096, n);
+        atomicAdd(&scalars[DECS_FIXED], (unsigned long long)(i1 - (int64_t)blockIdx.x * 4096) + t_extra - t_gone);
+        if (t_invalid) atomicAdd(&scalars[DECS_INVALID], (unsigned long long)t_invalid);
+    }
+}
+__global__ __launch_bounds__(256) void k_lossy_len(const uint8_t* __restrict__ text, int64_t n, const int64_t* __restrict__ doc_off, int64_t n_docs,
+                                                   uint32_t* __restrict__ len) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t l = 1u;
+    if (text[i] >= 0x80u) {
+        int64_t lo, hi;
+        lossy_bounds(doc_off, n_docs, i, lo, hi);
+        l = utf8_lossy_len(text, i, lo, hi);
+    }
+    len[i] = l;
+}
+__global__ __launch_bounds__(256) void k_lossy_scatter(const uint8_t* __restrict__ text, int64_t n, const uint32_t* __restrict__ len, const uint32_t* __restrict__ pos,
+                                                       uint8_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t l = len[i];
+    uint8_t* const dst = out + pos[i];
+    if (l == 1u) dst[0] = text[i];
+    else if (l == 3u) { dst[0] = 0xEFu; dst[1] = 0xBFu; dst[2] = 0xBDu; }
+}
+// the document CSR follows its text: in place, a lane an entry
+__global__ __launch_bounds__(256) void k_lossy_doc_off(int64_t* __restrict__ doc_off, int64_t n_docs, const uint32_t* __restrict__ pos, int64_t n,
+                                                       const int64_t* __restrict__ total) {
+    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (d > n_docs) return;
+    const int64_t o = doc_off[d];
+    doc_off[d] = o < n ? (int64_t)pos[o] : *total;
+}
+void launch_utf8_lossy_count(hipStream_t st, const uint8_t* text, int64_t n, const int64_t* doc_off, int64_t n_docs, int64_t* scalars) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_lossy_count, dim3(blocks_for((n + 15) / 16, 256)), dim3(256), 0, st, text, n, doc_off, n_docs, (unsigned long long*)scalars);
+}
+void launch_utf8_lossy_repair(hipStream_t st, const uint8_t* text, int64_t n, int64_t* doc_off, int64_t n_docs, uint32_t* len, uint32_t* bsum, uint32_t* pos,
+                              int64_t* total, uint8_t* out) {
+    if (n <= 0) return;
+    const unsigned nb = blocks_for(n, 256);
+    hipLaunchKernelGGL(k_lossy_len, dim3(nb), dim3(256), 0, st, text, n, (const int64_t*)doc_off, n_docs, len);
+    hipLaunchKernelGGL(k_u32_reduce, dim3(nb), dim3(256), 0, st, (const uint32_t*)len, n, bsum);
+    hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, st, bsum, (int64_t)nb, (const int64_t*)nullptr, (int64_t)1, total);
+    hipLaunchKernelGGL(k_u32_down, dim3(nb), dim3(256), 0, st, (const uint32_t*)len, n, (const uint32_t*)bsum, pos);
+    hipLaunchKernelGGL(k_lossy_scatter, dim3(nb), dim3(256), 0, st, text, n, (const uint32_t*)len, (const uint32_t*)pos, out);
+    hipLaunchKernelGGL(k_lossy_doc_off, dim3(blocks_for(n_docs + 1, 256)), dim3(256), 0, st, doc_off, n_docs, (const uint32_t*)pos, n, (const int64_t*)total);
+}
+// the TEXT_PAD readable zero bytes an encode over this text expects behind it
+void launch_decode_zero_pad(hipStream_t st, uint8_t* text, const int64_t* n_dev) {
+    hipLaunchKernelGGL(k_zero_tail, dim3(1), dim3(64), 0, st, text, n_dev, (int)TEXT_PAD, (unsigned long long*)nullptr, (int64_t)0);
+}

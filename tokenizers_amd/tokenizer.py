@@ -457,6 +457,46 @@ class DeviceBatch:
         return self._tensor(self._res.d_n_tokens, (1,), "<i8")
 
 
+class DeviceText:
+    """Result of :meth:`Tokenizer.decode_batch_device` / :meth:`Tokenizer.decode_tensor`: the decoded text in HBM -- valid UTF-8, one
+    buffer + int64 CSR with ``TEXT_PAD`` zero bytes behind it, what :meth:`Tokenizer.encode_batch_device` takes.  Raw pointers into the
+    handle's workspace: valid until the next decode call on the same tokenizer and stream."""
+
+    def __init__(self, tok: "Tokenizer", res: _lib.DeviceText, n_docs: int, stream: int):
+        self._tok, self._res, self.n_docs, self._stream = tok, res, n_docs, stream
+        self.n_bytes = int(res.n_bytes)
+        self.bytes_ptr = res.d_bytes or 0
+        self.doc_offsets_ptr = res.d_doc_offsets or 0
+
+    _tensor = DeviceBatch._tensor
+
+    def bytes_tensor(self):
+        """uint8 view of the HBM-resident text."""
+        return self._tensor(self.bytes_ptr, (max(self.n_bytes, 1),), "|u1")[: self.n_bytes]
+
+    def doc_offsets_tensor(self):
+        return self._tensor(self.doc_offsets_ptr, (self.n_docs + 1,), "<i8")
+
+    def to_host(self, slack: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """(uint8 bytes[n_bytes + slack], int64 doc_offsets[n_docs + 1]) in host memory: one copy down on the call's stream
+        (``tkamd_device_text_read``); ``slack`` <= TEXT_PAD bytes of the zero slack behind the text come along."""
+        raw, off = np.empty(self.n_bytes + slack, dtype=np.uint8), np.empty(self.n_docs + 1, dtype=np.int64)
+        _lib.check(self._tok._lib.tkamd_device_text_read(self._tok._h, C.byref(self._res), self.n_docs, slack, self._stream, raw.ctypes.data, off.ctypes.data, None))
+        return raw, off
+
+    def n_bytes_device(self) -> int:
+        """The byte count as the device holds it (``d_n_bytes``: what a consumer on the device reads); equals ``n_bytes``."""
+        n = C.c_int64(-1)
+        _lib.check(self._tok._lib.tkamd_device_text_read(self._tok._h, C.byref(self._res), self.n_docs, 0, self._stream, None, None, C.byref(n)))
+        return n.value
+
+    def to_strings(self) -> list[str]:
+        """One copy down; the decode is strict -- the text is valid UTF-8 by construction."""
+        raw, off = self.to_host()
+        buf = raw.tobytes()
+        return [buf[off[i]:off[i + 1]].decode("utf-8") for i in range(self.n_docs)]
+
+
 class _BatchOwner:
     """Keeps a tkamd_batch alive while numpy views of its buffers exist."""
 
@@ -1078,6 +1118,49 @@ class Tokenizer:
     def decode(self, ids: Sequence[int], skip_special_tokens: bool = True) -> str:
         """``Tokenizer.decode`` (tokenizer/mod.rs:935-953) as a batch of one."""
         return self.decode_batch([ids], skip_special_tokens)[0]
+
+    def decode_batch_device(self, d_ids_ptr: int, n_ids: int, d_begin_ptr: int, d_end_ptr: int, n_docs: int, skip_special_tokens: bool = True,
+                            ids_dtype: str = "uint32", stream: int = 0) -> DeviceText:
+        """Ids already in HBM (raw device pointers), the text stays there (``tkamd_decode_batch_device``): sequence d is
+        ``ids[begin[d]:end[d]]`` (int64 ranges in any order; ``n_ids`` bounds them), ``ids_dtype`` one of ``uint32`` / ``int32`` /
+        ``int64``.  Waits for ``stream`` to size its buffers (two or three times a call)."""
+        if ids_dtype not in ("uint32", "int32", "int64"):
+            raise ValueError("ids_dtype must be 'uint32', 'int32' or 'int64'")
+        flags = (_lib.SKIP_SPECIAL if skip_special_tokens else 0) | (_lib.DECODE_IDS_I64 if ids_dtype == "int64" else 0)
+        res = _lib.DeviceText()
+        _lib.check(self._lib.tkamd_decode_batch_device(self._h, d_ids_ptr, n_ids, d_begin_ptr, d_end_ptr, n_docs, flags, stream, C.byref(res)))
+        return DeviceText(self, res, n_docs, stream)
+
+    def decode_tensor(self, ids, lengths=None, starts=None, skip_special_tokens: bool = True) -> DeviceText:
+        """A 1-D or 2-D int32 / int64 torch tensor of ids on this tokenizer's device -> :class:`DeviceText`, on the current stream.
+        2-D: row r is ``ids[r, starts[r] : starts[r] + lengths[r]]`` (defaults: from 0, to the end of the row) -- a right-padded batch
+        passes ``lengths``, a left-padded one ``starts`` as well.  1-D: the sequences lie end to end, ``lengths`` says how long each is."""
+        import torch
+        if ids.dtype not in (torch.int32, torch.int64) or ids.dim() not in (1, 2):
+            raise TypeError("decode_tensor: ids must be a 1-D or 2-D int32 / int64 tensor")
+        if not ids.is_cuda or ids.device.index != self.device:
+            raise ValueError(f"decode_tensor: ids must live on cuda:{self.device}")
+        ids = ids.contiguous()
+        dev = ids.device
+        i64 = lambda x: torch.as_tensor(x, device=dev).to(torch.int64).reshape(-1)
+        with torch.cuda.device(dev):
+            if ids.dim() == 2:
+                rows, width = ids.shape
+                row0 = torch.arange(rows, device=dev, dtype=torch.int64) * width
+                begin = row0 if starts is None else row0 + i64(starts)
+                end = (row0 + width) if lengths is None else begin + i64(lengths)
+            else:
+                if lengths is None or starts is not None:
+                    raise ValueError("decode_tensor: a 1-D ids tensor takes lengths (and no starts)")
+                end = torch.cumsum(i64(lengths), 0)
+                begin = end - i64(lengths)
+                rows = end.numel()
+            if begin.numel() != rows or end.numel() != rows:
+                raise ValueError("decode_tensor: lengths / starts must hold one entry per sequence")
+            begin, end = begin.contiguous(), end.contiguous()
+            out = self.decode_batch_device(ids.data_ptr(), ids.numel(), begin.data_ptr(), end.data_ptr(), rows, skip_special_tokens,
+                                           "int64" if ids.dtype == torch.int64 else "int32", torch.cuda.current_stream(dev).cuda_stream)
+        return out                                           # (the call has waited for the stream: ids / begin / end may go)
 
     def encode_batch_device(self, d_text_ptr: int, d_doc_offsets_ptr: int, n_docs: int, n_bytes: int,
                             offsets: str = "none", word_ids: bool = False, stream: int = 0, unsynced: bool = False) -> DeviceBatch:
