@@ -102,7 +102,9 @@ typedef struct tkamd_info {
                                4 WhitespaceSplit, 5 BertPreTokenizer, 6 ByteLevel(use_regex=false), 7 the U+2581 front of SentencePiece-style BPE,
                                8 the chain of three Splits of DeepSeek-V3 / R1 + ByteLevel(use_regex=false),
                                9 Sequence[Digits, ByteLevel(GPT-2 regex)]: StarCoder / StarCoder2 / SantaCoder, Granite code, Command-R,
-                               10 Sequence[Split(the CLIP pattern, Removed, inverted), ByteLevel]: CLIP, the text encoders of Stable Diffusion */
+                               10 Sequence[Split(the CLIP pattern, Removed, inverted), ByteLevel]: CLIP, the text encoders of Stable Diffusion,
+                               11 Sequence[Split(BLOOM's pattern, Isolated), ByteLevel(use_regex=false)]: BLOOM / BLOOMZ.
+                               (7 also: Split(String " ", MergedWithPrevious) behind the U+2581 normalizers, where it is inert: Gemma-2 / Gemma-3) */
     int32_t normalizer;     /* 0 none, 1 BertNormalizer, 2 the U+2581 normalizers, 3 NFC, 4 Precompiled,
                                5 NFD / Lowercase / StripAccents, alone or chained in a Sequence, 6 NFKC,
                                7 Sequence[NFC, Replace(Regex "\\s+" -> " "), Lowercase] (with or without the Replace) of the CLIP files */

@@ -193,7 +193,7 @@ void Batch::check_request() {
           : n_bytes + (prefix_space ? n_docs + (int64_t)mcap : 0);
     if (n_x >= (int64_t)0xFFFFFF00ll) throw Invalid("batch larger than 4 GiB: split it (byte offsets are 32-bit on the device)");
     const bool bpe_path = hm.model == MODEL_BPE && !hm.char_bpe && (hm.pretok == PT_BYTELEVEL_GPT2 || hm.pretok == PT_LLAMA3 || hm.pretok == PT_SPLIT_CHAIN || hm.pretok == PT_DIGITS_GPT2 ||
-                                                                      hm.pretok == PT_BYTELEVEL_NOREGEX || hm.pretok == PT_CLIP);
+                                                                      hm.pretok == PT_BYTELEVEL_NOREGEX || hm.pretok == PT_CLIP || hm.pretok == PT_BLOOM);
     const bool local_pretok = hm.pretok == PT_WHITESPACE || hm.pretok == PT_WHITESPACE_SPLIT || hm.pretok == PT_BERT;
     const bool word_models = (hm.model == MODEL_WORDLEVEL || hm.model == MODEL_WORDPIECE) && local_pretok;
     const bool char_bpe = hm.model == MODEL_BPE && hm.char_bpe && (local_pretok || metaspace);      // BPE over characters rides the word models' pre-tokenizers, or the "▁" front
@@ -766,6 +766,15 @@ void Batch::pretokenize() {
         pf.begin("pretok_digits");
         launch_pretok_digits(st, x_text, n_x, x_len_dev, w->w_docmask.as<ull>(), t->dt.uc1, t->dt.uc2, hm.digits_individual, w->w_startmask.as<ull>(),
                              lead_done ? w->w_leadmask.as<ull>() : nullptr);
+        pf.end();
+    } else if (hm.pretok == PT_BLOOM) {
+        // Split(BLOOM's pattern, Isolated) + ByteLevel(use_regex=false): the pieces the Split leaves are the pre-tokens, one lane kernel
+        if (off_mode == TKAMD_OFFSETS_CHAR && x_text == d_text && !x_len_dev && n_x == n_bytes) {
+            w->w_leadmask.reserve((size_t)(W0 + 1) * 8);
+            lead_done = true;
+        }
+        pf.begin("pretok_bloom");
+        launch_pretok_bloom(st, x_text, n_x, x_len_dev, w->w_docmask.as<ull>(), t->dt.uc1, t->dt.uc2, w->w_startmask.as<ull>(), lead_done ? w->w_leadmask.as<ull>() : nullptr);
         pf.end();
     } else if (hm.pretok == PT_CLIP) {
         // Split(the CLIP pattern, Removed, inverted) + ByteLevel: one lane kernel writes the starts and the ends -- the \s runs belong to no

@@ -3,6 +3,7 @@
 #include "bert_norm_core.hpp"
 #include "nfc_core.hpp"
 #include "precompiled_core.hpp"
+#include "pretok_bloom_core.hpp"
 
 #include <algorithm>
 #include <cctype>
@@ -221,6 +222,12 @@ void build_unicode(HostModel& m) {
     if (m.pretok == PT_DIGITS_GPT2)
         for (const UcRun& r : kUcNumericRuns)
             for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] |= r.flags;
+    // the 39 chars BLOOM's Split class leaves out, Oniguruma's \s and fourteen punctuation marks: the same bit, for this kind's handles only
+    if (m.pretok == PT_BLOOM) {
+        for (uint32_t cp = 0; cp < 0x110000u; ++cp)
+            if (flat[cp] & UC_ONIG_S) flat[cp] |= UC_BLOOM_X;
+        for (uint32_t cp : kBloomPunct) flat[cp] |= UC_BLOOM_X;
+    }
     m.uc_stage1.assign(UC_STAGE1_LEN, 0);
     m.uc_stage2.clear();
     std::unordered_map<std::string, uint16_t> seen;
@@ -772,6 +779,8 @@ const char* const kMetaspace = "\xE2\x96\x81";     // U+2581, the "▁" of Sente
 // the Split pattern of the CLIP files (CLIPTokenizerFast, the text encoders of Stable Diffusion / SDXL, the OpenCLIP conversions), byte for
 // byte: with behavior Removed and invert = true its matches are the pre-tokens and the \s runs between them belong to none (pretok_clip_core.hpp)
 const char* const kClipPattern = "'s|'t|'re|'ve|'m|'ll|'d|[\\p{L}]+|[\\p{N}]|[^\\s\\p{L}\\p{N}]+";
+// BLOOM / BLOOMZ: " ?" and a run of the chars outside a class of 39 (pretok_bloom_core.hpp)
+const char* const kBloomPattern = " ?[^(\\s|[.,!?…。，、।۔،])]+";
 
 // A JSON number as serde_json reads it into an f64 WITHOUT its float_roundtrip feature -- how the reference is built (tokenizers/Cargo.toml:
 // serde_json = "1.0", no features) and so what its Unigram scores are: the digits are gathered into a u64 significand (those that no
@@ -888,6 +897,27 @@ PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
         throw Unsupported("pre_tokenizer: null is outside the hot path");
     }
     std::string type = pt->get_str("type");
+    if (type == "Split") {
+        // Gemma-2 / Gemma-3: Split(String " ", MergedWithPrevious) behind Replace(" " -> "▁").  The normalizer leaves no space to split at,
+        // so the Split is inert and the layout is the "▁" front with a null pre-tokenizer (the whole-piece checks of the model below stay in
+        // force).  Inverted it is not inert -- the whole text is one match -- and nothing else about it is taken on trust.
+        if (m.norm != NORM_METASPACE)
+            throw Unsupported("pre_tokenizer: Split alone is outside the hot path (only Split(String ' ', MergedWithPrevious) behind the U+2581 normalizers, "
+                              "where it is inert, is on it; and the Splits of Sequence[Split, ByteLevel])");
+        const JsonValue* pat = pt->get("pattern");
+        const JsonValue* lit = pat ? pat->get("String") : nullptr;
+        if (!lit || !lit->is_string())
+            throw Unsupported("pre_tokenizer: Split with a Regex pattern behind the U+2581 normalizers (only the String ' ', which they leave no match for, is on the path)");
+        if (lit->str != " ")
+            throw Unsupported("pre_tokenizer: Split with the String pattern '" + lit->str + "' behind the U+2581 normalizers (only the String ' ', which they leave no match for, "
+                              "is on the path)");
+        const std::string beh = pt->get_str("behavior");
+        if (beh != "MergedWithPrevious")
+            throw Unsupported("pre_tokenizer: Split(String ' ') with behavior '" + beh + "' behind the U+2581 normalizers (only MergedWithPrevious is on the path)");
+        if (pt->get_bool("invert", false))
+            throw Unsupported("pre_tokenizer: Split(String ' ') with invert = true behind the U+2581 normalizers (inverted, the whole text is one match: not inert)");
+        return PT_METASPACE;
+    }
     // (the U+2581 normalizers are the front of SentencePiece conversions: in front of any pre-tokenizer but none they are outside the path)
     if (m.norm == NORM_METASPACE && type != "Metaspace")
         throw Unsupported("normalizer: the U+2581 normalizers (Prepend / Replace ' ' -> U+2581) in front of pre_tokenizer '" + type +
@@ -953,6 +983,15 @@ PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
                 // that is every pre-token, not every document: no tokenizer in use is configured that way, and the path does not build it
                 if (b->get_bool("add_prefix_space", true))
                     throw Unsupported("pre_tokenizer: Sequence[Split, ByteLevel(add_prefix_space=true)] (a prefix space in front of every pre-token)");
+                if (rx == kBloomPattern) {
+                    // the BLOOM layout, by the exact pattern string (a pattern one char off is read by the family's parser below and refused
+                    // there); Isolated, not inverted, use_regex=false and no prefix space are established above
+                    if (m.norm != NORM_NONE)
+                        throw Unsupported("pre_tokenizer: BLOOM's Split + ByteLevel behind a normalizer is outside the hot path (only normalizer: null is on it)");
+                    m.byte_level = true;
+                    m.add_prefix_space = false;
+                    return PT_BLOOM;
+                }
                 SplitRule rule{};
                 bool gpt2 = false;
                 std::string why;
@@ -1617,6 +1656,8 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     const bool unigram = mtype == "Unigram";
     if (m.pretok == PT_CLIP && mtype != "BPE")
         throw Unsupported("pre_tokenizer: the CLIP Split + ByteLevel in front of a " + mtype + " model (only in front of byte-level BPE with an end_of_word_suffix is it on the path)");
+    if (m.pretok == PT_BLOOM && mtype != "BPE")
+        throw Unsupported("pre_tokenizer: BLOOM's Split + ByteLevel in front of a " + mtype + " model (only in front of byte-level BPE is it on the path)");
     if (m.pretok == PT_DIGITS_GPT2 && mtype != "BPE")
         throw Unsupported("pre_tokenizer: Sequence[Digits, ByteLevel] in front of a " + mtype + " model (only in front of byte-level BPE is it on the path)");
     if (unigram ? !(vocab && vocab->is_array()) : !(vocab && vocab->is_object())) throw Invalid("tokenizer.json: model.vocab missing");

@@ -40,6 +40,7 @@
 #include "pretok_ds3_core.hpp"
 #include "pretok_digits_core.hpp"
 #include "pretok_clip_core.hpp"
+#include "pretok_bloom_core.hpp"
 #include "pretok_local_core.hpp"
 #include "unigram_core.hpp"
 #include "utf8_lossy_core.hpp"
@@ -93,6 +94,7 @@ static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)(
 #include "kernels/pretok_ds3.hip"
 #include "kernels/pretok_digits.hip"
 #include "kernels/pretok_clip.hip"
+#include "kernels/pretok_bloom.hip"
 #include "kernels/pretok_local.hip"
 #include "kernels/bert_norm.hip"
 #include "kernels/nfc.hip"

@@ -418,6 +418,10 @@ void launch_pretok_digits(hipStream_t st, const uint8_t* text, int64_t n_bytes, 
 // ((n_bytes >> 6) + 1 words: an end bit can sit at byte n_bytes)
 void launch_pretok_clip(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* docmask,
                         const uint16_t* uc1, const uint8_t* uc2, unsigned long long* startmask, unsigned long long* endmask, unsigned long long* leadmask = nullptr);
+// Split(BLOOM's pattern, Isolated) + ByteLevel(use_regex=false) of BLOOM / BLOOMZ (PT_BLOOM, pretok_bloom_core.hpp): the arguments of
+// launch_pretok_gpt2; uc2 carries UC_BLOOM_X
+void launch_pretok_bloom(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* docmask,
+                         const uint16_t* uc1, const uint8_t* uc2, unsigned long long* startmask, unsigned long long* leadmask = nullptr);
 void launch_leadmask(hipStream_t st, const uint8_t* text, int64_t n_bytes, unsigned long long* leadmask);
 void launch_seq_regroup(hipStream_t st, const int64_t* seq_off, int64_t n_seqs, int64_t n_words, const int64_t* word_tok_off, int64_t* seq_tok_off, uint32_t* widx,
                         int64_t* first_tok);

@@ -305,6 +305,13 @@ void launch_pretok_clip(hipStream_t st, const uint8_t* text, int64_t n_bytes, co
     if (leadmask) hipLaunchKernelGGL(k_pretok_clip<true>, grid, dim3(256), 0, st, text, n_bytes, len_dev, docmask, uc1, uc2, startmask, endmask, leadmask);
     else hipLaunchKernelGGL(k_pretok_clip<false>, grid, dim3(256), 0, st, text, n_bytes, len_dev, docmask, uc1, uc2, startmask, endmask, none);
 }
+void launch_pretok_bloom(hipStream_t st, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* docmask,
+                         const uint16_t* uc1, const uint8_t* uc2, unsigned long long* startmask, unsigned long long* leadmask) {
+    const dim3 grid(blocks_for((n_bytes >> 6) + 1, G2_WORDS_PER_BLOCK));
+    unsigned long long* const none = nullptr;
+    if (leadmask) hipLaunchKernelGGL(k_pretok_bloom<true>, grid, dim3(256), 0, st, text, n_bytes, len_dev, docmask, uc1, uc2, startmask, leadmask);
+    else hipLaunchKernelGGL(k_pretok_bloom<false>, grid, dim3(256), 0, st, text, n_bytes, len_dev, docmask, uc1, uc2, startmask, none);
+}
 void launch_leadmask(hipStream_t st, const uint8_t* text, int64_t n_bytes, unsigned long long* leadmask) {
     hipLaunchKernelGGL(k_leadmask, dim3(blocks_for(n_bytes + 64, 256 * 16)), dim3(256), 0, st, text, n_bytes, leadmask);
 }

@@ -23,6 +23,8 @@ enum : uint8_t {
     UC_RUST_WS = 32,  // char::is_whitespace   whitespace.rs:38, bert.rs:15
     UC_BERT_P = 64,   // is_bert_punc          bert.rs:5-7
     UC_RUST_N = 128,  // char::is_numeric      digits.rs (unicode_numeric_ranges.inc; only in the table of a PT_DIGITS_GPT2 handle)
+    UC_BLOOM_X = 128, // the same bit in the table of a PT_BLOOM handle (no handle is both): the char is one of the 39 that BLOOM's Split
+                      // class leaves out -- Oniguruma's \s and fourteen punctuation marks (pretok_bloom_core.hpp kBloomPunct)
 };
 
 // 2-stage code-point table: stage1[cp >> 8] -> block index, stage2[block*256 + (cp & 255)] -> flags
@@ -196,7 +198,8 @@ enum PretokKind {
     PT_METASPACE = 7,        // the "▁" front of SentencePiece-style BPE: Metaspace (metaspace.rs:122-146), or null behind NORM_METASPACE
     PT_SPLIT_CHAIN = 8,      // Sequence[Split(\p{N}{1,3}), Split(CJK class +), Split(stage 3), ByteLevel(use_regex=false)]: DeepSeek-V3 / R1 (pretok_ds3_core.hpp)
     PT_DIGITS_GPT2 = 9,      // Sequence[Digits(individual_digits), ByteLevel(use_regex=true)]: StarCoder, Granite code, Command-R (pretok_digits_core.hpp)
-    PT_CLIP = 10             // Sequence[Split(the CLIP pattern, Removed, inverted), ByteLevel(add_prefix_space=false)]: CLIP, Stable Diffusion's text encoders (pretok_clip_core.hpp)
+    PT_CLIP = 10,            // Sequence[Split(the CLIP pattern, Removed, inverted), ByteLevel(add_prefix_space=false)]: CLIP, Stable Diffusion's text encoders (pretok_clip_core.hpp)
+    PT_BLOOM = 11            // Sequence[Split(BLOOM's pattern, Isolated), ByteLevel(add_prefix_space=false, use_regex=false)]: BLOOM / BLOOMZ (pretok_bloom_core.hpp)
 };
 // NORM_METASPACE: Sequence[Prepend("▁"), Replace(" " -> "▁")] or Replace(" " -> "▁") alone (prepend.rs:16-24, replace.rs:83)
 // NORM_NFC: NFC alone or Sequence[NFC] (normalizers/unicode.rs), in front of byte-level BPE (nfc_core.hpp, kernels/nfc.hip)

@@ -27,7 +27,7 @@ seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 budget = float(sys.argv[2]) if len(sys.argv) > 2 else 120
 names = sys.argv[3].split(",") if len(sys.argv) > 3 else [
     "bert_wordpiece_4000_specials", "bert_wordpiece_4000_added", "llama3_small_6000_specials", "bytelevel_prefix_trim_3000",
-    "wordlevel_whitespace_c1", "wordlevel_wssplit", "digits_individual", "digits_contiguous"]       # (gpt2_added_quirk / gpt2_added_tokens: 50 k vocabularies take ~40 s to load here)
+    "wordlevel_whitespace_c1", "wordlevel_wssplit", "digits_individual", "digits_contiguous", "bloom_bpe"]       # (gpt2_added_quirk / gpt2_added_tokens: 50 k vocabularies take ~40 s to load here)
 rnd = random.Random(seed)
 ALPHA = [
     "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ", "      ", " \t\n\r", "0123456789", ".,;:!?'\"()[]{}-_/\\@#$%^&*+=<>|~`",
