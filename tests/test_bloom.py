@@ -13,6 +13,7 @@ import pytest
 import tokenizers_amd as ta
 from oracle import synth
 from tests import bloom_cases as bc
+from tests import word_edge_totals as wt
 from tests.helpers import load_tokenizer_json
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -272,6 +273,13 @@ def test_device_edge_documents(harness, wheel):
         _check(harness, wheel, [d])
         _check(harness, wheel, docs[max(0, k - 1):k + 2])
     _check(harness, wheel, [bc.big_doc(), "", "x ", "y"])
+
+
+@pytest.mark.parametrize("total", wt.TOTALS)
+def test_total_lengths_at_the_workgroup_edge(total, harness, wheel):
+    """the text's last word, the position n_bytes and the edge of a workgroup together: one document and two"""
+    for docs in wt.batches(total):
+        _check(harness, wheel, docs)
 
 
 def test_300000_random_documents(harness, wheel):

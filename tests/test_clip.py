@@ -14,6 +14,7 @@ import pytest
 
 import tokenizers_amd as ta
 from tests import clip_cases as cc
+from tests import word_edge_totals as wt
 from tests.helpers import load_tokenizer_json
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -231,6 +232,13 @@ def test_edge_documents_alone_and_in_batches(harness, wheel):
     for b in (["1", "", "'s", "", "", "it's", ""], ["", "", "7"], ["x" * 63 + "'", "s" + "y" * 63, "'re"], ["x" * 62 + "it'", "s", " " * 9 + "1"], [" ", "'", " ", " 's", "1 "],
               ["x" * 64, "", " " * 64, "y" * 64], ["x" * 63 + " ", "x" * 64 + " "], ["\u0130" * 32, "\u0130" * 32, "\U0001f601" * 16]):
         _check(harness, wheel, b)
+
+
+@pytest.mark.parametrize("total", wt.TOTALS)
+def test_total_lengths_at_the_workgroup_edge(total, harness, wheel):
+    """the text's last word, the position n_bytes and the edge of a workgroup together: one document and two"""
+    for docs in wt.batches(total):
+        _check(harness, wheel, docs)
 
 
 def test_exhaustive_short_strings_at_every_word_offset(harness, wheel):

@@ -14,6 +14,7 @@ import pytest
 import tokenizers_amd as ta
 from oracle import synth
 from tests import digits_cases as dc
+from tests import word_edge_totals as wt
 from tests.helpers import load_tokenizer_json
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -224,6 +225,13 @@ def test_edge_documents_alone_and_in_batches(harness, wheel):
     for b in dc.batches():
         _check(harness, wheel, b)
     _check(harness, wheel, [d for d in dc.edge_docs() if len(d) < 2000])
+
+
+@pytest.mark.parametrize("total", wt.TOTALS)
+def test_total_lengths_at_the_workgroup_edge(total, harness, wheel):
+    """the text's last word, the position n_bytes and the edge of a workgroup together: one document and two"""
+    for docs in wt.batches(total):
+        _check(harness, wheel, docs)
 
 
 def test_exhaustive_short_strings_at_every_word_offset(harness, wheel):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from tests import gpt2_word_cases as gc
+from tests import word_edge_totals as wt
 from tests.helpers import load_tokenizer_json
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -90,6 +91,13 @@ def test_words_equal_windows_at_text_lengths(harness, js, n):
         total += b
     docs.append("x" * (n - total))
     _same(harness, js, *_pack(docs))
+
+
+@pytest.mark.parametrize("total", wt.TOTALS)
+def test_words_equal_windows_at_the_workgroup_edge_in_one_document_and_two(harness, js, total):
+    """the text's last word and the edge of a workgroup together, without a document edge near them"""
+    for docs in wt.batches(total):
+        _same(harness, js, *_pack(docs))
 
 
 def test_standalone_program_under_sanitizers(js, tmp_path):

@@ -719,23 +719,22 @@ void Batch::pretokenize() {
     launch_mark_doc_starts_n(st, lean ? raw_doc_off : x_doc_off, n_docs, n_x, x_len_dev, w->w_docmask.as<ull>(), d_err);
     if (matchmask) launch_mask_or(st, w->w_docmask.as<ull>(), w->w_hardmask.as<ull>(), W, n_match);   // match edges are hard boundaries
     pf.end();
+    // char offsets over a text the pre-tokenizer reads as it came: the lead-byte mask rides along in its lane kernel (where that has the form)
+    const bool text_as_it_came = off_mode == TKAMD_OFFSETS_CHAR && x_text == d_text && !x_len_dev && n_x == n_bytes;
+    const auto ride_lead = [&] {
+        w->w_leadmask.reserve((size_t)(W0 + 1) * 8);
+        lead_done = true;
+    };
     if (hm.pretok == PT_BYTELEVEL_GPT2) {
         pf.begin("pretok_gpt2_seq");
-        // (char offsets over a text the pre-tokenizer reads as it came: the lead-byte mask rides along)
-        if (off_mode == TKAMD_OFFSETS_CHAR && x_text == d_text && !x_len_dev && n_x == n_bytes) {
-            w->w_leadmask.reserve((size_t)(W0 + 1) * 8);
-            lead_done = true;
-        }
+        if (text_as_it_came) ride_lead();
         launch_pretok_gpt2(st, x_text, n_x, x_len_dev, w->w_docmask.as<ull>(), t->dt.uc1, t->dt.uc2, w->w_startmask.as<ull>(), lead_done ? w->w_leadmask.as<ull>() : nullptr);
         pf.end();
     } else if (hm.pretok == PT_LLAMA3) {
         w->w_endmask.reserve((size_t)(W + 1) * 8);          // reused as the "unresolved" mask
         w->w_slow_docs.reserve((size_t)(n_docs + 1) * 4);
-        // (char offsets over a text the pre-tokenizer reads as it came: the lead-byte mask rides in the lane kernel of the bit-parallel members)
-        if (off_mode == TKAMD_OFFSETS_CHAR && x_text == d_text && !x_len_dev && n_x == n_bytes && (split_rule_fast(hm.split_rule) || (split_rule_fast_cs(hm.split_rule) && t->t_ucc1.p))) {
-            w->w_leadmask.reserve((size_t)(W0 + 1) * 8);
-            lead_done = true;
-        }
+        // (the lane kernel of the bit-parallel members)
+        if (text_as_it_came && (split_rule_fast(hm.split_rule) || (split_rule_fast_cs(hm.split_rule) && t->t_ucc1.p))) ride_lead();
         pf.begin("pretok_llama3");
         w->w_slow_docs.reserve((size_t)((piece_off ? seg_cap : (size_t)n_docs) + 1) * 4);
         launch_pretok_llama3(st, x_text, n_x, x_len_dev, w->w_docmask.as<ull>(), t->dt.uc1, t->dt.uc2, w->w_startmask.as<ull>(),
@@ -747,10 +746,7 @@ void Batch::pretokenize() {
     } else if (hm.pretok == PT_SPLIT_CHAIN) {
         // the chained Split of DeepSeek-V3 / R1: the lane kernel, then the sequential matcher on the sentences it left a byte of undecided
         w->w_endmask.reserve((size_t)(W + 1) * 8);          // reused as the "unresolved" mask
-        if (off_mode == TKAMD_OFFSETS_CHAR && x_text == d_text && !x_len_dev && n_x == n_bytes) {
-            w->w_leadmask.reserve((size_t)(W0 + 1) * 8);
-            lead_done = true;
-        }
+        if (text_as_it_came) ride_lead();
         pf.begin("pretok_ds3");
         w->w_slow_docs.reserve((size_t)((piece_off ? seg_cap : (size_t)n_docs) + 1) * 4);
         launch_pretok_ds3(st, x_text, n_x, x_len_dev, w->w_docmask.as<ull>(), t->dt.uc1, t->dt.uc2, t->t_ucc1.as<uint16_t>(), t->t_ucc2.as<uint8_t>(),
@@ -759,20 +755,14 @@ void Batch::pretokenize() {
         pf.end();
     } else if (hm.pretok == PT_DIGITS_GPT2) {
         // Sequence[Digits, ByteLevel] of the StarCoder family: the GPT-2 rule inside the pieces Digits cuts, one lane kernel
-        if (off_mode == TKAMD_OFFSETS_CHAR && x_text == d_text && !x_len_dev && n_x == n_bytes) {
-            w->w_leadmask.reserve((size_t)(W0 + 1) * 8);
-            lead_done = true;
-        }
+        if (text_as_it_came) ride_lead();
         pf.begin("pretok_digits");
         launch_pretok_digits(st, x_text, n_x, x_len_dev, w->w_docmask.as<ull>(), t->dt.uc1, t->dt.uc2, hm.digits_individual, w->w_startmask.as<ull>(),
                              lead_done ? w->w_leadmask.as<ull>() : nullptr);
         pf.end();
     } else if (hm.pretok == PT_BLOOM) {
         // Split(BLOOM's pattern, Isolated) + ByteLevel(use_regex=false): the pieces the Split leaves are the pre-tokens, one lane kernel
-        if (off_mode == TKAMD_OFFSETS_CHAR && x_text == d_text && !x_len_dev && n_x == n_bytes) {
-            w->w_leadmask.reserve((size_t)(W0 + 1) * 8);
-            lead_done = true;
-        }
+        if (text_as_it_came) ride_lead();
         pf.begin("pretok_bloom");
         launch_pretok_bloom(st, x_text, n_x, x_len_dev, w->w_docmask.as<ull>(), t->dt.uc1, t->dt.uc2, w->w_startmask.as<ull>(), lead_done ? w->w_leadmask.as<ull>() : nullptr);
         pf.end();
@@ -781,10 +771,7 @@ void Batch::pretokenize() {
         // pre-token -- and the lookup, the merges' queues and the offsets take the ends from the mask, as behind the word models' pre-tokenizers
         w->w_endmask.reserve((size_t)(W + 1) * 8);
         has_end = true;
-        if (off_mode == TKAMD_OFFSETS_CHAR && x_text == d_text && !x_len_dev && n_x == n_bytes) {
-            w->w_leadmask.reserve((size_t)(W0 + 1) * 8);
-            lead_done = true;
-        }
+        if (text_as_it_came) ride_lead();
         pf.begin("pretok_clip");
         launch_pretok_clip(st, x_text, n_x, x_len_dev, w->w_docmask.as<ull>(), t->dt.uc1, t->dt.uc2, w->w_startmask.as<ull>(), w->w_endmask.as<ull>(),
                            lead_done ? w->w_leadmask.as<ull>() : nullptr);

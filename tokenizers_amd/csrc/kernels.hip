@@ -8,7 +8,9 @@
 //        │──────precompiled────► Precompiled normalizer (charsmap trie per grapheme cluster) in front of Unigram   kernels/precompiled.hip
 //        │──────nfkc───────────► NFKC (the K mode of the NFC core) in front of the "▁" front                kernels/nfkc.hip
 //        │──────metaspace──────► "▁" text X + its pre-token starts (SentencePiece-style BPE)        kernels/metaspace.hip
-//        │──────pretok_*───────► pre-token start (/ end) bitmask: per-lane 64-bit mask algebra    kernels/pretok_{gpt2,llama3,local}.hip
+//        │──────pretok_*───────► pre-token start (/ end) bitmask: per-lane 64-bit mask algebra    kernels/pretok_*.hip:
+//        │                       a 64-byte mask word a lane, or 48 bytes in a 64-byte window        {gpt2,digits,clip,bloom},
+//        │                       (window load and V / D: pretok_window.hip)                         pretok_window.hip + {llama3,ds3,local}
 //        │──────scan_emit──────► pt_start[P+1]   (byte offset of every pre-token = "split")       kernels/scan_emit.hip
 //        │──────lookup─────────► straight from the bitmasks: whole-word hit -> 1 token (LDS hot    kernels/lookup.hip
 //        │                       table, then the perfect hash in HBM); misses queued by length class
@@ -90,6 +92,7 @@ static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)(
 #include "kernels/scan_util.hip"
 #include "kernels/documents.hip"
 #include "kernels/pretok_gpt2.hip"
+#include "kernels/pretok_window.hip"
 #include "kernels/pretok_llama3.hip"
 #include "kernels/pretok_ds3.hip"
 #include "kernels/pretok_digits.hip"

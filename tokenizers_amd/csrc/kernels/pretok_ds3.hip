@@ -1,6 +1,6 @@
-// Part of kernels.hip (ONE translation unit: this file is #included there, inside namespace tkamd, after kernels/pretok_llama3.hip, whose
-// SqChunk loads, LUT copies and k_l3_slow_docs it shares; it is not compiled on its own).  The DeepSeek-V3 / R1 chain of three Splits in
-// front of ByteLevel(use_regex=false): per-lane kernel, sequential per-document matcher.  There is no tile tier.
+// Part of kernels.hip (ONE translation unit: this file is #included there, inside namespace tkamd, after kernels/pretok_window.hip, whose
+// helpers it calls, and kernels/pretok_llama3.hip, whose k_l3_slow_docs it shares; it is not compiled on its own).  The DeepSeek-V3 / R1
+// chain of three Splits in front of ByteLevel(use_regex=false): per-lane kernel, sequential per-document matcher.  There is no tile tier.
 
 // =================================================================================================
 // K_pretok_ds3_lane: Sequence[Split(\p{N}{1,3}), Split([CJK class]+), Split(main pattern), ByteLevel(use_regex=false)], bit-parallel PER
@@ -33,26 +33,9 @@ __global__ __launch_bounds__(256) void k_pretok_ds3_lane(const uint8_t* __restri
     unsigned long long st = 0, un = 0, ld = 0;
     if (a < n_bytes) {
         uint32_t w[16];
-        {
-            // four 16-byte loads (8-byte aligned: gfx950 takes dwordx4 at any alignment); only lane 0's window starts before the text
-            SqChunk c0{0u, 0u, 0u, 0u};
-            if (base >= 0) c0 = *(const SqChunk*)(text + base);
-            else { const uint2 t = *(const uint2*)text; c0.c = t.x; c0.d = t.y; }
-            const SqChunk c1 = *(const SqChunk*)(text + base + 16), c2 = *(const SqChunk*)(text + base + 32), c3 = *(const SqChunk*)(text + base + 48);
-            w[0] = c0.a; w[1] = c0.b; w[2] = c0.c; w[3] = c0.d; w[4] = c1.a; w[5] = c1.b; w[6] = c1.c; w[7] = c1.d;
-            w[8] = c2.a; w[9] = c2.b; w[10] = c2.c; w[11] = c2.d; w[12] = c3.a; w[13] = c3.b; w[14] = c3.c; w[15] = c3.d;
-        }
+        window_load(text, base, w);
         L3Window m;
-        const int vlo = base < 0 ? (int)-base : 0;
-        const int64_t rem = n_bytes - base;
-        m.V = (rem >= 64 ? ~0ull : ((1ull << rem) - 1ull)) & (~0ull << vlo);
-        if (base < 0) m.D = docmask[0] << L3W_HALO;
-        else {
-            const int64_t wi = base >> 6;
-            const int sh = (int)(base & 63);
-            m.D = docmask[wi] >> sh;
-            if (sh && wi + 1 < n_words_host) m.D |= docmask[wi + 1] << (64 - sh);
-        }
+        window_valid(base, n_bytes, n_words_host, docmask, L3W_HALO, m.V, m.D);
         const uint2* my_lut = lut + (threadIdx.x & (SQ_LUT_COPIES - 1)) * 256;
         m.L = m.N = m.W = m.R = m.SP = m.C = m.AP = m.MU = 0;
         m.B5 = 0;

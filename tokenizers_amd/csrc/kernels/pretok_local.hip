@@ -43,15 +43,7 @@ __global__ __launch_bounds__(256) void k_pretok_local_lane(const uint8_t* __rest
     unsigned long long st = 0, en = 0;
     if (a <= n_bytes) {                                      // "<=": the end bit of the last pre-token sits at byte n_bytes
         uint32_t w[16];
-        {
-            SqChunk c0{0, 0, 0, 0};
-            if (base >= 0) c0 = *(const SqChunk*)(text + base);
-            else { const uint2 t = *(const uint2*)text; c0.c = t.x; c0.d = t.y; }
-            const SqChunk c1 = *(const SqChunk*)(text + base + 16), c2 = *(const SqChunk*)(text + base + 32),
-                          c3 = *(const SqChunk*)(text + base + 48);
-            w[0] = c0.a; w[1] = c0.b; w[2] = c0.c; w[3] = c0.d; w[4] = c1.a; w[5] = c1.b; w[6] = c1.c; w[7] = c1.d;
-            w[8] = c2.a; w[9] = c2.b; w[10] = c2.c; w[11] = c2.d; w[12] = c3.a; w[13] = c3.b; w[14] = c3.c; w[15] = c3.d;
-        }
+        window_load(text, base, w);
         LocalWindow m;
         const int vlo = base < 0 ? (int)-base : 0;
         const int64_t rem = n_bytes - base;                  // >= PLW_HALO
