@@ -347,6 +347,51 @@ int tkamd_decode_batch_device(tkamd_tokenizer* tok, const void* d_ids, int64_t n
  * pointers of tkamd_device_text directly. */
 int tkamd_device_text_read(tkamd_tokenizer* tok, const tkamd_device_text* text, int64_t n_docs, int64_t n_slack, void* hip_stream,
                            uint8_t* bytes, int64_t* doc_offsets, int64_t* n_bytes);
+
+/* ---- streaming decode: DecodeStream for a batch of running sequences, state and text in HBM ---------------
+ * The reference's DecodeStream (tokenizer/mod.rs step_decode_stream; Python tokenizers.decoders.DecodeStream) is one object per
+ * sequence, stepped on the host.  A tkamd_decode_stream holds n_streams of them for one tokenizer handle: a step takes ONE new id per
+ * stream from HBM and leaves, per stream, the text that just became printable -- bit for bit what n_streams DecodeStreams return.
+ * Per stream the device keeps a window of ids and two counts (the reference's ids, prefix -- always the decode of the first ids of
+ * the window, so no text is stored -- and prefix_index); a step decodes three short ranges of every window with the range decode of
+ * tkamd_decode_batch_device (so first- and last-token forms, CTC's dedup, ByteFallback's runs and the lossy UTF-8 repair apply to the
+ * WINDOW, as in the reference), compares, emits and drains.
+ *   new  : flags = TKAMD_SKIP_SPECIAL or 0, kept for every step.  window = the most ids one stream's window may hold (0: 32; at least 2;
+ *          the reference's grows without bound -- it holds the ids since the last chunk, 1 - 3 on ordinary text).  n_streams >= 0.
+ *          A host-only handle gets TKAMD_ERR_DEVICE, a decoder outside the decode path TKAMD_ERR_UNSUPPORTED with decode_batch's message;
+ *          a multi-device handle streams on devices[0].  The object must be freed before its tokenizer.
+ *   reset: the streams which[0 .. n) (host indices; NULL: all of them) are empty again -- a slot of a continuous batch taken by a new
+ *          sequence.  Enqueue only.
+ *   seed : reset of ONE stream whose window then holds ids[0 .. n) (host ids): the reference constructor's ids=.  n > window is
+ *          TKAMD_ERR_INVALID.  Enqueue only.
+ *   step : d_ids[n_streams] in HBM, uint32 / int32 bit patterns or, with TKAMD_DECODE_IDS_I64, int64 (a value outside [0, 2^32) is an id
+ *          without a token, as above); d_active uint8[n_streams] in HBM or NULL (all): a stream with 0 is not stepped, its state untouched.
+ *          With TKAMD_STREAM_IDS_HOST both are HOST arrays, which the call copies down itself (bindings without a HIP runtime).
+ *          *text: n_streams documents, document s = the chunk of stream s (empty for every status but 1), TKAMD_TEXT_PAD zero bytes
+ *          behind the text.  *d_status: uint8[n_streams] in HBM --
+ *            0 stepped, nothing to emit (the reference's None)     1 chunk     2 not stepped (inactive)
+ *            3 InvalidPrefix: the step's string does not start with the prefix (the reference's error); the state is what the reference
+ *              leaves -- the window holds the id, nothing is drained -- and the stream may be stepped again
+ *            4 window full: the id did not fit.  The stream is stuck -- every later step of it reports 4 -- until it is reset.
+ *          Text and status live in buffers of the stream object: valid until its next step, whatever else runs on the handle.
+ *          The step WAITS for hip_stream as the range decode does (two times, three for the ByteLevel decoder) and once more for the
+ *          byte count of the chunks (text->n_bytes).
+ *   read : the last step's text (with n_slack <= TKAMD_TEXT_PAD bytes of its slack), its CSR [n_streams + 1] and its status [n_streams]
+ *          copied to host memory in one wait; any of the three may be NULL.
+ *   peek : (tests, debugging) the state of ONE stream on the host, after a wait for the whole device: up to cap ids of its window,
+ *          their count *n, and the reference's prefix as ids (*pe: prefix = decode of the first *pe ids) and prefix_index (*pi).
+ * One call at a time per object (calls are serialised inside); the caller orders its streams as for any stream-ordered API. */
+#define TKAMD_STREAM_IDS_HOST 4u           /* tkamd_decode_stream_step: d_ids / d_active are host memory */
+typedef struct tkamd_decode_stream tkamd_decode_stream;
+int  tkamd_decode_stream_new(tkamd_tokenizer* tok, int64_t n_streams, int32_t window, uint32_t flags, tkamd_decode_stream** out);
+void tkamd_decode_stream_free(tkamd_decode_stream* s);
+int  tkamd_decode_stream_reset(tkamd_decode_stream* s, const int64_t* which, int64_t n, void* hip_stream);
+int  tkamd_decode_stream_seed(tkamd_decode_stream* s, int64_t which_one, const uint32_t* ids, int64_t n, void* hip_stream);
+int  tkamd_decode_stream_step(tkamd_decode_stream* s, const void* d_ids, const uint8_t* d_active, uint32_t flags, void* hip_stream,
+                              tkamd_device_text* text, const uint8_t** d_status);
+int  tkamd_decode_stream_read(tkamd_decode_stream* s, int64_t n_slack, void* hip_stream, uint8_t* bytes, int64_t* doc_offsets, uint8_t* status);
+int  tkamd_decode_stream_peek(tkamd_decode_stream* s, int64_t which_one, uint32_t* ids, int64_t cap, int64_t* n, int64_t* pe, int64_t* pi);
+
 /* String::from_utf8_lossy of ONE sequence -- bytes[0 .. n) -- by the host run of the very per-byte decision the kernels make
  * (csrc/utf8_lossy_core.hpp): out[0 .. *n_out).  Takes no handle and needs no device.  cap: what out holds; *n_out is set even when
  * it is too small (TKAMD_ERR_INVALID then). */

@@ -27,6 +27,7 @@ WANT_OVERFLOW = 32
 NO_SPECULATION = 64      # device entry, results consumed stream-ordered without tkamd_device_sync: the added tokens' matching passes and the NFC normalizer outright
 SKIP_SPECIAL = 1          # tkamd_decode_batch flag
 DECODE_IDS_I64 = 2        # tkamd_decode_batch_device: the ids are int64
+STREAM_IDS_HOST = 4       # tkamd_decode_stream_step: the ids and the mask are host arrays
 TEXT_PAD = 64
 MAX_STAGES = 24
 
@@ -43,6 +44,8 @@ SYMBOLS = [
     "tkamd_tokenizer_from_json_devices", "tkamd_tokenizer_set_collect", "tkamd_tokenizer_devices", "tkamd_shard_stats", "tkamd_debug_phases",
     "tkamd_pinned_alloc", "tkamd_pinned_free", "tkamd_encode_batch_paced",
     "tkamd_decode_batch_device", "tkamd_device_text_read", "tkamd_probe_utf8_lossy",
+    "tkamd_decode_stream_new", "tkamd_decode_stream_free", "tkamd_decode_stream_reset", "tkamd_decode_stream_seed", "tkamd_decode_stream_step",
+    "tkamd_decode_stream_read", "tkamd_decode_stream_peek",
 ]
 COLLECT_HOST, COLLECT_ROOT_P2P, COLLECT_ROOT_RCCL = 0, 1, 2
 
@@ -79,6 +82,16 @@ class UnsupportedError(TokenizersAmdError):
 
 class DeviceError(TokenizersAmdError):
     """HIP runtime failure or no GPU: the path has no CPU fallback."""
+
+
+class DecodeStreamError(TokenizersAmdError):
+    """A step of :class:`tokenizers_amd.DecodeStreams` on which a stream reported InvalidPrefix (3: the reference's
+    ``DecodeStreamError::InvalidPrefix``) or a full window (4).  ``status``: the status of every stream; ``chunks``: what the step
+    returned for every stream (None for the failing ones), so the healthy streams lose nothing."""
+
+    def __init__(self, msg: str, status: list, chunks: list):
+        super().__init__(msg)
+        self.status, self.chunks = status, chunks
 
 
 _lib = None
@@ -164,6 +177,20 @@ def load() -> C.CDLL:
     lib.tkamd_decode_batch_device.restype = i32
     lib.tkamd_device_text_read.argtypes = [vp, C.POINTER(DeviceText), i64, i64, vp, vp, vp, C.POINTER(i64)]
     lib.tkamd_device_text_read.restype = i32
+    lib.tkamd_decode_stream_new.argtypes = [vp, i64, C.c_int32, u32, C.POINTER(vp)]
+    lib.tkamd_decode_stream_new.restype = i32
+    lib.tkamd_decode_stream_free.argtypes = [vp]
+    lib.tkamd_decode_stream_free.restype = None
+    lib.tkamd_decode_stream_reset.argtypes = [vp, vp, i64, vp]
+    lib.tkamd_decode_stream_reset.restype = i32
+    lib.tkamd_decode_stream_seed.argtypes = [vp, i64, vp, i64, vp]
+    lib.tkamd_decode_stream_seed.restype = i32
+    lib.tkamd_decode_stream_step.argtypes = [vp, vp, vp, u32, vp, C.POINTER(DeviceText), C.POINTER(vp)]
+    lib.tkamd_decode_stream_step.restype = i32
+    lib.tkamd_decode_stream_read.argtypes = [vp, i64, vp, vp, vp, vp]
+    lib.tkamd_decode_stream_read.restype = i32
+    lib.tkamd_decode_stream_peek.argtypes = [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    lib.tkamd_decode_stream_peek.restype = i32
     lib.tkamd_probe_utf8_lossy.argtypes = [vp, i64, vp, i64, C.POINTER(i64)]
     lib.tkamd_probe_utf8_lossy.restype = i32
     lib.tkamd_decode_token.argtypes = [vp, u32, i32, vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

@@ -42,4 +42,5 @@ static_assert(TEXT_PAD == TKAMD_TEXT_PAD, "the kernels rely on the slack the ABI
 #include "capi/sharding.cpp"      // one host-entry call over the devices of a multi-device handle
 #include "capi/host_entry.cpp"      // the host-buffer entries (sliced, paced, mixed, words) and the result accessors
 #include "capi/decode.cpp"      // decode_batch
+#include "capi/decode_stream.cpp"      // DecodeStream for a batch of running sequences, around the range decode
 #include "capi/probes.cpp"      // host-side probes of the load-time tables, switches, measurement hooks

@@ -67,6 +67,92 @@ int tkamd_decode_batch(tkamd_tokenizer* t, const uint32_t* ids, const int64_t* t
 }
 // ---- decode_batch with the ids in HBM already and the text left there: the range gather in front of launch_decode's two phases, the lossy
 // UTF-8 repair (ByteLevel) and the zero slack behind them (kernels/decode.hip).  On the caller's stream, in the workspace keyed by it. ----
+// (the body: in workspace w, whose lock the caller holds, on the device the caller has set.  The public entry runs it in the workspace
+// keyed by the stream; a decode stream -- capi/decode_stream.cpp -- in a workspace of its own, so that neither moves the other's text.)
+static int decode_ranges_device(tkamd_tokenizer* t, Workspace* w, hipStream_t st, const void* d_ids, int64_t n_elems, const int64_t* d_begin, const int64_t* d_end,
+                                int64_t n_docs, uint32_t flags, tkamd_device_text* out) {
+    const HostModel& hm = t->hm;
+    // 1. the ranges: lengths, their scan into the token CSR, the first range that is not inside [0, n_elems]
+    const size_t nd = (size_t)n_docs + 1;
+    w->dw_tok_off.reserve(nd * 8);
+    w->dw_out_off.reserve(nd * 8);
+    w->dw_rpos.reserve(nd * 4 + 64);
+    w->dw_len.reserve(nd * 4 + 64);
+    w->dw_bsum.reserve((nd / 256 + 2) * 4);
+    w->dw_total.reserve(64);
+    int64_t* scalars = w->dw_total.as<int64_t>();
+    launch_decode_ranges(st, d_begin, d_end, n_docs, n_elems, w->dw_len.as<uint32_t>(), w->dw_bsum.as<uint32_t>(), w->dw_rpos.as<uint32_t>(),
+                         w->dw_tok_off.as<int64_t>(), scalars);
+    HIP_CHECK(hipGetLastError());
+    int64_t head[3] = {0, 0, 0};                           // tokens by the u32 scan, the first bad range, tokens summed in 64 bits
+    HIP_CHECK(hipMemcpyAsync(head, scalars + 1, 24, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (head[1]) {
+        const int64_t d = n_docs - (head[1] >> 4);
+        const int why = (int)(head[1] & 15);
+        throw Invalid("decode_batch: sequence " + std::to_string(d) + (why & 1 ? ": begin > end" : why & 2 ? ": begin < 0" : why & 4 ? ": end > n_ids" : ": 2^31 ids or more"));
+    }
+    // (overlapping ranges can sum past 2^32 over a small array: the limit is held against the 64-bit sum, which the scan's total
+    // equals below it)
+    if (head[2] < 0 || head[2] >= ((int64_t)1 << 31)) throw Invalid("more than 2^31 tokens in one decode_batch call");
+    const int64_t n_tok = head[0];
+    if (n_tok != head[2]) throw std::runtime_error("decode_batch: the token scan and the token sum disagree");
+    // 2. the ids, one lane each, into the array launch_decode reads; its first phase
+    const uint32_t n_ids = (uint32_t)(hm.dec_entry.size() / 4);
+    w->dw_ids.reserve((size_t)n_tok * 4 + 64);
+    w->dw_first.reserve((size_t)(n_tok / 32 + 2) * 4);
+    w->dw_len.reserve((size_t)n_tok * 4 + 64);
+    w->dw_bsum.reserve((size_t)(n_tok / 256 + 2) * 4);
+    w->dw_pos.reserve((size_t)n_tok * 4 + 64);
+    launch_decode_gather(st, d_ids, (flags & TKAMD_DECODE_IDS_I64) != 0, d_begin, w->dw_rpos.as<uint32_t>(), n_docs, n_tok, w->dw_ids.as<uint32_t>());
+    uint32_t* firstmask = hm.dec_position_dependent ? w->dw_first.as<uint32_t>() : nullptr;
+    uint32_t* badmask = nullptr;
+    if (hm.dec_has_bytes) { w->dw_bad.reserve((size_t)(n_tok / 32 + 2) * 4); badmask = w->dw_bad.as<uint32_t>(); }
+    uint32_t* dupmask = nullptr;
+    if (hm.dec_dedup) { w->dw_dup.reserve((size_t)(n_tok / 32 + 2) * 4); dupmask = w->dw_dup.as<uint32_t>(); }
+    const uint32_t from_end = hm.dec_special_is_last ? 1u : 0u;
+    const uint32_t skip = (flags & TKAMD_SKIP_SPECIAL) ? 1u : 0u;
+    launch_decode(st, w->dw_ids.as<uint32_t>(), w->dw_tok_off.as<int64_t>(), n_docs, n_tok, t->t_dec_entry.p, n_ids, t->t_dec_blob.as<uint8_t>(), skip,
+                  firstmask, w->dw_len.as<uint32_t>(), w->dw_bsum.as<uint32_t>(), w->dw_pos.as<uint32_t>(), scalars, w->dw_out_off.as<int64_t>(), nullptr,
+                  from_end, badmask, dupmask);
+    HIP_CHECK(hipGetLastError());
+    int64_t total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, scalars, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (total >= ((int64_t)1 << 32)) throw Invalid("decoded text beyond 4 GiB in one decode_batch call");
+    // 3. the bytes, and the zero slack an encode over them reads
+    w->dw_bytes.reserve((size_t)total + TKAMD_TEXT_PAD + 16);
+    launch_decode(st, w->dw_ids.as<uint32_t>(), w->dw_tok_off.as<int64_t>(), n_docs, n_tok, t->t_dec_entry.p, n_ids, t->t_dec_blob.as<uint8_t>(), skip,
+                  firstmask, w->dw_len.as<uint32_t>(), w->dw_bsum.as<uint32_t>(), w->dw_pos.as<uint32_t>(), scalars, w->dw_out_off.as<int64_t>(),
+                  w->dw_bytes.as<uint8_t>(), from_end, badmask, dupmask);
+    launch_decode_zero_pad(st, w->dw_bytes.as<uint8_t>(), scalars);
+    HIP_CHECK(hipGetLastError());
+    out->d_bytes = w->dw_bytes.as<uint8_t>();
+    out->d_doc_offsets = w->dw_out_off.as<int64_t>();
+    out->d_n_bytes = scalars;
+    out->n_bytes = total;
+    // 4. String::from_utf8_lossy of the ByteLevel decoder: what the repaired text would hold and whether anything is to repair
+    if (hm.decoder != DEC_BYTELEVEL || total == 0) return TKAMD_OK;
+    launch_utf8_lossy_count(st, w->dw_bytes.as<uint8_t>(), total, w->dw_out_off.as<int64_t>(), n_docs, scalars);
+    HIP_CHECK(hipGetLastError());
+    int64_t fix[2] = {0, 0};                               // bytes of the repaired text, invalid subparts
+    HIP_CHECK(hipMemcpyAsync(fix, scalars + 4, 16, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (fix[1] == 0) return TKAMD_OK;
+    if (fix[0] >= ((int64_t)1 << 32)) throw Invalid("decoded text beyond 4 GiB in one decode_batch call");
+    w->dw_fixed.reserve((size_t)fix[0] + TKAMD_TEXT_PAD + 16);
+    w->dw_len.reserve((size_t)total * 4 + 64);
+    w->dw_bsum.reserve((size_t)(total / 256 + 2) * 4);
+    w->dw_pos.reserve((size_t)total * 4 + 64);
+    launch_utf8_lossy_repair(st, w->dw_bytes.as<uint8_t>(), total, w->dw_out_off.as<int64_t>(), n_docs, w->dw_len.as<uint32_t>(), w->dw_bsum.as<uint32_t>(),
+                             w->dw_pos.as<uint32_t>(), scalars + 4, w->dw_fixed.as<uint8_t>());
+    launch_decode_zero_pad(st, w->dw_fixed.as<uint8_t>(), scalars + 4);
+    HIP_CHECK(hipGetLastError());
+    out->d_bytes = w->dw_fixed.as<uint8_t>();
+    out->d_n_bytes = scalars + 4;
+    out->n_bytes = fix[0];
+    return TKAMD_OK;
+}
 int tkamd_decode_batch_device(tkamd_tokenizer* t, const void* d_ids, int64_t n_elems, const int64_t* d_begin, const int64_t* d_end, int64_t n_docs,
                               uint32_t flags, void* hip_stream, tkamd_device_text* out) {
     if (!t || !out || n_docs < 0 || n_elems < 0 || (n_docs > 0 && (!d_begin || !d_end)) || (n_elems > 0 && !d_ids) || n_docs >= ((int64_t)1 << 31))
@@ -74,93 +160,13 @@ int tkamd_decode_batch_device(tkamd_tokenizer* t, const void* d_ids, int64_t n_e
     *out = tkamd_device_text{};
     if (t->device < 0) return set_error(TKAMD_ERR_DEVICE, "host-only tokenizer handle: no HIP device bound (there is no CPU fallback)");
     return guarded([&]() -> int {
-        const HostModel& hm = t->hm;
-        if (hm.decoder == DEC_UNSUPPORTED) throw Unsupported("decode_batch: " + hm.dec_unsupported);
+        if (t->hm.decoder == DEC_UNSUPPORTED) throw Unsupported("decode_batch: " + t->hm.dec_unsupported);
         check_not_forked();
         hipStream_t st = (hipStream_t)hip_stream;
         Workspace* w = workspace_of_stream(t, st, true);
         std::lock_guard<std::mutex> lk(w->mu);
         HIP_CHECK(hipSetDevice(t->device));
-        // 1. the ranges: lengths, their scan into the token CSR, the first range that is not inside [0, n_elems]
-        const size_t nd = (size_t)n_docs + 1;
-        w->dw_tok_off.reserve(nd * 8);
-        w->dw_out_off.reserve(nd * 8);
-        w->dw_rpos.reserve(nd * 4 + 64);
-        w->dw_len.reserve(nd * 4 + 64);
-        w->dw_bsum.reserve((nd / 256 + 2) * 4);
-        w->dw_total.reserve(64);
-        int64_t* scalars = w->dw_total.as<int64_t>();
-        launch_decode_ranges(st, d_begin, d_end, n_docs, n_elems, w->dw_len.as<uint32_t>(), w->dw_bsum.as<uint32_t>(), w->dw_rpos.as<uint32_t>(),
-                             w->dw_tok_off.as<int64_t>(), scalars);
-        HIP_CHECK(hipGetLastError());
-        int64_t head[3] = {0, 0, 0};                           // tokens by the u32 scan, the first bad range, tokens summed in 64 bits
-        HIP_CHECK(hipMemcpyAsync(head, scalars + 1, 24, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (head[1]) {
-            const int64_t d = n_docs - (head[1] >> 4);
-            const int why = (int)(head[1] & 15);
-            throw Invalid("decode_batch: sequence " + std::to_string(d) + (why & 1 ? ": begin > end" : why & 2 ? ": begin < 0" : why & 4 ? ": end > n_ids" : ": 2^31 ids or more"));
-        }
-        // (overlapping ranges can sum past 2^32 over a small array: the limit is held against the 64-bit sum, which the scan's total
-        // equals below it)
-        if (head[2] < 0 || head[2] >= ((int64_t)1 << 31)) throw Invalid("more than 2^31 tokens in one decode_batch call");
-        const int64_t n_tok = head[0];
-        if (n_tok != head[2]) throw std::runtime_error("decode_batch: the token scan and the token sum disagree");
-        // 2. the ids, one lane each, into the array launch_decode reads; its first phase
-        const uint32_t n_ids = (uint32_t)(hm.dec_entry.size() / 4);
-        w->dw_ids.reserve((size_t)n_tok * 4 + 64);
-        w->dw_first.reserve((size_t)(n_tok / 32 + 2) * 4);
-        w->dw_len.reserve((size_t)n_tok * 4 + 64);
-        w->dw_bsum.reserve((size_t)(n_tok / 256 + 2) * 4);
-        w->dw_pos.reserve((size_t)n_tok * 4 + 64);
-        launch_decode_gather(st, d_ids, (flags & TKAMD_DECODE_IDS_I64) != 0, d_begin, w->dw_rpos.as<uint32_t>(), n_docs, n_tok, w->dw_ids.as<uint32_t>());
-        uint32_t* firstmask = hm.dec_position_dependent ? w->dw_first.as<uint32_t>() : nullptr;
-        uint32_t* badmask = nullptr;
-        if (hm.dec_has_bytes) { w->dw_bad.reserve((size_t)(n_tok / 32 + 2) * 4); badmask = w->dw_bad.as<uint32_t>(); }
-        uint32_t* dupmask = nullptr;
-        if (hm.dec_dedup) { w->dw_dup.reserve((size_t)(n_tok / 32 + 2) * 4); dupmask = w->dw_dup.as<uint32_t>(); }
-        const uint32_t from_end = hm.dec_special_is_last ? 1u : 0u;
-        const uint32_t skip = (flags & TKAMD_SKIP_SPECIAL) ? 1u : 0u;
-        launch_decode(st, w->dw_ids.as<uint32_t>(), w->dw_tok_off.as<int64_t>(), n_docs, n_tok, t->t_dec_entry.p, n_ids, t->t_dec_blob.as<uint8_t>(), skip,
-                      firstmask, w->dw_len.as<uint32_t>(), w->dw_bsum.as<uint32_t>(), w->dw_pos.as<uint32_t>(), scalars, w->dw_out_off.as<int64_t>(), nullptr,
-                      from_end, badmask, dupmask);
-        HIP_CHECK(hipGetLastError());
-        int64_t total = 0;
-        HIP_CHECK(hipMemcpyAsync(&total, scalars, 8, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (total >= ((int64_t)1 << 32)) throw Invalid("decoded text beyond 4 GiB in one decode_batch call");
-        // 3. the bytes, and the zero slack an encode over them reads
-        w->dw_bytes.reserve((size_t)total + TKAMD_TEXT_PAD + 16);
-        launch_decode(st, w->dw_ids.as<uint32_t>(), w->dw_tok_off.as<int64_t>(), n_docs, n_tok, t->t_dec_entry.p, n_ids, t->t_dec_blob.as<uint8_t>(), skip,
-                      firstmask, w->dw_len.as<uint32_t>(), w->dw_bsum.as<uint32_t>(), w->dw_pos.as<uint32_t>(), scalars, w->dw_out_off.as<int64_t>(),
-                      w->dw_bytes.as<uint8_t>(), from_end, badmask, dupmask);
-        launch_decode_zero_pad(st, w->dw_bytes.as<uint8_t>(), scalars);
-        HIP_CHECK(hipGetLastError());
-        out->d_bytes = w->dw_bytes.as<uint8_t>();
-        out->d_doc_offsets = w->dw_out_off.as<int64_t>();
-        out->d_n_bytes = scalars;
-        out->n_bytes = total;
-        // 4. String::from_utf8_lossy of the ByteLevel decoder: what the repaired text would hold and whether anything is to repair
-        if (hm.decoder != DEC_BYTELEVEL || total == 0) return TKAMD_OK;
-        launch_utf8_lossy_count(st, w->dw_bytes.as<uint8_t>(), total, w->dw_out_off.as<int64_t>(), n_docs, scalars);
-        HIP_CHECK(hipGetLastError());
-        int64_t fix[2] = {0, 0};                               // bytes of the repaired text, invalid subparts
-        HIP_CHECK(hipMemcpyAsync(fix, scalars + 4, 16, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (fix[1] == 0) return TKAMD_OK;
-        if (fix[0] >= ((int64_t)1 << 32)) throw Invalid("decoded text beyond 4 GiB in one decode_batch call");
-        w->dw_fixed.reserve((size_t)fix[0] + TKAMD_TEXT_PAD + 16);
-        w->dw_len.reserve((size_t)total * 4 + 64);
-        w->dw_bsum.reserve((size_t)(total / 256 + 2) * 4);
-        w->dw_pos.reserve((size_t)total * 4 + 64);
-        launch_utf8_lossy_repair(st, w->dw_bytes.as<uint8_t>(), total, w->dw_out_off.as<int64_t>(), n_docs, w->dw_len.as<uint32_t>(), w->dw_bsum.as<uint32_t>(),
-                                 w->dw_pos.as<uint32_t>(), scalars + 4, w->dw_fixed.as<uint8_t>());
-        launch_decode_zero_pad(st, w->dw_fixed.as<uint8_t>(), scalars + 4);
-        HIP_CHECK(hipGetLastError());
-        out->d_bytes = w->dw_fixed.as<uint8_t>();
-        out->d_n_bytes = scalars + 4;
-        out->n_bytes = fix[0];
-        return TKAMD_OK;
+        return decode_ranges_device(t, w, st, d_ids, n_elems, d_begin, d_end, n_docs, flags, out);
     });
 }
 // a result of the call above copied to host memory: what a binding without a HIP runtime of its own (ctypes) reads it with

@@ -21,6 +21,7 @@
 //        │──────output─────────► ids[T] (single-pass compaction over published chunk totals), per-document CSR,      kernels/output.hip, results.hip
 //        │                       offsets, word ids, specials
 //   ids ────────decode─────────► text (decode_batch)                                              kernels/decode.hip
+//   id per stream ─decode_stream► the text that became printable (DecodeStream, around the range decode)   kernels/decode_stream.hip
 //
 // Every kernel cites the reference code it replaces.  All results are bit-exact integers.
 #include <hip/hip_runtime.h>
@@ -113,6 +114,7 @@ static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)(
 #include "kernels/output.hip"
 #include "kernels/epilogue.hip"
 #include "kernels/decode.hip"
+#include "kernels/decode_stream.hip"
 #include "kernels/launch.hip"
 
 }  // namespace tkamd

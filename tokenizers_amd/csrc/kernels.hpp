@@ -498,6 +498,24 @@ void launch_utf8_lossy_count(hipStream_t st, const uint8_t* text, int64_t n, con
 void launch_utf8_lossy_repair(hipStream_t st, const uint8_t* text, int64_t n, int64_t* doc_off, int64_t n_docs, uint32_t* len, uint32_t* bsum, uint32_t* pos,
                               int64_t* total, uint8_t* out);
 void launch_decode_zero_pad(hipStream_t st, uint8_t* text, const int64_t* n_dev);
+// streaming decode (kernels/decode_stream.hip): the state of n_streams independent DecodeStreams in HBM -- per stream a window of up to
+// `window` ids, how many it holds, the ids its prefix is the decode of (pe), the ids a drain drops (pi), and a byte: the window was full
+struct DsState {
+    uint32_t* win;               // [n_streams * window]
+    uint32_t *n, *pe, *pi;       // [n_streams]
+    uint8_t* stuck;              // [n_streams]
+    int64_t n_streams;
+    uint32_t window;
+};
+constexpr int DS_RANGES = 3;     // ranges of its window a stream has decoded per step: [0, pe), [0, n0), [0, n)
+// a step around the range decode: push (the new id, begin / end of DS_RANGES ranges a stream, the status of a stream that is not
+// stepped), then -- over the decoded ranges' CSR and text -- decide (status, chunk length, the prefix a step sets) and, behind the u32 scan
+// of the lengths, copy (chunk bytes, their CSR, the drained window)
+void launch_ds_push(hipStream_t st, const DsState& z, const void* ids, bool wide, const uint8_t* active, int64_t* begin, int64_t* end, uint8_t* status);
+void launch_ds_emit(hipStream_t st, const DsState& z, uint8_t* status, const int64_t* doc_off, const uint8_t* text, uint32_t* len, uint32_t* bsum, uint32_t* pos,
+                    int64_t* total, uint8_t* out, int64_t* out_off);
+void launch_ds_reset(hipStream_t st, const DsState& z, const int64_t* which, int64_t n_which);      // which == nullptr: every stream
+void launch_ds_seed(hipStream_t st, const DsState& z, int64_t stream, const uint32_t* ids, uint32_t n);
 int prepare_long_kernel();
 void launch_bpe_merge_long(hipStream_t st, int grid, const DevTables& t, const uint8_t* text, const QView& v, void* rows,
                            uint32_t* tmp_ids, uint32_t* tmp_end, uint32_t* list_huge, uint32_t* n_huge,

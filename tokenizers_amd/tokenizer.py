@@ -497,6 +497,109 @@ class DeviceText:
         return [buf[off[i]:off[i + 1]].decode("utf-8") for i in range(self.n_docs)]
 
 
+class DecodeStreams:
+    """``tokenizers.decoders.DecodeStream`` for ``n_streams`` running sequences at once (:meth:`Tokenizer.decode_stream`): one new id
+    per stream and step in, the text that just became printable out -- what ``n_streams`` DecodeStreams of the reference return, with
+    the windows, the decode and the comparison on the device (``tkamd_decode_stream_*``).  It belongs to the native handle it was made
+    from: make it after ``add_tokens`` / ``enable_truncation`` and their like, which replace that handle."""
+
+    def __init__(self, tok: "Tokenizer", n_streams: int, skip_special_tokens: bool = False, window: int = 32):
+        self._tok, self._lib, self.n_streams, self.window = tok, tok._lib, int(n_streams), int(window) or 32
+        self.skip_special_tokens = bool(skip_special_tokens)
+        h = C.c_void_p()
+        _lib.check(self._lib.tkamd_decode_stream_new(tok._h, self.n_streams, int(window), _lib.SKIP_SPECIAL if skip_special_tokens else 0, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                self._lib.tkamd_decode_stream_free(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def step_device(self, d_ids_ptr: int, d_active_ptr: int = 0, ids_dtype: str = "uint32", stream: int = 0, host: bool = False):
+        """Raw pointers (``tkamd_decode_stream_step``): ``n_streams`` ids and, optionally, as many uint8 flags, in HBM -- or, with
+        ``host``, in host memory -> (:class:`DeviceText` of ``n_streams`` documents, device pointer of the uint8 status of every stream)."""
+        if ids_dtype not in ("uint32", "int32", "int64"):
+            raise ValueError("ids_dtype must be 'uint32', 'int32' or 'int64'")
+        flags = (_lib.DECODE_IDS_I64 if ids_dtype == "int64" else 0) | (_lib.STREAM_IDS_HOST if host else 0)
+        res, status = _lib.DeviceText(), C.c_void_p()
+        _lib.check(self._lib.tkamd_decode_stream_step(self._h, d_ids_ptr, d_active_ptr or None, flags, stream, C.byref(res), C.byref(status)))
+        return DeviceText(self._tok, res, self.n_streams, stream), status.value or 0
+
+    def read(self, text: DeviceText, slack: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(bytes, doc_offsets, status) of the last step in host memory: one copy down (``tkamd_decode_stream_read``)"""
+        raw, off, status = np.empty(text.n_bytes + slack, dtype=np.uint8), np.empty(self.n_streams + 1, dtype=np.int64), np.empty(self.n_streams, dtype=np.uint8)
+        _lib.check(self._lib.tkamd_decode_stream_read(self._h, slack, text._stream, raw.ctypes.data, off.ctypes.data, status.ctypes.data))
+        return raw, off, status
+
+    def step(self, ids, active=None) -> list:
+        """One id per stream (a list or a numpy array on the host; ``active``: truthy for the streams that step) -> per stream the chunk
+        that became printable, or None (nothing yet, or not stepped).  One device call and one copy down.  A stream that reports
+        InvalidPrefix or a full window raises :class:`DecodeStreamError`, which carries every stream's status and the other streams' chunks."""
+        ids = np.ascontiguousarray(ids)
+        if ids.dtype not in (np.uint32, np.int32, np.int64):
+            ids = ids.astype(np.int64)
+        if ids.shape != (self.n_streams,):
+            raise ValueError(f"step: one id per stream ({self.n_streams}) expected")
+        mask = None
+        if active is not None:
+            mask = np.ascontiguousarray(np.asarray(active).astype(bool).astype(np.uint8))
+            if mask.shape != (self.n_streams,):
+                raise ValueError(f"step: one flag per stream ({self.n_streams}) expected")
+        text, _ = self.step_device(ids.ctypes.data, mask.ctypes.data if mask is not None else 0, str(ids.dtype), 0, host=True)
+        raw, off, status = self.read(text)
+        buf = raw.tobytes()
+        chunks = [buf[off[i]:off[i + 1]].decode("utf-8") if status[i] == 1 else None for i in range(self.n_streams)]
+        bad = [i for i in range(self.n_streams) if status[i] >= 3]
+        if bad:
+            what = ", ".join(f"stream {i}: " + ("InvalidPrefix" if status[i] == 3 else "window full") for i in bad[:8])
+            raise _lib.DecodeStreamError(f"decode_stream step: {what}" + (" ..." if len(bad) > 8 else ""), [int(x) for x in status], chunks)
+        return chunks
+
+    def step_tensor(self, ids, active=None):
+        """A 1-D int32 / int64 torch tensor of ``n_streams`` ids on the tokenizer's device (``active``: a bool / uint8 tensor there), on
+        the current stream -> (:class:`DeviceText`, uint8 status tensor [n_streams]); both live in the object until its next step.
+        Never raises on a stream's status."""
+        import torch
+        if ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 1 or ids.numel() != self.n_streams:
+            raise TypeError("step_tensor: ids must be a 1-D int32 / int64 tensor of n_streams ids")
+        if not ids.is_cuda or ids.device.index != self._tok.device:
+            raise ValueError(f"step_tensor: ids must live on cuda:{self._tok.device}")
+        ids = ids.contiguous()
+        if active is not None:
+            active = active.to(device=ids.device, dtype=torch.uint8).contiguous()
+            if active.numel() != self.n_streams:
+                raise ValueError("step_tensor: active must hold one flag per stream")
+        with torch.cuda.device(ids.device):
+            text, status = self.step_device(ids.data_ptr(), active.data_ptr() if active is not None else 0, "int64" if ids.dtype == torch.int64 else "int32",
+                                            torch.cuda.current_stream(ids.device).cuda_stream)
+        return text, text._tensor(status, (max(self.n_streams, 1),), "|u1")[: self.n_streams]
+
+    def reset(self, which=None, stream: int = 0) -> None:
+        """The named streams (all of them by default) are empty again."""
+        if which is None:
+            _lib.check(self._lib.tkamd_decode_stream_reset(self._h, None, 0, stream))
+            return
+        w = np.ascontiguousarray(which, dtype=np.int64).reshape(-1)
+        _lib.check(self._lib.tkamd_decode_stream_reset(self._h, w.ctypes.data, len(w), stream))
+
+    def seed(self, index: int, ids, stream: int = 0) -> None:
+        """Stream ``index`` starts over with ``ids`` in its window (the reference constructor's ``ids=``)."""
+        a = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        _lib.check(self._lib.tkamd_decode_stream_seed(self._h, int(index), a.ctypes.data, len(a), stream))
+
+    def peek(self, index: int) -> tuple[list, int, int]:
+        """(window ids, pe, pi) of one stream, read back on the host (tests, debugging): the reference's ids, its prefix as the count
+        of ids it is the decode of, its prefix_index."""
+        ids = np.zeros(self.window, dtype=np.uint32)
+        n, pe, pi = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.tkamd_decode_stream_peek(self._h, int(index), ids.ctypes.data, len(ids), C.byref(n), C.byref(pe), C.byref(pi)))
+        return [int(x) for x in ids[:n.value]], pe.value, pi.value
+
+
 class _BatchOwner:
     """Keeps a tkamd_batch alive while numpy views of its buffers exist."""
 
@@ -1161,6 +1264,11 @@ class Tokenizer:
             out = self.decode_batch_device(ids.data_ptr(), ids.numel(), begin.data_ptr(), end.data_ptr(), rows, skip_special_tokens,
                                            "int64" if ids.dtype == torch.int64 else "int32", torch.cuda.current_stream(dev).cuda_stream)
         return out                                           # (the call has waited for the stream: ids / begin / end may go)
+
+    def decode_stream(self, n_streams: int, skip_special_tokens: bool = False, window: int = 32) -> DecodeStreams:
+        """``n_streams`` DecodeStreams (``tokenizers.decoders.DecodeStream``) stepped together on the device: see :class:`DecodeStreams`.
+        ``window``: the ids one stream may hold back before it reports a full window."""
+        return DecodeStreams(self, n_streams, skip_special_tokens, window)
 
     def encode_batch_device(self, d_text_ptr: int, d_doc_offsets_ptr: int, n_docs: int, n_bytes: int,
                             offsets: str = "none", word_ids: bool = False, stream: int = 0, unsynced: bool = False) -> DeviceBatch:
