@@ -331,8 +331,15 @@ void Batch::empty_batch() {
 
 AddedArgs Batch::args_of(int c) {
     AddedArgs a{t->t_at_blob[c].as<uint8_t>(), t->t_at_off[c].as<uint32_t>(), t->t_at_first[c].as<uint32_t>(), t->t_at_id[c].as<uint32_t>(),
-                t->t_at_flags[c].as<uint32_t>(), {0ull, 0ull, 0ull, 0ull}, 0u, {0u, 0u, 0u, 0u}, t->encode_special ? 1u : 0u};
-    const std::vector<uint32_t>& first = hm.at[c].first;
+                t->t_at_flags[c].as<uint32_t>(), {0ull, 0ull, 0ull, 0ull}, 0u, {0u, 0u, 0u, 0u}, t->encode_special ? 1u : 0u, (c == 1 && hm.nfc_ws_fold) ? 1u : 0u};
+    std::vector<uint32_t> first = hm.at[c].first;
+    if (a.ws_fold && first.size() == 257 && first[' ' + 1] > first[' ']) {
+        // a pattern that opens with ' ' may start at any \s char: the first bytes of the 25 of them (k_added_candidates)
+        std::vector<uint32_t> has(256, 0u);
+        for (uint32_t b = 0; b < 256u; ++b) has[b] = first[b + 1] > first[b] ? 1u : 0u;
+        for (uint32_t b : {9u, 10u, 11u, 12u, 13u, 0xC2u, 0xE1u, 0xE2u, 0xE3u}) has[b] = 1u;
+        for (uint32_t b = 0; b < 256u; ++b) first[b + 1] = first[b] + has[b];       // (only "is the bucket empty" is read below)
+    }
     for (uint32_t b = 0; b < 256u && first.size() == 257; ++b)
         if (first[b + 1] > first[b]) {
             a.first_set[b >> 6] |= 1ull << (b & 63);
@@ -1083,6 +1090,7 @@ void Batch::compact_and_meta() {
         }
         a.trim_offsets = hm.trim_offsets;
         a.trim_matches_only = !hm.byte_level;            // (a model that is not byte-level: only an added token's slice can hold what is trimmed; the loader checked the vocabulary)
+        a.trim_token_text = hm.model == MODEL_UNIGRAM && !hm.uni_bytes;
         a.pp_add_prefix_space = hm.pp_add_prefix_space;
         a.want_offsets = off_mode != TKAMD_OFFSETS_NONE;
         a.char_mode = off_mode == TKAMD_OFFSETS_CHAR;

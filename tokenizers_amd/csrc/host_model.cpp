@@ -1383,7 +1383,8 @@ HostModel HostModel::from_json(const char* json, size_t len) {
             // NFC alone inside a Sequence is NFC; next to any other normalizer the alignment of one is the input of the other: not on the path
             // ... but for the chain of the CLIP files, Sequence[NFC, Replace(Regex "\\s+" -> " "), Lowercase]: Lowercase is a map of single chars
             // that the NFC core applies to what it composed (nfc_core.hpp NFC_LOWER), and the Replace only touches runs of \s chars, which the CLIP
-            // pre-tokenizer drops -- it is inert there, and no kernel runs for it.  Whether the CLIP pre-tokenizer follows is asked below.
+            // pre-tokenizer drops -- it is inert there, and no kernel runs for it (but for the normalized added tokens: nfc_ws_fold).  Whether the
+            // CLIP pre-tokenizer follows is asked below.
             const auto& arr = norm->get("normalizers")->arr;
             if (arr.size() != 1) {
                 const std::string base = "normalizer: NFC inside a longer Sequence is outside the hot path (only NFC alone, or Sequence[NFC], is on it; and "
@@ -1395,6 +1396,7 @@ HostModel HostModel::from_json(const char* json, size_t len) {
                     const JsonValue* pat = arr[1]->get("pattern");
                     if (!pat || !pat->is_object() || !pat->get("Regex") || pat->get_str("Regex") != "\\s+" || arr[1]->get_str("content") != " ")
                         throw Unsupported(base + "this Sequence's Replace is another one)");
+                    m.nfc_ws_fold = true;
                 }
                 const JsonValue* pt = root->get("pre_tokenizer");
                 const JsonValue* seq = (pt && pt->is_object() && pt->get_str("type") == "Sequence") ? pt->get("pretokenizers") : nullptr;
@@ -2093,6 +2095,20 @@ HostModel HostModel::from_json(const char* json, size_t len) {
                 bool refused = false;
                 pat = m.nfc_normalize(a.content, nullptr, &refused);
                 if (refused) throw Unsupported("added token '" + a.content + "' holds a run of more than 48 combining characters (NFC of such a run is not built)");
+                if (m.nfc_ws_fold) {                               // Replace(Regex "\\s+" -> " ") of the CLIP chain: every \s run of the pattern is one ' '
+                    std::string folded;
+                    bool in_run = false;
+                    for (size_t i = 0; i < pat.size();) {
+                        uint32_t cp = 0;
+                        const int l = std::max(1, utf8_decode((const uint8_t*)pat.data() + i, pat.size() - i, &cp));
+                        const bool ws = cp < 0x110000u && (m.uc_stage2[((size_t)m.uc_stage1[cp >> 8] << 8) | (cp & 255u)] & UC_RX_S);
+                        if (!ws) folded.append(pat, i, (size_t)l);
+                        else if (!in_run) folded.push_back(' ');
+                        in_run = ws;
+                        i += (size_t)l;
+                    }
+                    pat = folded;
+                }
             }
             if (a.normalized && m.norm == NORM_NFKC) {
                 bool refused = false;

@@ -73,6 +73,9 @@ struct HostModel {
     // NORM_NFC with Lowercase behind it: Sequence[NFC, Replace(Regex "\\s+" -> " "), Lowercase] of the CLIP files, or the same without the
     // Replace (inert in front of the CLIP pre-tokenizer: no \s char ever reaches a pre-token).  tkamd_info reports NORM_NFC_LOWER
     bool nfc_lower = false;
+    // ... WITH the Replace: inert for the pre-tokens, not for the normalized added tokens -- their patterns and the text they are matched
+    // on have every \s run collapsed to one ' ' (k_added_resolve, AddedArgs::ws_fold)
+    bool nfc_ws_fold = false;
     // the mode bits of the NFC core (nfc_core.hpp) this file's normalizer runs it in: 0 for NFC itself
     uint32_t nfc_mode() const { return nfc_lower ? 8u : nfd_mode(); }
 

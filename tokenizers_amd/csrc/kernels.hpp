@@ -155,6 +155,8 @@ struct MetaArgs {
     const uint32_t* lprefix;
     uint32_t byte_level, trim_offsets, pp_add_prefix_space, want_offsets, char_mode, want_words;
     uint32_t trim_matches_only;       // trim_offsets on a model that is not byte-level: only added-token matches are looked at
+    uint32_t trim_token_text;         // ... but behind Unigram without byte_fallback: an unknown run's token IS its text (unigram/model.rs: the piece, not
+                                      // unk_token), whitespace included -- every token's own text is looked at (no vocabulary entry has such an edge: the loader)
     uint32_t snap_chars;              // token edges snap outwards to char boundaries: byte-level tokens, and BPE over characters (its offsets are running
                                       // sums of symbol lengths, which cut chars behind a dropped char or inside byte_fallback's one-byte symbols)
     const uint32_t* char_id;          // BPE over characters WITHOUT an unk_token: chars the vocabulary lacks are dropped and every offset behind them
@@ -185,6 +187,7 @@ struct AddedArgs {
     uint32_t n_first;          // distinct first bytes; the first four of them:
     uint32_t first_byte[4];
     uint32_t skip_special;     // Tokenizer.encode_special_tokens: a special token found in the text is left there as text (added_vocabulary.rs:450-453)
+    uint32_t ws_fold;          // the text is matched as if Replace(Regex "\\s+" -> " ") had run over it (the CLIP normalizer chain): a ' ' of a pattern is a whole \s run
 };
 
 // arguments of k_add_specials, passed by value
@@ -331,6 +334,7 @@ enum : int { CNT_LIST16 = 0, CNT_LIST64 = 1, CNT_LISTL = 2, CNT_LIST32 = 3, CNT_
               CNT_MATCHES = 9, CNT_MATCH_DOCS2 = 10, CNT_CLAIM_GAVE_UP = 11, CNT_MERGE_PROBES = 12, CNT_COUNT = 13 };
 // (CNT_CLAIM_*: in-batch claims -- candidates the lookup looked at, how many were another pre-token's word, workgroups that stopped claiming)
 
+constexpr uint32_t MATCH_WS_FOLD = 0x40000000u;     // ... word 3: matched with AddedArgs::ws_fold -- the token's string holds ONE ' ' per \\s run of its slice
 constexpr uint32_t MATCH_LEN_ORIG = 0x80000000u;    // added-token match list, word 3: the length counts bytes of the ORIGINAL text
 constexpr int TEXT_PAD = 64;        // = TKAMD_TEXT_PAD (include/tokenizers_amd.h): readable bytes past the end of every text buffer
 constexpr int LONG_PT_MAX = 8192;  // symbols per pre-token on the workgroup path (LDS resident); longer ones use the global-scratch kernel

@@ -62,11 +62,55 @@ __device__ __forceinline__ void pair_probe2(const MergeSlot* __restrict__ tab, u
 //   k_apply_match_ids  : that pre-token gets the added token's id.
 // =================================================================================================
 
-// longest pattern starting at text[i] inside [i, end): returns its index or -1
+// byte length of the char at text[i] if it is one of the 25 the regex class \s holds (White_Space), else 0; i < end
+__device__ __forceinline__ uint32_t ws_char_len(const uint8_t* __restrict__ text, int64_t i, int64_t end) {
+    const uint32_t b = text[i];
+    if (b < 0x80u) return ((b >= 9u && b <= 13u) || b == 32u) ? 1u : 0u;
+    if (b == 0xC2u) return (i + 2 <= end && (text[i + 1] == 0x85u || text[i + 1] == 0xA0u)) ? 2u : 0u;
+    if (b < 0xE1u || b > 0xE3u || i + 3 > end) return 0u;
+    const uint32_t c = text[i + 1], d = text[i + 2];
+    if (b == 0xE1u) return (c == 0x9Au && d == 0x80u) ? 3u : 0u;                                    // U+1680
+    if (b == 0xE3u) return (c == 0x80u && d == 0x80u) ? 3u : 0u;                                    // U+3000
+    return ((c == 0x80u && ((d >= 0x80u && d <= 0x8Au) || d == 0xA8u || d == 0xA9u || d == 0xAFu)) || (c == 0x81u && d == 0x9Fu)) ? 3u : 0u;
+}
+
+// longest pattern starting at text[i] inside [i, end): returns its index or -1; *len = the bytes of TEXT it covers.
+// ws_fold (the CLIP chain's Replace(Regex "\s+" -> " ") in front of the match, which no kernel applies to the text): the patterns hold one
+// ' ' per \s run, and the text is read as the reference's normalized string -- a ' ' inside or at the end of a pattern is a WHOLE \s run
+// of the text; the ' ' a pattern opens with is the run's LAST char, where the reference's alignment puts the one ' ' the run became
+// (NormalizedString::replace: every earlier char of the run is removed), so a match's range starts there.
 __device__ __forceinline__ int added_longest(const AddedArgs& a, const uint8_t* __restrict__ text, int64_t i, int64_t end, uint32_t* len) {
     uint32_t b = text[i];
     int best = -1;
-    uint32_t best_len = 0;
+    uint32_t best_len = 0, best_text = 0;
+    if (a.ws_fold) {
+        const uint32_t wl = ws_char_len(text, i, end);
+        if (wl) {
+            if (i + wl < end && ws_char_len(text, i + wl, end)) { *len = 0; return -1; }      // not the last char of its run
+            b = ' ';
+        }
+        for (uint32_t k = a.first[b]; k < a.first[b + 1]; ++k) {
+            const uint32_t o = a.off[k], l = a.off[k + 1] - o;
+            if (l <= best_len) continue;                               // (longest in the normalized string: by the pattern's own length)
+            int64_t p = i + (wl ? wl : 1u);
+            uint32_t j = 1;
+            for (; j < l; ++j) {
+                if (p >= end) break;
+                const uint32_t pb = a.blob[o + j];
+                if (pb == ' ') {
+                    uint32_t r = ws_char_len(text, p, end);
+                    if (!r) break;
+                    do { p += r; r = p < end ? ws_char_len(text, p, end) : 0u; } while (r);
+                } else {
+                    if (text[p] != pb) break;
+                    ++p;
+                }
+            }
+            if (j == l) { best = (int)k; best_len = l; best_text = (uint32_t)(p - i); }
+        }
+        *len = best_text;
+        return best;
+    }
     for (uint32_t k = a.first[b]; k < a.first[b + 1]; ++k) {
         uint32_t o = a.off[k], l = a.off[k + 1] - o;
         if (i + l > end || l <= best_len) continue;
@@ -106,7 +150,8 @@ __global__ __launch_bounds__(256) void k_added_candidates(AddedArgs a, const uin
             for (int j = 0; j < nv; ++j) {
                 const uint32_t b = (x[j >> 2] >> (8 * (j & 3))) & 0xFFu;
                 const unsigned long long set = b < 128u ? (b < 64u ? a.first_set[0] : a.first_set[1]) : (b < 192u ? a.first_set[2] : a.first_set[3]);
-                if ((set >> (b & 63u)) & 1ull) { uint32_t l; if (added_longest(a, text, i0 + j, n_bytes, &l) >= 0) cand |= 1u << j; }
+                // (ws_fold: whether a \s char is the last of its run depends on where its sentence ends, which k_added_resolve knows: every one is a candidate)
+                if ((set >> (b & 63u)) & 1ull) { uint32_t l; if ((a.ws_fold && ws_char_len(text, i0 + j, n_bytes)) || added_longest(a, text, i0 + j, n_bytes, &l) >= 0) cand |= 1u << j; }
             }
         }
     }
@@ -160,8 +205,16 @@ __global__ void k_added_resolve(AddedArgs a, const uint8_t* __restrict__ text, c
                 if ((fl & 8u) && a.skip_special) continue;            // encode_special_tokens: its text stays text (for this pass and the next)
                 if (fl & 1u) {                                        // single_word: \w on either side rejects the match
                     bool ok = true;
-                    if (start > da) {
-                        int64_t p = start - 1;
+                    int64_t left = start;                             // (ws_fold: the char in front of the ' ' a match opens with stands in front of its whole run)
+                    if (a.ws_fold && ws_char_len(text, start, db))
+                        while (left > da) {
+                            int64_t p = left - 1;
+                            while (p > da && (text[p] & 0xC0u) == 0x80u) --p;
+                            if (!ws_char_len(text, p, db)) break;
+                            left = p;
+                        }
+                    if (left > da) {
+                        int64_t p = left - 1;
                         while (p > da && (text[p] & 0xC0u) == 0x80u) --p;
                         uint32_t l2;
                         ok = !(uc_flags(utf8_global(text, p, &l2), uc1, uc2) & UC_RX_W);
@@ -169,9 +222,12 @@ __global__ void k_added_resolve(AddedArgs a, const uint8_t* __restrict__ text, c
                     if (ok && stop < db) { uint32_t l2; ok = !(uc_flags(utf8_global(text, stop, &l2), uc1, uc2) & UC_RX_W); }
                     if (!ok) continue;
                 }
+                // (ws_fold: in front of the match the normalized string holds at most ONE ' ', aligned to its run's last char -- one char is
+                // swallowed --, and none in front of a match that opens with the ' ' of a run)
                 if (fl & 2u) {                                        // lstrip
                     int64_t ns = start;
-                    while (ns > da) {
+                    const bool opens_ws = a.ws_fold && ws_char_len(text, start, db);
+                    while (ns > da && !opens_ws && !(a.ws_fold && ns < start)) {
                         int64_t p = ns - 1;
                         while (p > da && (text[p] & 0xC0u) == 0x80u) --p;
                         uint32_t l2;
@@ -203,7 +259,7 @@ __global__ void k_added_resolve(AddedArgs a, const uint8_t* __restrict__ text, c
                     match_list[4 * mi] = (uint32_t)start;
                     match_list[4 * mi + 1] = (uint32_t)stop;          // end in the masks
                     match_list[4 * mi + 2] = a.id[k];
-                    match_list[4 * mi + 3] = (uint32_t)(stop - start) | len_flag;   // the split's own length (in this text's bytes)
+                    match_list[4 * mi + 3] = (uint32_t)(stop - start) | len_flag | (a.ws_fold ? MATCH_WS_FOLD : 0u);   // the split's own length (in this text's bytes)
                     prev = mi;
                 } else atomicOr(err, ERR_INTERNAL);
                 start_offset = stop;

@@ -427,8 +427,11 @@ __device__ __forceinline__ void meta_one_token(const MetaArgs& a, int64_t p, int
     uint32_t os, oe;
     const uint8_t* ttext = a.x_text;                      // text the trimming below reads, and the token's span in it
     uint32_t tts = ts, tte = te;
+    bool ws_fold = false;                                 // the match's string is its slice with every \s run collapsed (MATCH_WS_FOLD)
     if (is_match) {
-        const uint32_t ml = a.tmp_end[s];
+        uint32_t ml = a.tmp_end[s];
+        ws_fold = (ml & MATCH_WS_FOLD) != 0u;
+        ml &= ~MATCH_WS_FOLD;
         os = a.norig ? a.norig[s] : s - xdoc + odoc;
         if (ml & MATCH_LEN_ORIG) { oe = os + (ml & ~MATCH_LEN_ORIG); ttext = a.text; tts = os; tte = oe; }
         else { tte = s + ml; oe = a.norig ? norig_end(a, tte - 1u) : tte - xdoc + odoc; }
@@ -442,18 +445,31 @@ __device__ __forceinline__ void meta_one_token(const MetaArgs& a, int64_t p, int
     } else { os -= odoc; oe -= odoc; }
     if (a.trim_offsets) {                                 // process_offsets, byte_level.rs:202-234
         uint32_t lead_sp = 0, trail_sp = 0;
-        if (is_match) {
+        if (is_match || a.trim_token_text) {
             // an added token's text is the raw slice: its leading / trailing chars are tested with char::is_whitespace
+            // (trim_token_text: so is the token of a Unigram unknown run, the slice [ts, te) of the text the model read)
             uint32_t q = tts;
-            while (q < tte) { uint32_t l; const uint32_t cp = utf8_global(ttext, q, &l); if (cp != 0x120u && !(uc_flags(cp, a.uc1, a.uc2) & UC_RUST_WS)) break; ++lead_sp; q += l; }
+            bool in_run = false;                                  // (ws_fold: a run of \s chars is one char of the token's string)
+            while (q < tte) {
+                uint32_t l;
+                const uint32_t cp = utf8_global(ttext, q, &l);
+                const bool ws = (uc_flags(cp, a.uc1, a.uc2) & UC_RUST_WS) != 0u;
+                if (cp != 0x120u && !ws) break;
+                if (!(ws_fold && ws && in_run)) ++lead_sp;
+                in_run = ws;
+                q += l;
+            }
             q = tte;
+            in_run = false;
             while (q > tts) {
                 uint32_t r = q - 1;
                 while (r > tts && (ttext[r] & 0xC0u) == 0x80u) --r;
                 uint32_t l;
                 const uint32_t cp = utf8_global(ttext, r, &l);
-                if (cp != 0x120u && !(uc_flags(cp, a.uc1, a.uc2) & UC_RUST_WS)) break;   // (*c == 'Ġ' || c.is_whitespace())
-                ++trail_sp;
+                const bool ws = (uc_flags(cp, a.uc1, a.uc2) & UC_RUST_WS) != 0u;
+                if (cp != 0x120u && !ws) break;   // (*c == 'Ġ' || c.is_whitespace())
+                if (!(ws_fold && ws && in_run)) ++trail_sp;
+                in_run = ws;
                 q = r;
             }
         } else if (!a.trim_matches_only) {
