@@ -336,14 +336,14 @@ typedef struct tkamd_device_text {
     const uint8_t* d_bytes;        /* [n_bytes] valid UTF-8, followed by >= TKAMD_TEXT_PAD zero bytes */
     const int64_t* d_doc_offsets;  /* [n_docs + 1] CSR into d_bytes                                   */
     const int64_t* d_n_bytes;      /* [1]                                                             */
-    int64_t        n_bytes;        /* the same count, known when the call returns                     */
+    int64_t        n_bytes;        /* the same count, known when the call returns (-1: a fused stream step) */
 } tkamd_device_text;
 int tkamd_decode_batch_device(tkamd_tokenizer* tok, const void* d_ids, int64_t n_ids,
                               const int64_t* d_begin, const int64_t* d_end, int64_t n_docs,
                               uint32_t flags, void* hip_stream, tkamd_device_text* out);
 /* A result of the call above copied to host memory on `hip_stream` (the call waits for it): bytes[0 .. text->n_bytes + n_slack) -- n_slack
  * <= TKAMD_TEXT_PAD bytes of the zero slack behind the text --, doc_offsets[0 .. n_docs] and *n_bytes, the count as the device holds it.
- * Any of the three may be NULL.  For bindings that have no HIP runtime of their own to copy with; a consumer on the device reads the
+ * Any of the three may be NULL.  text->n_bytes < 0 (a fused stream step): the count is fetched first, one more wait.  For bindings that have no HIP runtime of their own to copy with; a consumer on the device reads the
  * pointers of tkamd_device_text directly. */
 int tkamd_device_text_read(tkamd_tokenizer* tok, const tkamd_device_text* text, int64_t n_docs, int64_t n_slack, void* hip_stream,
                            uint8_t* bytes, int64_t* doc_offsets, int64_t* n_bytes);
@@ -356,7 +356,7 @@ int tkamd_device_text_read(tkamd_tokenizer* tok, const tkamd_device_text* text, 
  * the window, so no text is stored -- and prefix_index); a step decodes three short ranges of every window with the range decode of
  * tkamd_decode_batch_device (so first- and last-token forms, CTC's dedup, ByteFallback's runs and the lossy UTF-8 repair apply to the
  * WINDOW, as in the reference), compares, emits and drains.
- *   new  : flags = TKAMD_SKIP_SPECIAL or 0, kept for every step.  window = the most ids one stream's window may hold (0: 32; at least 2;
+ *   new  : flags = TKAMD_SKIP_SPECIAL or 0, kept for every step, and TKAMD_STREAM_FUSED (below).  window = the most ids one stream's window may hold (0: 32; at least 2;
  *          the reference's grows without bound -- it holds the ids since the last chunk, 1 - 3 on ordinary text).  n_streams >= 0.
  *          A host-only handle gets TKAMD_ERR_DEVICE, a decoder outside the decode path TKAMD_ERR_UNSUPPORTED with decode_batch's message;
  *          a multi-device handle streams on devices[0].  The object must be freed before its tokenizer.
@@ -380,8 +380,28 @@ int tkamd_device_text_read(tkamd_tokenizer* tok, const tkamd_device_text* text, 
  *          copied to host memory in one wait; any of the three may be NULL.
  *   peek : (tests, debugging) the state of ONE stream on the host, after a wait for the whole device: up to cap ids of its window,
  *          their count *n, and the reference's prefix as ids (*pe: prefix = decode of the first *pe ids) and prefix_index (*pi).
- * One call at a time per object (calls are serialised inside); the caller orders its streams as for any stream-ordered API. */
+ *   info : whether the object is fused (below), and what it allocated for that: the bytes its chunk buffer holds and its string scratch
+ *          (both 0 for an object that is not fused, whose buffers follow the counts of each step).  Any pointer may be NULL.
+ * One call at a time per object (calls are serialised inside); the caller orders its streams as for any stream-ordered API.
+ *
+ * A FUSED object (new with TKAMD_STREAM_FUSED) steps WITHOUT a host wait: push, the three strings of every window and the decision run in
+ * one kernel with a lane per stream (over the very per-token device functions of the range decode), followed by the scan of the chunk
+ * lengths, the copy and the zero slack -- 6 kernel launches, the same for every decoder and whatever the windows hold.  Everything a
+ * step touches is allocated by `new`, sized by a bound instead of counts: a decoded window is at most window x max(L, 3) bytes, L = the
+ * longest string one id decodes to in either position form (for ByteLevel: repaired by from_utf8_lossy on its own, which bounds what it
+ * contributes in any company) and 3 = one U+FFFD per byte token of a run that is not UTF-8; 3 such strings a stream (4 for ByteLevel) and
+ * a chunk buffer of n_streams x window x max(L, 3) bytes.  `new` fails with TKAMD_ERR_INVALID naming n_streams, window and L when strings
+ * and chunks together exceed 1 GiB.  A step of a fused object only enqueues: no synchronisation, no copy to the host, no allocation; it
+ * returns text->d_bytes / d_doc_offsets / d_n_bytes as above and text->n_bytes = -1 -- the host does not hold the count; it is
+ * *text->d_n_bytes (and d_doc_offsets[n_streams]) once the stream has drained.  Status values and every state transition are those
+ * of an object that is not fused.  Such a step can be captured into a HIP graph and replayed: step once outside the capture, keep d_ids
+ * (and d_active) at fixed addresses and write the new ids there before each replay.  TKAMD_STREAM_IDS_HOST is allowed on a fused object
+ * but stages through pinned host memory of the object and may wait for the previous staging: not a form to capture.  read,
+ * tkamd_device_text_read and the Python helpers fetch the count from the device first when text->n_bytes < 0 (every time: a replayed graph
+ * refills the buffers without a call); a bytes buffer handed to them must then hold the chunk capacity of `info` + n_slack, or be sized after
+ * asking tkamd_device_text_read for *n_bytes alone.  reset, seed and peek work on both kinds of object (one state layout). */
 #define TKAMD_STREAM_IDS_HOST 4u           /* tkamd_decode_stream_step: d_ids / d_active are host memory */
+#define TKAMD_STREAM_FUSED 8u              /* tkamd_decode_stream_new: a step only enqueues (one fused kernel, buffers sized by bounds) */
 typedef struct tkamd_decode_stream tkamd_decode_stream;
 int  tkamd_decode_stream_new(tkamd_tokenizer* tok, int64_t n_streams, int32_t window, uint32_t flags, tkamd_decode_stream** out);
 void tkamd_decode_stream_free(tkamd_decode_stream* s);
@@ -391,6 +411,7 @@ int  tkamd_decode_stream_step(tkamd_decode_stream* s, const void* d_ids, const u
                               tkamd_device_text* text, const uint8_t** d_status);
 int  tkamd_decode_stream_read(tkamd_decode_stream* s, int64_t n_slack, void* hip_stream, uint8_t* bytes, int64_t* doc_offsets, uint8_t* status);
 int  tkamd_decode_stream_peek(tkamd_decode_stream* s, int64_t which_one, uint32_t* ids, int64_t cap, int64_t* n, int64_t* pe, int64_t* pi);
+int  tkamd_decode_stream_info(tkamd_decode_stream* s, int64_t* fused, int64_t* chunk_capacity, int64_t* scratch_bytes);
 
 /* String::from_utf8_lossy of ONE sequence -- bytes[0 .. n) -- by the host run of the very per-byte decision the kernels make
  * (csrc/utf8_lossy_core.hpp): out[0 .. *n_out).  Takes no handle and needs no device.  cap: what out holds; *n_out is set even when

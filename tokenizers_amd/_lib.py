@@ -28,6 +28,7 @@ NO_SPECULATION = 64      # device entry, results consumed stream-ordered without
 SKIP_SPECIAL = 1          # tkamd_decode_batch flag
 DECODE_IDS_I64 = 2        # tkamd_decode_batch_device: the ids are int64
 STREAM_IDS_HOST = 4       # tkamd_decode_stream_step: the ids and the mask are host arrays
+STREAM_FUSED = 8          # tkamd_decode_stream_new: a step only enqueues (one fused kernel, buffers sized by bounds)
 TEXT_PAD = 64
 MAX_STAGES = 24
 
@@ -45,7 +46,7 @@ SYMBOLS = [
     "tkamd_pinned_alloc", "tkamd_pinned_free", "tkamd_encode_batch_paced",
     "tkamd_decode_batch_device", "tkamd_device_text_read", "tkamd_probe_utf8_lossy",
     "tkamd_decode_stream_new", "tkamd_decode_stream_free", "tkamd_decode_stream_reset", "tkamd_decode_stream_seed", "tkamd_decode_stream_step",
-    "tkamd_decode_stream_read", "tkamd_decode_stream_peek",
+    "tkamd_decode_stream_read", "tkamd_decode_stream_peek", "tkamd_decode_stream_info",
 ]
 COLLECT_HOST, COLLECT_ROOT_P2P, COLLECT_ROOT_RCCL = 0, 1, 2
 
@@ -191,6 +192,8 @@ def load() -> C.CDLL:
     lib.tkamd_decode_stream_read.restype = i32
     lib.tkamd_decode_stream_peek.argtypes = [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     lib.tkamd_decode_stream_peek.restype = i32
+    lib.tkamd_decode_stream_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    lib.tkamd_decode_stream_info.restype = i32
     lib.tkamd_probe_utf8_lossy.argtypes = [vp, i64, vp, i64, C.POINTER(i64)]
     lib.tkamd_probe_utf8_lossy.restype = i32
     lib.tkamd_decode_token.argtypes = [vp, u32, i32, vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

@@ -172,14 +172,20 @@ int tkamd_decode_batch_device(tkamd_tokenizer* t, const void* d_ids, int64_t n_e
 // a result of the call above copied to host memory: what a binding without a HIP runtime of its own (ctypes) reads it with
 int tkamd_device_text_read(tkamd_tokenizer* t, const tkamd_device_text* text, int64_t n_docs, int64_t n_slack, void* hip_stream, uint8_t* bytes,
                            int64_t* doc_offsets, int64_t* n_bytes) {
-    if (!t || !text || n_docs < 0 || n_slack < 0 || n_slack > TKAMD_TEXT_PAD || !text->d_bytes || !text->d_doc_offsets || !text->d_n_bytes || text->n_bytes < 0)
+    if (!t || !text || n_docs < 0 || n_slack < 0 || n_slack > TKAMD_TEXT_PAD || !text->d_bytes || !text->d_doc_offsets || !text->d_n_bytes)
         return set_error(TKAMD_ERR_INVALID, "bad argument");
     if (t->device < 0) return set_error(TKAMD_ERR_DEVICE, "host-only tokenizer handle: no HIP device bound (there is no CPU fallback)");
     return guarded([&]() -> int {
         check_not_forked();
         hipStream_t st = (hipStream_t)hip_stream;
         HIP_CHECK(hipSetDevice(t->device));
-        if (bytes && text->n_bytes + n_slack > 0) HIP_CHECK(hipMemcpyAsync(bytes, text->d_bytes, (size_t)(text->n_bytes + n_slack), hipMemcpyDeviceToHost, st));
+        int64_t have = text->n_bytes;
+        if (have < 0 && bytes) {                               // (a fused stream step's text: the count is on the device alone; one more wait)
+            HIP_CHECK(hipMemcpyAsync(&have, text->d_n_bytes, 8, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            if (have < 0) throw std::runtime_error("device text: a negative byte count");
+        }
+        if (bytes && have + n_slack > 0) HIP_CHECK(hipMemcpyAsync(bytes, text->d_bytes, (size_t)(have + n_slack), hipMemcpyDeviceToHost, st));
         if (doc_offsets) HIP_CHECK(hipMemcpyAsync(doc_offsets, text->d_doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, st));
         if (n_bytes) HIP_CHECK(hipMemcpyAsync(n_bytes, text->d_n_bytes, 8, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));

@@ -518,6 +518,19 @@ constexpr int DS_RANGES = 3;     // ranges of its window a stream has decoded pe
 void launch_ds_push(hipStream_t st, const DsState& z, const void* ids, bool wide, const uint8_t* active, int64_t* begin, int64_t* end, uint8_t* status);
 void launch_ds_emit(hipStream_t st, const DsState& z, uint8_t* status, const int64_t* doc_off, const uint8_t* text, uint32_t* len, uint32_t* bsum, uint32_t* pos,
                     int64_t* total, uint8_t* out, int64_t* out_off);
+// the fused step (k_ds_step_fused): push, the three strings of every window and the decision in ONE kernel, a lane a stream, in front of the
+// scan chain, k_ds_copy and the zero pad -- no count goes to the host.  The decoder as launch_decode is given it, and the scratch.
+struct DsFused {
+    const void* entry;           // dec_entry (uint4 per id)
+    const uint8_t* blob;
+    uint32_t n_ids, skip_special;
+    uint32_t position_forms, from_end, byte_runs, dedup, lossy;      // HostModel dec_position_dependent / dec_special_is_last / dec_has_bytes / dec_dedup; ByteLevel
+    uint8_t* scratch;            // [n_streams x (lossy ? 4 : 3) x cap]: a stream's decoded strings
+    uint8_t* flag;               // [n_streams x window]: a stream's token masks
+    int64_t cap;                 // bytes one decoded string may take: >= window x the longest contribution of an id
+};
+void launch_ds_step_fused(hipStream_t st, const DsState& z, const DsFused& f, const void* ids, bool wide, const uint8_t* active, uint8_t* status, uint32_t* len,
+                          int64_t* str_end, uint32_t* bsum, uint32_t* pos, int64_t* total, uint8_t* out, int64_t* out_off);
 void launch_ds_reset(hipStream_t st, const DsState& z, const int64_t* which, int64_t n_which);      // which == nullptr: every stream
 void launch_ds_seed(hipStream_t st, const DsState& z, int64_t stream, const uint32_t* ids, uint32_t n);
 int prepare_long_kernel();

@@ -13,30 +13,34 @@
 // plain concatenation) and ByteFallback (byte_fallback.rs:27-67): a <0xXX> token is its byte, and a maximal run of such tokens that
 // is not valid UTF-8 as a whole becomes one U+FFFD per byte -- k_decode_byte_runs walks every sequence once and marks those.
 // =================================================================================================
+// ---- the per-token rules, stated ONCE: the kernels of launch_decode (a lane a sequence for the masks, a lane a token for lengths and
+// bytes) and the fused stream step (kernels/decode_stream.hip: a lane walks its own window) are written over these and nothing else ----
 __device__ __forceinline__ bool dec_kept(uint32_t lenflags, uint32_t skip_special) {
     return !(lenflags & DEC_ABSENT) && !(skip_special && (lenflags & DEC_SPECIAL));
 }
-__global__ __launch_bounds__(256) void k_decode_first(const uint32_t* __restrict__ ids, const int64_t* __restrict__ tok_off, int64_t n_docs,
-                                                      const uint4* __restrict__ entry, uint32_t n_ids, uint32_t skip_special,
-                                                      uint32_t* __restrict__ firstmask, uint32_t from_end) {
-    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (d >= n_docs) return;
-    if (from_end) {                                            // (BPEDecoder: the last kept token)
-        for (int64_t t = tok_off[d + 1] - 1, b = tok_off[d]; t >= b; --t) {
-            const uint32_t id = ids[t];
-            if (id < n_ids && dec_kept(entry[id].y, skip_special)) { atomicOr(&firstmask[t >> 5], 1u << (t & 31)); break; }
-        }
-        return;
+// is `id` a token the decoder sees (the id bound, then dec_kept)?  Its entry -> e.
+__device__ __forceinline__ bool dec_kept_id(const uint4* __restrict__ entry, uint32_t n_ids, uint32_t skip_special, uint32_t id, uint4& e) {
+    if (id >= n_ids) return false;                             // (no such token: dropped before the decoder sees the sequence)
+    e = entry[id];
+    return dec_kept(e.y, skip_special);
+}
+// the token of ids[b, end) with the position form of its own: the first kept one, or -- from_end (BPEDecoder) -- the last kept one; -1: none
+__device__ __forceinline__ int64_t dec_form_token(const uint32_t* __restrict__ ids, int64_t b, int64_t end, const uint4* __restrict__ entry, uint32_t n_ids,
+                                                  uint32_t skip_special, uint32_t from_end) {
+    uint4 e;
+    if (from_end) {
+        for (int64_t t = end - 1; t >= b; --t)
+            if (dec_kept_id(entry, n_ids, skip_special, ids[t], e)) return t;
+        return -1;
     }
-    for (int64_t t = tok_off[d], e = tok_off[d + 1]; t < e; ++t) {
-        const uint32_t id = ids[t];
-        if (id < n_ids && dec_kept(entry[id].y, skip_special)) { atomicOr(&firstmask[t >> 5], 1u << (t & 31)); break; }
-    }
+    for (int64_t t = b; t < end; ++t)
+        if (dec_kept_id(entry, n_ids, skip_special, ids[t], e)) return t;
+    return -1;
 }
 // ByteFallback::decode_chain (decoders/byte_fallback.rs:27-67): the KEPT tokens of a sequence in order; a maximal run of <0xXX> tokens is
-// String::from_utf8 of its bytes, or -- if that fails -- one U+FFFD per byte.  One lane per sequence walks it once: a run is validated
+// String::from_utf8 of its bytes, or -- if that fails -- one U+FFFD per byte.  A sequence is walked once: a run is validated
 // as it goes (the UTF-8 automaton of the standard library: no overlong forms, no surrogates, nothing above U+10FFFF) and, if it fails,
-// walked again to mark its tokens in badmask.
+// walked again to mark its tokens: mark(t) for every byte token of a failed run.
 __device__ __forceinline__ bool utf8_step(uint32_t b, uint32_t& need, uint32_t& lo, uint32_t& hi) {      // false: invalid here
     if (need == 0u) {
         lo = 0x80u; hi = 0xBFu;
@@ -55,28 +59,23 @@ __device__ __forceinline__ bool utf8_step(uint32_t b, uint32_t& need, uint32_t& 
     lo = 0x80u; hi = 0xBFu;
     return true;
 }
-__global__ __launch_bounds__(256) void k_decode_byte_runs(const uint32_t* __restrict__ ids, const int64_t* __restrict__ tok_off, int64_t n_docs,
-                                                          const uint4* __restrict__ entry, uint32_t n_ids, uint32_t skip_special,
-                                                          uint32_t* __restrict__ badmask) {
-    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (d >= n_docs) return;
-    const int64_t end = tok_off[d + 1];
+template <class Mark>
+__device__ __forceinline__ void dec_bad_byte_runs(const uint32_t* __restrict__ ids, int64_t b, int64_t end, const uint4* __restrict__ entry, uint32_t n_ids,
+                                                  uint32_t skip_special, Mark mark) {
     int64_t run0 = -1;                                         // first token of the run under way
     uint32_t need = 0u, lo = 0x80u, hi = 0xBFu;
     bool ok = true;
     auto close_run = [&](int64_t upto) {                       // the run [run0, upto) is over
         if (run0 >= 0 && (!ok || need != 0u))
             for (int64_t t = run0; t < upto; ++t) {
-                const uint32_t id = ids[t];
-                if (id < n_ids) { const uint32_t y = entry[id].y; if (dec_kept(y, skip_special) && (y & DEC_BYTE)) atomicOr(&badmask[t >> 5], 1u << (t & 31)); }
+                uint4 e;
+                if (dec_kept_id(entry, n_ids, skip_special, ids[t], e) && (e.y & DEC_BYTE)) mark(t);
             }
         run0 = -1; need = 0u; ok = true;
     };
-    for (int64_t t = tok_off[d]; t < end; ++t) {
-        const uint32_t id = ids[t];
-        if (id >= n_ids) continue;                             // (no such token: dropped before the decoder sees the sequence)
-        const uint4 e = entry[id];
-        if (!dec_kept(e.y, skip_special)) continue;
+    for (int64_t t = b; t < end; ++t) {
+        uint4 e;
+        if (!dec_kept_id(entry, n_ids, skip_special, ids[t], e)) continue;
         if (e.y & DEC_BYTE) {
             if (run0 < 0) run0 = t;
             if (ok) ok = utf8_step(e.x & 0xFFu, need, lo, hi);
@@ -84,36 +83,70 @@ __global__ __launch_bounds__(256) void k_decode_byte_runs(const uint32_t* __rest
     }
     close_run(end);
 }
-// CTC (decoders/ctc.rs:47-48: `.dedup()` over the kept tokens): a kept token whose id equals the kept id in front of it is marked and
-// contributes nothing.  One lane per sequence.
+// CTC (decoders/ctc.rs:47-48: `.dedup()` over the kept tokens): a kept token whose id equals the kept id in front of it contributes
+// nothing: mark(t) for every such token.
+template <class Mark>
+__device__ __forceinline__ void dec_dups(const uint32_t* __restrict__ ids, int64_t b, int64_t end, const uint4* __restrict__ entry, uint32_t n_ids,
+                                         uint32_t skip_special, Mark mark) {
+    uint32_t prev = 0xFFFFFFFFu;
+    for (int64_t t = b; t < end; ++t) {
+        const uint32_t id = ids[t];
+        uint4 e;
+        if (!dec_kept_id(entry, n_ids, skip_special, id, e)) continue;
+        if (id == prev) mark(t);
+        prev = id;
+    }
+}
+// what a token that is kept and no duplicate contributes.  A byte token: U+FFFD -- three bytes -- if its run is not UTF-8, else its byte
+// (as the first kept token under a leading Strip of that very byte the first-position form has length 0); any other: its string in
+// the form of its position.
+__device__ __forceinline__ uint32_t dec_piece_len(const uint4& e, bool first, bool bad) {
+    if ((e.y & DEC_BYTE) && bad) return 3u;
+    return first ? (e.y & DEC_LEN_MASK) : e.w;
+}
+__device__ __forceinline__ void dec_piece_write(const uint4& e, bool first, bool bad, const uint8_t* __restrict__ blob, uint8_t* __restrict__ dst) {
+    if (e.y & DEC_BYTE) {
+        if (bad) { dst[0] = 0xEFu; dst[1] = 0xBFu; dst[2] = 0xBDu; }
+        else if ((first ? (e.y & DEC_LEN_MASK) : e.w) != 0u) dst[0] = (uint8_t)e.x;
+        return;
+    }
+    const uint32_t off = first ? e.x : e.z, l = first ? (e.y & DEC_LEN_MASK) : e.w;
+    const uint8_t* src = blob + off;
+    for (uint32_t i = 0; i < l; ++i) dst[i] = src[i];
+}
+__device__ __forceinline__ bool dec_mask_bit(const uint32_t* __restrict__ mask, int64_t t) { return mask && ((mask[t >> 5] >> (t & 31)) & 1u); }
+
+__global__ __launch_bounds__(256) void k_decode_first(const uint32_t* __restrict__ ids, const int64_t* __restrict__ tok_off, int64_t n_docs,
+                                                      const uint4* __restrict__ entry, uint32_t n_ids, uint32_t skip_special,
+                                                      uint32_t* __restrict__ firstmask, uint32_t from_end) {
+    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (d >= n_docs) return;
+    const int64_t t = dec_form_token(ids, tok_off[d], tok_off[d + 1], entry, n_ids, skip_special, from_end);
+    if (t >= 0) atomicOr(&firstmask[t >> 5], 1u << (t & 31));
+}
+// one lane per sequence
+__global__ __launch_bounds__(256) void k_decode_byte_runs(const uint32_t* __restrict__ ids, const int64_t* __restrict__ tok_off, int64_t n_docs,
+                                                          const uint4* __restrict__ entry, uint32_t n_ids, uint32_t skip_special,
+                                                          uint32_t* __restrict__ badmask) {
+    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (d >= n_docs) return;
+    dec_bad_byte_runs(ids, tok_off[d], tok_off[d + 1], entry, n_ids, skip_special, [&](int64_t t) { atomicOr(&badmask[t >> 5], 1u << (t & 31)); });
+}
+// one lane per sequence
 __global__ __launch_bounds__(256) void k_decode_dups(const uint32_t* __restrict__ ids, const int64_t* __restrict__ tok_off, int64_t n_docs,
                                                      const uint4* __restrict__ entry, uint32_t n_ids, uint32_t skip_special, uint32_t* __restrict__ dupmask) {
     const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (d >= n_docs) return;
-    uint32_t prev = 0xFFFFFFFFu;
-    for (int64_t t = tok_off[d], e = tok_off[d + 1]; t < e; ++t) {
-        const uint32_t id = ids[t];
-        if (id >= n_ids || !dec_kept(entry[id].y, skip_special)) continue;
-        if (id == prev) atomicOr(&dupmask[t >> 5], 1u << (t & 31));
-        prev = id;
-    }
+    dec_dups(ids, tok_off[d], tok_off[d + 1], entry, n_ids, skip_special, [&](int64_t t) { atomicOr(&dupmask[t >> 5], 1u << (t & 31)); });
 }
 __global__ __launch_bounds__(256) void k_decode_len(const uint32_t* __restrict__ ids, int64_t n_tok, const uint4* __restrict__ entry, uint32_t n_ids,
                                                     uint32_t skip_special, const uint32_t* __restrict__ firstmask, const uint32_t* __restrict__ badmask,
                                                     const uint32_t* __restrict__ dupmask, uint32_t* __restrict__ len) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= n_tok) return;
-    const uint32_t id = ids[t];
+    uint4 e;
     uint32_t l = 0;
-    if (id < n_ids && !(dupmask && ((dupmask[t >> 5] >> (t & 31)) & 1u))) {
-        const uint4 e = entry[id];
-        if (dec_kept(e.y, skip_special)) {
-            // (a byte token: U+FFFD -- three bytes -- if its run is not UTF-8, else its byte; as the first kept token under a leading
-            // Strip of that very byte the first-position form has length 0)
-            if ((e.y & DEC_BYTE) && badmask && ((badmask[t >> 5] >> (t & 31)) & 1u)) l = 3u;
-            else l = (firstmask && ((firstmask[t >> 5] >> (t & 31)) & 1u)) ? (e.y & DEC_LEN_MASK) : e.w;
-        }
-    }
+    if (dec_kept_id(entry, n_ids, skip_special, ids[t], e) && !dec_mask_bit(dupmask, t)) l = dec_piece_len(e, dec_mask_bit(firstmask, t), dec_mask_bit(badmask, t));
     len[t] = l;
 }
 __global__ __launch_bounds__(256) void k_decode_doc_off(const int64_t* __restrict__ tok_off, int64_t n_docs, const uint32_t* __restrict__ pos,
@@ -129,21 +162,55 @@ __global__ __launch_bounds__(256) void k_decode_copy(const uint32_t* __restrict_
                                                      uint8_t* __restrict__ out) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= n_tok) return;
-    const uint32_t id = ids[t];
-    if (id >= n_ids || (dupmask && ((dupmask[t >> 5] >> (t & 31)) & 1u))) return;
-    const uint4 e = entry[id];
-    if (!dec_kept(e.y, skip_special)) return;
-    const bool first = firstmask && ((firstmask[t >> 5] >> (t & 31)) & 1u);
-    if (e.y & DEC_BYTE) {
-        uint8_t* const dst = out + pos[t];
-        if (badmask && ((badmask[t >> 5] >> (t & 31)) & 1u)) { dst[0] = 0xEFu; dst[1] = 0xBFu; dst[2] = 0xBDu; }
-        else if ((first ? (e.y & DEC_LEN_MASK) : e.w) != 0u) dst[0] = (uint8_t)e.x;
-        return;
+    uint4 e;
+    if (!dec_kept_id(entry, n_ids, skip_special, ids[t], e) || dec_mask_bit(dupmask, t)) return;
+    dec_piece_write(e, dec_mask_bit(firstmask, t), dec_mask_bit(badmask, t), blob, out + pos[t]);
+}
+// ONE lane decodes ONE short sequence ids[0, k) into dst (the fused stream step: a window is a few ids): the passes of launch_decode in
+// their order -- the position form, the byte runs, the dedup, then lengths and bytes token by token -- with the three masks as bits of
+// flag[0, k), a byte a token in the lane's own scratch.  Returns the bytes written: at most k x the longest per-id string (3 for a
+// byte token of a failed run).
+struct DecSeqView {
+    const uint4* entry;
+    const uint8_t* blob;
+    uint32_t n_ids, skip_special;
+    uint32_t position_forms, from_end, byte_runs, dedup;       // which masks launch_decode would be given (HostModel dec_*)
+};
+constexpr uint8_t DEC_F_FORM = 1, DEC_F_BAD = 2, DEC_F_DUP = 4;
+__device__ __forceinline__ uint32_t dec_lane_sequence(const DecSeqView& v, const uint32_t* __restrict__ ids, uint32_t k, uint8_t* __restrict__ flag,
+                                                      uint8_t* __restrict__ dst) {
+    for (uint32_t t = 0; t < k; ++t) flag[t] = 0;
+    if (v.position_forms) {
+        const int64_t t = dec_form_token(ids, 0, (int64_t)k, v.entry, v.n_ids, v.skip_special, v.from_end);
+        if (t >= 0) flag[t] |= DEC_F_FORM;
     }
-    const uint32_t off = first ? e.x : e.z, l = first ? (e.y & DEC_LEN_MASK) : e.w;
-    const uint8_t* src = blob + off;
-    uint8_t* dst = out + pos[t];
-    for (uint32_t i = 0; i < l; ++i) dst[i] = src[i];
+    if (v.byte_runs) dec_bad_byte_runs(ids, 0, (int64_t)k, v.entry, v.n_ids, v.skip_special, [&](int64_t t) { flag[t] |= DEC_F_BAD; });
+    if (v.dedup) dec_dups(ids, 0, (int64_t)k, v.entry, v.n_ids, v.skip_special, [&](int64_t t) { flag[t] |= DEC_F_DUP; });
+    uint32_t at = 0u;
+    for (uint32_t t = 0; t < k; ++t) {
+        uint4 e;
+        const uint8_t f = flag[t];
+        if (!dec_kept_id(v.entry, v.n_ids, v.skip_special, ids[t], e) || (f & DEC_F_DUP)) continue;
+        dec_piece_write(e, (f & DEC_F_FORM) != 0, (f & DEC_F_BAD) != 0, v.blob, dst + at);
+        at += dec_piece_len(e, (f & DEC_F_FORM) != 0, (f & DEC_F_BAD) != 0);
+    }
+    return at;
+}
+// what a byte that contributes l bytes (utf8_lossy_len) leaves at dst: itself, U+FFFD, or nothing
+__device__ __forceinline__ void lossy_put(uint32_t l, uint8_t b, uint8_t* __restrict__ dst) {
+    if (l == 1u) dst[0] = b;
+    else if (l == 3u) { dst[0] = 0xEFu; dst[1] = 0xBFu; dst[2] = 0xBDu; }
+}
+// String::from_utf8_lossy of ONE sequence src[0, n) by one lane, the sequence's own bounds as utf8_lossy_len's: dst gets the repaired
+// text, at most 3 bytes a source byte.  Returns its length.
+__device__ __forceinline__ uint32_t lossy_lane_sequence(const uint8_t* __restrict__ src, uint32_t n, uint8_t* __restrict__ dst) {
+    uint32_t at = 0u;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t l = utf8_lossy_len(src, (int64_t)i, 0, (int64_t)n);
+        lossy_put(l, src[i], dst + at);
+        at += l;
+    }
+    return at;
 }
 void launch_decode(hipStream_t st, const uint32_t* ids, const int64_t* tok_off, int64_t n_docs, int64_t n_tok, const void* entry, uint32_t n_ids,
                    const uint8_t* blob, uint32_t skip_special, uint32_t* firstmask, uint32_t* len, uint32_t* bsum, uint32_t* pos, int64_t* total,
@@ -313,10 +380,7 @@ __global__ __launch_bounds__(256) void k_lossy_scatter(const uint8_t* __restrict
                                                        uint8_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const uint32_t l = len[i];
-    uint8_t* const dst = out + pos[i];
-    if (l == 1u) dst[0] = text[i];
-    else if (l == 3u) { dst[0] = 0xEFu; dst[1] = 0xBFu; dst[2] = 0xBDu; }
+    lossy_put(len[i], text[i], out + pos[i]);
 }
 // the document CSR follows its text: in place, a lane an entry
 __global__ __launch_bounds__(256) void k_lossy_doc_off(int64_t* __restrict__ doc_off, int64_t n_docs, const uint32_t* __restrict__ pos, int64_t n,

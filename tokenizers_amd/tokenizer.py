@@ -460,7 +460,9 @@ class DeviceBatch:
 class DeviceText:
     """Result of :meth:`Tokenizer.decode_batch_device` / :meth:`Tokenizer.decode_tensor`: the decoded text in HBM -- valid UTF-8, one
     buffer + int64 CSR with ``TEXT_PAD`` zero bytes behind it, what :meth:`Tokenizer.encode_batch_device` takes.  Raw pointers into the
-    handle's workspace: valid until the next decode call on the same tokenizer and stream."""
+    handle's workspace: valid until the next decode call on the same tokenizer and stream.  ``n_bytes`` is -1 for the text of a fused
+    :class:`DecodeStreams` step, whose count the host does not hold: :meth:`n_bytes_device` and every method that needs the count
+    fetch it from the device then (a wait for the stream)."""
 
     def __init__(self, tok: "Tokenizer", res: _lib.DeviceText, n_docs: int, stream: int):
         self._tok, self._res, self.n_docs, self._stream = tok, res, n_docs, stream
@@ -470,9 +472,23 @@ class DeviceText:
 
     _tensor = DeviceBatch._tensor
 
+    def _count(self) -> int:
+        return self.n_bytes if self.n_bytes >= 0 else self.n_bytes_device()     # (asked anew every time: a replayed graph refills this text)
+
+    def _sized(self) -> "_lib.DeviceText":
+        """the native result with the count filled in"""
+        if self.n_bytes >= 0:
+            return self._res
+        return _lib.DeviceText(self._res.d_bytes, self._res.d_doc_offsets, self._res.d_n_bytes, self._count())
+
     def bytes_tensor(self):
-        """uint8 view of the HBM-resident text."""
-        return self._tensor(self.bytes_ptr, (max(self.n_bytes, 1),), "|u1")[: self.n_bytes]
+        """uint8 view of the HBM-resident text (a fused stream step's text: sized by the count fetched from the device)."""
+        n = self._count()
+        return self._tensor(self.bytes_ptr, (max(n, 1),), "|u1")[:n]
+
+    def n_bytes_tensor(self):
+        """The byte count as a one-element int64 tensor in HBM (valid once the stream has drained): what a consumer on the device reads."""
+        return self._tensor(self._res.d_n_bytes, (1,), "<i8")
 
     def doc_offsets_tensor(self):
         return self._tensor(self.doc_offsets_ptr, (self.n_docs + 1,), "<i8")
@@ -480,12 +496,14 @@ class DeviceText:
     def to_host(self, slack: int = 0) -> tuple[np.ndarray, np.ndarray]:
         """(uint8 bytes[n_bytes + slack], int64 doc_offsets[n_docs + 1]) in host memory: one copy down on the call's stream
         (``tkamd_device_text_read``); ``slack`` <= TEXT_PAD bytes of the zero slack behind the text come along."""
-        raw, off = np.empty(self.n_bytes + slack, dtype=np.uint8), np.empty(self.n_docs + 1, dtype=np.int64)
-        _lib.check(self._tok._lib.tkamd_device_text_read(self._tok._h, C.byref(self._res), self.n_docs, slack, self._stream, raw.ctypes.data, off.ctypes.data, None))
+        res = self._sized()
+        raw, off = np.empty(res.n_bytes + slack, dtype=np.uint8), np.empty(self.n_docs + 1, dtype=np.int64)
+        _lib.check(self._tok._lib.tkamd_device_text_read(self._tok._h, C.byref(res), self.n_docs, slack, self._stream, raw.ctypes.data, off.ctypes.data, None))
         return raw, off
 
     def n_bytes_device(self) -> int:
-        """The byte count as the device holds it (``d_n_bytes``: what a consumer on the device reads); equals ``n_bytes``."""
+        """The byte count as the device holds it (``d_n_bytes``: what a consumer on the device reads); equals ``n_bytes`` where the
+        host holds one."""
         n = C.c_int64(-1)
         _lib.check(self._tok._lib.tkamd_device_text_read(self._tok._h, C.byref(self._res), self.n_docs, 0, self._stream, None, None, C.byref(n)))
         return n.value
@@ -501,14 +519,23 @@ class DecodeStreams:
     """``tokenizers.decoders.DecodeStream`` for ``n_streams`` running sequences at once (:meth:`Tokenizer.decode_stream`): one new id
     per stream and step in, the text that just became printable out -- what ``n_streams`` DecodeStreams of the reference return, with
     the windows, the decode and the comparison on the device (``tkamd_decode_stream_*``).  It belongs to the native handle it was made
-    from: make it after ``add_tokens`` / ``enable_truncation`` and their like, which replace that handle."""
+    from: make it after ``add_tokens`` / ``enable_truncation`` and their like, which replace that handle.
 
-    def __init__(self, tok: "Tokenizer", n_streams: int, skip_special_tokens: bool = False, window: int = 32):
+    ``fused``: a step only enqueues -- one kernel with a lane per stream in front of the scan and the copy, every buffer allocated here
+    and sized by a bound (``chunk_capacity`` and ``scratch_bytes`` say how much), no host wait -- and its :class:`DeviceText` has
+    ``n_bytes == -1``.  A :meth:`step_tensor` of a fused object can be captured into a ``torch.cuda.CUDAGraph`` behind one warm-up step,
+    with static ``ids`` / ``active`` tensors that each replay finds refilled; the host-ids form (:meth:`step`) is not for capture."""
+
+    def __init__(self, tok: "Tokenizer", n_streams: int, skip_special_tokens: bool = False, window: int = 32, fused: bool = False):
         self._tok, self._lib, self.n_streams, self.window = tok, tok._lib, int(n_streams), int(window) or 32
         self.skip_special_tokens = bool(skip_special_tokens)
         h = C.c_void_p()
-        _lib.check(self._lib.tkamd_decode_stream_new(tok._h, self.n_streams, int(window), _lib.SKIP_SPECIAL if skip_special_tokens else 0, C.byref(h)))
+        flags = (_lib.SKIP_SPECIAL if skip_special_tokens else 0) | (_lib.STREAM_FUSED if fused else 0)
+        _lib.check(self._lib.tkamd_decode_stream_new(tok._h, self.n_streams, int(window), flags, C.byref(h)))
         self._h = h
+        f, cc, sb = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.tkamd_decode_stream_info(h, C.byref(f), C.byref(cc), C.byref(sb)))
+        self.fused, self.chunk_capacity, self.scratch_bytes = bool(f.value), cc.value, sb.value
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -530,14 +557,23 @@ class DecodeStreams:
         return DeviceText(self._tok, res, self.n_streams, stream), status.value or 0
 
     def read(self, text: DeviceText, slack: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """(bytes, doc_offsets, status) of the last step in host memory: one copy down (``tkamd_decode_stream_read``)"""
-        raw, off, status = np.empty(text.n_bytes + slack, dtype=np.uint8), np.empty(self.n_streams + 1, dtype=np.int64), np.empty(self.n_streams, dtype=np.uint8)
+        """(bytes, doc_offsets, status) of the last step in host memory: one copy down (``tkamd_decode_stream_read``); for a fused
+        step two -- the CSR, whose last entry is the byte count the host did not hold, and the status, then the bytes"""
+        off, status = np.empty(self.n_streams + 1, dtype=np.int64), np.empty(self.n_streams, dtype=np.uint8)
+        if text.n_bytes < 0:
+            _lib.check(self._lib.tkamd_decode_stream_read(self._h, 0, text._stream, None, off.ctypes.data, status.ctypes.data))
+            res = _lib.DeviceText(text._res.d_bytes, text._res.d_doc_offsets, text._res.d_n_bytes, int(off[-1]))
+            raw = np.empty(res.n_bytes + slack, dtype=np.uint8)
+            _lib.check(self._lib.tkamd_device_text_read(self._tok._h, C.byref(res), self.n_streams, slack, text._stream, raw.ctypes.data, None, None))
+            return raw, off, status
+        raw = np.empty(text.n_bytes + slack, dtype=np.uint8)
         _lib.check(self._lib.tkamd_decode_stream_read(self._h, slack, text._stream, raw.ctypes.data, off.ctypes.data, status.ctypes.data))
         return raw, off, status
 
     def step(self, ids, active=None) -> list:
         """One id per stream (a list or a numpy array on the host; ``active``: truthy for the streams that step) -> per stream the chunk
-        that became printable, or None (nothing yet, or not stepped).  One device call and one copy down.  A stream that reports
+        that became printable, or None (nothing yet, or not stepped).  One device call and one copy down (on a fused object the read
+        is the only wait).  A stream that reports
         InvalidPrefix or a full window raises :class:`DecodeStreamError`, which carries every stream's status and the other streams' chunks."""
         ids = np.ascontiguousarray(ids)
         if ids.dtype not in (np.uint32, np.int32, np.int64):
@@ -562,7 +598,7 @@ class DecodeStreams:
     def step_tensor(self, ids, active=None):
         """A 1-D int32 / int64 torch tensor of ``n_streams`` ids on the tokenizer's device (``active``: a bool / uint8 tensor there), on
         the current stream -> (:class:`DeviceText`, uint8 status tensor [n_streams]); both live in the object until its next step.
-        Never raises on a stream's status."""
+        Never raises on a stream's status.  On a fused object the call only enqueues and ``text.n_bytes`` is -1."""
         import torch
         if ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 1 or ids.numel() != self.n_streams:
             raise TypeError("step_tensor: ids must be a 1-D int32 / int64 tensor of n_streams ids")
@@ -1265,10 +1301,10 @@ class Tokenizer:
                                            "int64" if ids.dtype == torch.int64 else "int32", torch.cuda.current_stream(dev).cuda_stream)
         return out                                           # (the call has waited for the stream: ids / begin / end may go)
 
-    def decode_stream(self, n_streams: int, skip_special_tokens: bool = False, window: int = 32) -> DecodeStreams:
+    def decode_stream(self, n_streams: int, skip_special_tokens: bool = False, window: int = 32, fused: bool = False) -> DecodeStreams:
         """``n_streams`` DecodeStreams (``tokenizers.decoders.DecodeStream``) stepped together on the device: see :class:`DecodeStreams`.
         ``window``: the ids one stream may hold back before it reports a full window."""
-        return DecodeStreams(self, n_streams, skip_special_tokens, window)
+        return DecodeStreams(self, n_streams, skip_special_tokens, window, fused)
 
     def encode_batch_device(self, d_text_ptr: int, d_doc_offsets_ptr: int, n_docs: int, n_bytes: int,
                             offsets: str = "none", word_ids: bool = False, stream: int = 0, unsynced: bool = False) -> DeviceBatch:
