@@ -214,35 +214,7 @@ bool bytelevel_to_raw(const std::string& tok, const std::unordered_map<uint32_t,
     return true;
 }
 
-void build_unicode(HostModel& m) {
-    std::vector<uint8_t> flat(0x110000, 0);
-    for (const UcRun& r : kUcRuns)
-        for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
-    // char::is_numeric, the class the Digits pre-tokenizer splits on: one more flag of the same byte, only where a kernel reads it
-    if (m.pretok == PT_DIGITS_GPT2)
-        for (const UcRun& r : kUcNumericRuns)
-            for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] |= r.flags;
-    // the 39 chars BLOOM's Split class leaves out, Oniguruma's \s and fourteen punctuation marks: the same bit, for this kind's handles only
-    if (m.pretok == PT_BLOOM) {
-        for (uint32_t cp = 0; cp < 0x110000u; ++cp)
-            if (flat[cp] & UC_ONIG_S) flat[cp] |= UC_BLOOM_X;
-        for (uint32_t cp : kBloomPunct) flat[cp] |= UC_BLOOM_X;
-    }
-    m.uc_stage1.assign(UC_STAGE1_LEN, 0);
-    m.uc_stage2.clear();
-    std::unordered_map<std::string, uint16_t> seen;
-    for (uint32_t blk = 0; blk < (uint32_t)UC_STAGE1_LEN; ++blk) {
-        std::string key((const char*)&flat[blk * 256], 256);
-        auto it = seen.find(key);
-        if (it == seen.end()) {
-            uint16_t idx = (uint16_t)(m.uc_stage2.size() / 256);
-            m.uc_stage2.insert(m.uc_stage2.end(), key.begin(), key.end());
-            it = seen.emplace(std::move(key), idx).first;
-        }
-        m.uc_stage1[blk] = it->second;
-    }
-}
-
+// a flag byte per code point -> the two stages the kernels index: the distinct 256-char blocks in order of first use, and per block its index
 void two_stage(const std::vector<uint8_t>& flat, std::vector<uint16_t>* s1, std::vector<uint8_t>* s2) {
     s1->assign(UC_STAGE1_LEN, 0);
     s2->clear();
@@ -257,6 +229,30 @@ void two_stage(const std::vector<uint8_t>& flat, std::vector<uint16_t>* s1, std:
         }
         (*s1)[blk] = it->second;
     }
+}
+
+// the flags of a table of runs, one byte per code point
+template <size_t N>
+std::vector<uint8_t> flat_of(const UcRun (&runs)[N]) {
+    std::vector<uint8_t> flat(0x110000, 0);
+    for (const UcRun& r : runs)
+        for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
+    return flat;
+}
+
+void build_unicode(HostModel& m) {
+    std::vector<uint8_t> flat = flat_of(kUcRuns);
+    // char::is_numeric, the class the Digits pre-tokenizer splits on: one more flag of the same byte, only where a kernel reads it
+    if (m.pretok == PT_DIGITS_GPT2)
+        for (const UcRun& r : kUcNumericRuns)
+            for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] |= r.flags;
+    // the 39 chars BLOOM's Split class leaves out, Oniguruma's \s and fourteen punctuation marks: the same bit, for this kind's handles only
+    if (m.pretok == PT_BLOOM) {
+        for (uint32_t cp = 0; cp < 0x110000u; ++cp)
+            if (flat[cp] & UC_ONIG_S) flat[cp] |= UC_BLOOM_X;
+        for (uint32_t cp : kBloomPunct) flat[cp] |= UC_BLOOM_X;
+    }
+    two_stage(flat, &m.uc_stage1, &m.uc_stage2);
 }
 
 template <class Slot, class IsEmpty, class H1, class H2>
@@ -396,8 +392,6 @@ void build_trie(HostModel& m, const std::vector<std::pair<std::string, uint32_t>
     build_pair_table(items, &m.trie.table, &m.trie.mask, &m.trie.seed);
 }
 
-void build_pair_table(const std::vector<MergeSlot>& items, std::vector<MergeSlot>* out, uint32_t* out_mask, uint32_t* out_seed);
-
 // the members a normalizer chain is made of (tables.hpp ChainMember); -1: not one of them
 int chain_member(const std::string& type) { return type == "NFD" ? CHAIN_NFD : type == "Lowercase" ? CHAIN_LOWERCASE : type == "StripAccents" ? CHAIN_STRIP_ACCENTS : -1; }
 // a chain that reads well but stands in front of something it is not built for: refused in the words the section was always refused by
@@ -409,10 +403,7 @@ std::string chain_refusal(const HostModel& m, const std::string& what) {
 // BertNormalizer data: flags as a 2-stage table, the NFD+strip (kind 0) and lowercase (kind 1) maps as one
 // cuckoo table keyed (cp, kind) with the up-to-3 output code points packed 21 bits each
 void build_bert_norm(HostModel& m) {
-    std::vector<uint8_t> flat(0x110000, 0);
-    for (const UcRun& r : kBnRuns)
-        for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
-    two_stage(flat, &m.bn_stage1, &m.bn_stage2);
+    two_stage(flat_of(kBnRuns), &m.bn_stage1, &m.bn_stage2);
     std::vector<MergeSlot> items;
     auto add = [&](const BnMapRow& r, uint32_t kind) {
         uint64_t v = (uint64_t)r.a | ((uint64_t)r.b << 21) | ((uint64_t)r.c << 42);
@@ -480,10 +471,7 @@ void build_norm_chain(HostModel& m, const std::vector<uint8_t>& members) {
 // NFC data: flags as a 2-stage table; one pair table with the full canonical decompositions -- (cp, 0) -> three code points packed 21
 // bits each, (cp, 1) -> the fourth -- and the primary composites (first, second) -> composite (a second is never below U+0300)
 void build_nfc_tables(HostModel& m) {
-    std::vector<uint8_t> flat(0x110000, 0);
-    for (const UcRun& r : kNfcRuns)
-        for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
-    two_stage(flat, &m.nfc_stage1, &m.nfc_stage2);
+    two_stage(flat_of(kNfcRuns), &m.nfc_stage1, &m.nfc_stage2);
     std::vector<MergeSlot> items;
     for (const NfcDecompRow& r : kNfcDecomp) {
         const uint64_t v = (uint64_t)r.d[0] | ((uint64_t)r.d[1] << 21) | ((uint64_t)r.d[2] << 42);
@@ -498,10 +486,7 @@ void build_nfc_tables(HostModel& m) {
 // compatibility decompositions as one flat array behind a pair table (cp, 0) -> (offset, length)
 void build_nfkc_tables(HostModel& m) {
     build_nfc_tables(m);
-    std::vector<uint8_t> flat(0x110000, 0);
-    for (const UcRun& r : kNfkRuns)
-        for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
-    two_stage(flat, &m.nfc_stage1, &m.nfc_stage2);
+    two_stage(flat_of(kNfkRuns), &m.nfc_stage1, &m.nfc_stage2);
     m.nfk_flat.assign(kNfkFlat, kNfkFlat + NFKC_N_FLAT);
     std::vector<MergeSlot> items;
     for (const NfkDecompRow& r : kNfkDecomp) {
@@ -890,6 +875,75 @@ bool base64_decode(const std::string& in, std::string* out) {
     return pad <= 2;
 }
 
+// ---- small readers of the tokenizer.json sections ----
+// the array a Sequence section keeps its members under ("normalizers", "pretokenizers", "processors"), or null
+const JsonValue* members_of(const JsonValue* section, const char* key) {
+    const JsonValue* a = section ? section->get(key) : nullptr;
+    return (a && a->is_array()) ? a : nullptr;
+}
+// the type of a section or of a Sequence's member; `other` for what is no object
+std::string member_type(const JsonValue* v, const char* other = "?") { return (v && v->is_object()) ? v->get_str("type") : other; }
+// how a refusal names the file's pre-tokenizer
+std::string type_name_or_null(const JsonValue* pt) { return member_type(pt, "null"); }
+// a Metaspace's prepend scheme, where it stands alone and behind WhitespaceSplit (pre_tokenizers/metaspace.rs:34-77: the legacy
+// add_prefix_space = false means "never"); only the U+2581 replacement is on the path
+std::string metaspace_scheme(const JsonValue* ms) {
+    const std::string rep = ms->get_str("replacement");
+    if (rep != kMetaspace) throw Unsupported("pre_tokenizer: Metaspace with replacement '" + rep + "' (only U+2581 is on the path)");
+    const JsonValue* ps = ms->get("prepend_scheme");
+    return (ps && ps->is_string()) ? ps->str : (ms->get_bool("add_prefix_space", true) ? "always" : "never");
+}
+
+// Sequence[Split(a), ByteLevel(b)]: the CLIP layout, BLOOM's, or a member of the tiktoken family -- in this order, each behind its own refusals
+PretokKind parse_split_bytelevel(const JsonValue* a, const JsonValue* b, HostModel& m) {
+    const JsonValue* pat = a->get("pattern");
+    std::string rx = pat ? pat->get_str("Regex") : "";
+    bool invert = a->get_bool("invert", false);
+    std::string beh = a->get_str("behavior");
+    m.byte_level = true;                 // (every layout accepted below is byte-level, without a prefix space)
+    m.add_prefix_space = false;
+    if (rx.empty()) throw Unsupported("pre_tokenizer: Split with a String pattern (only Regex patterns of the tiktoken family are on the path)");
+    if (rx == kClipPattern) {
+        // the CLIP layout.  ByteLevel's own regex (use_regex = true, as the files have it) matches every piece this pattern can cut
+        // as one whole, so both spellings of use_regex are the same pre-tokenizer
+        if (!invert || beh != "Removed")
+            throw Unsupported("pre_tokenizer: the CLIP Split pattern with behavior '" + beh + "'" + (invert ? " inverted" : ", not inverted") +
+                              " (only Removed, inverted, is on the path: the pattern's matches are the pre-tokens)");
+        if (b->get_bool("add_prefix_space", true))
+            throw Unsupported("pre_tokenizer: Sequence[Split(the CLIP pattern), ByteLevel(add_prefix_space=true)] (a prefix space in front of every pre-token)");
+        if (!m.nfc_lower)
+            throw Unsupported("pre_tokenizer: the CLIP Split is only on the path behind the normalizer Sequence[NFC, Replace(Regex '\\s+' -> ' '), Lowercase] "
+                              "(with or without the Replace)");
+        return PT_CLIP;
+    }
+    if (invert && beh == "Removed")
+        throw Unsupported("pre_tokenizer: Split with behavior 'Removed' inverted (only Isolated is on the path; Removed, inverted, with the CLIP pattern alone, "
+                          "which this pattern is not)");
+    if (invert || beh != "Isolated") throw Unsupported("pre_tokenizer: Split with behavior '" + beh + "'" + (invert ? " inverted" : "") + " (only Isolated is on the path)");
+    if (b->get_bool("use_regex", true)) throw Unsupported("pre_tokenizer: Sequence[Split, ByteLevel(use_regex=true)] applies two regexes");
+    // ByteLevel::pre_tokenize puts its prefix space in front of every SPLIT it is handed (byte_level.rs:122-125) -- behind a Split
+    // that is every pre-token, not every document: no tokenizer in use is configured that way, and the path does not build it
+    if (b->get_bool("add_prefix_space", true))
+        throw Unsupported("pre_tokenizer: Sequence[Split, ByteLevel(add_prefix_space=true)] (a prefix space in front of every pre-token)");
+    if (rx == kBloomPattern) {
+        // the BLOOM layout, by the exact pattern string (a pattern one char off is read by the family's parser below and refused
+        // there); Isolated, not inverted, use_regex=false and no prefix space are established above
+        if (m.norm != NORM_NONE)
+            throw Unsupported("pre_tokenizer: BLOOM's Split + ByteLevel behind a normalizer is outside the hot path (only normalizer: null is on it)");
+        return PT_BLOOM;
+    }
+    SplitRule rule{};
+    bool gpt2 = false;
+    std::string why;
+    if (!parse_split_pattern(rx, &rule, &gpt2, &why))
+        throw Unsupported("pre_tokenizer: Split pattern outside the tiktoken family (" + why + ")");
+    if (gpt2) return PT_BYTELEVEL_GPT2;
+    m.split_rule = rule;
+    return PT_LLAMA3;
+}
+
+// reads "pre_tokenizer", norm, nfc_lower, pc_space_runs; writes byte_level, add_prefix_space, ms_*, split_rule, digits_individual and returns
+// the kind.  A pre-tokenizer refuses HERE the normalizers it does not stand behind; what follows from the kind is finish_pretok's.
 PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
     if (!pt || pt->is_null()) {
         // the "▁" normalizers leave every piece ONE pre-token (the device cuts it into units: the model check below proves that exact)
@@ -927,10 +981,7 @@ PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
         if (m.norm != NORM_NONE && m.norm != NORM_PRECOMPILED && m.norm != NORM_NFKC) throw Unsupported("pre_tokenizer: Metaspace behind a normalizer");
         // (behind bare Metaspace a run of spaces is a run of U+2581: the Replace(Regex " {2,}") member is not inert there)
         if (m.pc_space_runs) throw Unsupported("normalizer: Replace(Regex ' {2,}' -> ' ') behind Precompiled is only on the path in front of Sequence[WhitespaceSplit, Metaspace]");
-        const std::string rep = pt->get_str("replacement");
-        if (rep != kMetaspace) throw Unsupported("pre_tokenizer: Metaspace with replacement '" + rep + "' (only U+2581 is on the path)");
-        const JsonValue* ps = pt->get("prepend_scheme");
-        std::string scheme = (ps && ps->is_string()) ? ps->str : (pt->get_bool("add_prefix_space", true) ? "always" : "never");
+        const std::string scheme = metaspace_scheme(pt);
         if (scheme == "always") m.ms_prepend = MS_ALWAYS;
         else if (scheme == "first") m.ms_prepend = MS_FIRST;
         else if (scheme == "never") m.ms_prepend = MS_NEVER;
@@ -949,80 +1000,25 @@ PretokKind parse_pretok(const JsonValue* pt, HostModel& m) {
     if (type == "BertPreTokenizer") return PT_BERT;
     if (type == "Digits") throw Unsupported("pre_tokenizer: Digits alone is outside the hot path (only Sequence[Digits, ByteLevel] in front of byte-level BPE is on it)");
     if (type == "Sequence") {
-        const JsonValue* seq = pt->get("pretokenizers");
-        if (seq && seq->is_array() && seq->arr.size() == 2) {
-            const JsonValue* a = seq->arr[0].get();
-            const JsonValue* b = seq->arr[1].get();
-            if (a->get_str("type") == "Split" && b->get_str("type") == "ByteLevel") {
-                const JsonValue* pat = a->get("pattern");
-                std::string rx = pat ? pat->get_str("Regex") : "";
-                bool invert = a->get_bool("invert", false);
-                std::string beh = a->get_str("behavior");
-                if (rx.empty()) throw Unsupported("pre_tokenizer: Split with a String pattern (only Regex patterns of the tiktoken family are on the path)");
-                if (rx == kClipPattern) {
-                    // the CLIP layout.  ByteLevel's own regex (use_regex = true, as the files have it) matches every piece this pattern can cut
-                    // as one whole, so both spellings of use_regex are the same pre-tokenizer
-                    if (!invert || beh != "Removed")
-                        throw Unsupported("pre_tokenizer: the CLIP Split pattern with behavior '" + beh + "'" + (invert ? " inverted" : ", not inverted") +
-                                          " (only Removed, inverted, is on the path: the pattern's matches are the pre-tokens)");
-                    if (b->get_bool("add_prefix_space", true))
-                        throw Unsupported("pre_tokenizer: Sequence[Split(the CLIP pattern), ByteLevel(add_prefix_space=true)] (a prefix space in front of every pre-token)");
-                    if (!m.nfc_lower)
-                        throw Unsupported("pre_tokenizer: the CLIP Split is only on the path behind the normalizer Sequence[NFC, Replace(Regex '\\s+' -> ' '), Lowercase] "
-                                          "(with or without the Replace)");
-                    m.byte_level = true;
-                    m.add_prefix_space = false;
-                    return PT_CLIP;
-                }
-                if (invert && beh == "Removed")
-                    throw Unsupported("pre_tokenizer: Split with behavior 'Removed' inverted (only Isolated is on the path; Removed, inverted, with the CLIP pattern alone, "
-                                      "which this pattern is not)");
-                if (invert || beh != "Isolated") throw Unsupported("pre_tokenizer: Split with behavior '" + beh + "'" + (invert ? " inverted" : "") + " (only Isolated is on the path)");
-                if (b->get_bool("use_regex", true)) throw Unsupported("pre_tokenizer: Sequence[Split, ByteLevel(use_regex=true)] applies two regexes");
-                // ByteLevel::pre_tokenize puts its prefix space in front of every SPLIT it is handed (byte_level.rs:122-125) -- behind a Split
-                // that is every pre-token, not every document: no tokenizer in use is configured that way, and the path does not build it
-                if (b->get_bool("add_prefix_space", true))
-                    throw Unsupported("pre_tokenizer: Sequence[Split, ByteLevel(add_prefix_space=true)] (a prefix space in front of every pre-token)");
-                if (rx == kBloomPattern) {
-                    // the BLOOM layout, by the exact pattern string (a pattern one char off is read by the family's parser below and refused
-                    // there); Isolated, not inverted, use_regex=false and no prefix space are established above
-                    if (m.norm != NORM_NONE)
-                        throw Unsupported("pre_tokenizer: BLOOM's Split + ByteLevel behind a normalizer is outside the hot path (only normalizer: null is on it)");
-                    m.byte_level = true;
-                    m.add_prefix_space = false;
-                    return PT_BLOOM;
-                }
-                SplitRule rule{};
-                bool gpt2 = false;
-                std::string why;
-                if (!parse_split_pattern(rx, &rule, &gpt2, &why))
-                    throw Unsupported("pre_tokenizer: Split pattern outside the tiktoken family (" + why + ")");
-                m.byte_level = true;
-                m.add_prefix_space = false;
-                if (gpt2) return PT_BYTELEVEL_GPT2;
-                m.split_rule = rule;
-                return PT_LLAMA3;
-            }
-        }
-        if (seq && seq->is_array() && seq->arr.size() == 2 && seq->arr[0] && seq->arr[1] && seq->arr[0]->get_str("type") == "WhitespaceSplit" &&
+        const JsonValue* seq = members_of(pt, "pretokenizers");
+        if (seq && seq->arr.size() == 2 && seq->arr[0]->get_str("type") == "Split" && seq->arr[1]->get_str("type") == "ByteLevel")
+            return parse_split_bytelevel(seq->arr[0].get(), seq->arr[1].get(), m);
+        if (seq && seq->arr.size() == 2 && seq->arr[0] && seq->arr[1] && seq->arr[0]->get_str("type") == "WhitespaceSplit" &&
             seq->arr[1]->get_str("type") == "Metaspace") {
             // Sequence[WhitespaceSplit, Metaspace] (XLM-R, T5, mBART): the words between char::is_whitespace chars, each with its "▁".  On the
             // path behind Precompiled alone: the front then reads the normalizer's text, where the word rule runs (kernels/metaspace.hip MS_WORD)
             if (m.norm != NORM_PRECOMPILED)
                 throw Unsupported("pre_tokenizer: Sequence[WhitespaceSplit, Metaspace] is only on the path behind a Precompiled normalizer");
             const JsonValue* b = seq->arr[1].get();
-            const std::string rep = b->get_str("replacement");
-            if (rep != kMetaspace) throw Unsupported("pre_tokenizer: Metaspace with replacement '" + rep + "' (only U+2581 is on the path)");
-            const JsonValue* ps = b->get("prepend_scheme");
-            const std::string scheme = (ps && ps->is_string()) ? ps->str : (b->get_bool("add_prefix_space", true) ? "always" : "never");
+            const std::string scheme = metaspace_scheme(b);
             if (scheme != "always")
                 throw Unsupported("pre_tokenizer: Sequence[WhitespaceSplit, Metaspace] with prepend_scheme '" + scheme + "' (only 'always' is on the path)");
             m.ms_prepend = MS_WORD;
             m.ms_split = b->get_bool("split", true);
             return PT_METASPACE;
         }
-        if (seq && seq->is_array() && parse_split_chain(seq, m)) return PT_SPLIT_CHAIN;
-        if (seq && seq->is_array() && parse_digits_bytelevel(seq, m)) return PT_DIGITS_GPT2;
+        if (seq && parse_split_chain(seq, m)) return PT_SPLIT_CHAIN;
+        if (seq && parse_digits_bytelevel(seq, m)) return PT_DIGITS_GPT2;
         throw Unsupported("pre_tokenizer: this Sequence is outside the hot path");
     }
     throw Unsupported("pre_tokenizer: type '" + type + "' is outside the hot path");
@@ -1041,23 +1037,25 @@ uint32_t fnv1a(const uint8_t* p, size_t n) {
     return h;
 }
 
+// str::replace of a non-empty literal: every match, left to right, none overlapping
+static std::string replace_all(const std::string& t, const std::string& from, const std::string& to) {
+    std::string out;
+    size_t pos = 0;
+    for (;;) {
+        const size_t hit = t.find(from, pos);
+        if (hit == std::string::npos) { out.append(t, pos, std::string::npos); break; }
+        out.append(t, pos, hit - pos);
+        out += to;
+        pos = hit + from.size();
+    }
+    return out;
+}
+
 // WordPiece decoder cleanup (decoders/wordpiece.rs:31-44): eleven literal replacements applied in order
 static std::string wp_cleanup(std::string t) {
     static const char* const rules[][2] = {{" .", "."}, {" ?", "?"}, {" !", "!"}, {" ,", ","}, {" ' ", "'"}, {" n't", "n't"},
                                            {" 'm", "'m"}, {" do not", " don't"}, {" 's", "'s"}, {" 've", "'ve"}, {" 're", "'re"}};
-    for (auto& r : rules) {
-        const std::string from = r[0], to = r[1];
-        std::string out;
-        size_t pos = 0;
-        for (;;) {
-            size_t hit = t.find(from, pos);
-            if (hit == std::string::npos) { out.append(t, pos, std::string::npos); break; }
-            out.append(t, pos, hit - pos);
-            out += to;
-            pos = hit + from.size();
-        }
-        t.swap(out);
-    }
+    for (auto& r : rules) t = replace_all(t, r[0], r[1]);
     return t;
 }
 
@@ -1080,25 +1078,14 @@ static void build_decode_tables(HostModel& m, const JsonValue* root, const std::
     struct DecEl { int kind; std::string a, b; int64_t start, stop; };      // 0: Replace a -> b; 1: Strip a (one char), start / stop
     std::vector<DecEl> chain;
     auto replace_lit = [](const std::string& t, const std::string& from, const std::string& to) {
-        std::string out;
-        if (from.empty()) {                    // str::replace("", to): the empty pattern matches in front of every char and at the end
-            out = to;
-            for (size_t i = 0; i < t.size();) {
-                size_t j = i + 1;
-                while (j < t.size() && ((uint8_t)t[j] & 0xC0u) == 0x80u) ++j;
-                out.append(t, i, j - i);
-                out += to;
-                i = j;
-            }
-            return out;
-        }
-        size_t pos = 0;
-        for (;;) {
-            const size_t hit = t.find(from, pos);
-            if (hit == std::string::npos) { out.append(t, pos, std::string::npos); break; }
-            out.append(t, pos, hit - pos);
+        if (!from.empty()) return replace_all(t, from, to);
+        std::string out = to;                  // str::replace("", to): the empty pattern matches in front of every char and at the end
+        for (size_t i = 0; i < t.size();) {
+            size_t j = i + 1;
+            while (j < t.size() && ((uint8_t)t[j] & 0xC0u) == 0x80u) ++j;
+            out.append(t, i, j - i);
             out += to;
-            pos = hit + from.size();
+            i = j;
         }
         return out;
     };
@@ -1231,20 +1218,8 @@ static void build_decode_tables(HostModel& m, const JsonValue* root, const std::
         } else if (m.decoder == DEC_BPE) {
             // token.replace(suffix, " "), and token.replace(suffix, "") on the LAST token (decoders/bpe.rs:30-37): `first` is the form of
             // the position that has one of its own -- here the last kept token (dec_special_is_last)
-            auto replace_all = [&](const std::string& with) {
-                std::string out;
-                size_t pos = 0;
-                for (;;) {
-                    const size_t hit = t.find(suffix, pos);
-                    if (hit == std::string::npos) { out.append(t, pos, std::string::npos); break; }
-                    out.append(t, pos, hit - pos);
-                    out += with;
-                    pos = hit + suffix.size();
-                }
-                return out;
-            };
-            first = replace_all("");
-            rest = replace_all(" ");
+            first = replace_all(t, suffix, "");
+            rest = replace_all(t, suffix, " ");
         } else if (m.decoder == DEC_CTC) {
             // (an empty pad_token replaces nothing by nothing; an empty word_delimiter_token puts a space in front of every char of
             // the cleaned token and one at its end, as str::replace does -- " " for a token the pad emptied)
@@ -1297,18 +1272,54 @@ static void build_decode_tables(HostModel& m, const JsonValue* root, const std::
     m.dec_blob.resize(m.dec_blob.size() + 16, 0);                        // readable slack for vector loads
 }
 
-HostModel HostModel::from_json(const char* json, size_t len) {
-    JsonPtr root;
-    try {
-        root = json_parse(json, len);
-    } catch (const std::exception& e) {
-        throw Invalid(e.what());
-    }
-    if (!root->is_object()) throw Invalid("tokenizer.json: top level is not an object");
-    HostModel m;
-    std::fill(m.byte_id, m.byte_id + 256, 0xFFFFFFFFu);
+// ==== HostModel::from_json, stage by stage (its table of contents is from_json itself, at the end).  The stages run in the order the
+// sections were always read in, and THE ORDER IS PART OF THE RESULT: a file with two faults gets the message of the refusal asked first,
+// and the vocabulary map is walked in the order it was filled in, which lays out every table.  tests/test_host_model_outcomes.py pins
+// both: no refusal moves, merges or changes its words unless that test's golden data changes with it.
+namespace {
 
-    // ---- truncation / padding: an epilogue over the finished token CSR (tokenizer/mod.rs:1265-1317) ----
+// What the stages from read_vocab on share of the model section.  Never copied: the iteration order of `id` decides raw_tokens and
+// through them the layout of every table, and a copy of an unordered_map need not iterate like its source.
+struct Vocab {
+    const JsonValue* model = nullptr;                // the "model" section
+    std::string mtype;                               // its type, the legacy untagged spellings resolved
+    bool unigram = false;
+    std::unordered_map<std::string, uint32_t> id;    // piece -> id; what added tokens, templates, padding and the decode tables read
+    std::vector<std::string> uni_pieces;             // Unigram: id -> piece, per index (id_to_token, unigram/model.rs:483-485)
+    uint32_t b2c[256];                               // the GPT-2 byte alphabet and its inverse
+    std::unordered_map<uint32_t, uint8_t> c2b;
+    Vocab() {
+        build_bytes_char(b2c);
+        for (int b = 0; b < 256; ++b) c2b[b2c[b]] = (uint8_t)b;
+    }
+    Vocab(const Vocab&) = delete;
+};
+
+// ---- small things the stages share (the readers of sections stand in front of parse_pretok) ----
+// the class flags of a code point (uc_stage1 / uc_stage2 must be built)
+uint32_t uc_flags(const HostModel& m, uint32_t cp) { return cp < 0x110000u ? m.uc_stage2[((size_t)m.uc_stage1[cp >> 8] << 8) | (cp & 255u)] : 0u; }
+bool opt_str(const JsonValue* section, const char* key, std::string* out) {
+    const JsonValue* x = section->get(key);
+    if (x && x->is_string()) { *out = x->str; return true; }
+    return false;
+}
+// the id of the byte token "<0xXX>" of byte b, or null; *spelt (if given): the token
+const uint32_t* byte_token_id(const Vocab& v, int b, std::string* spelt = nullptr) {
+    char code[8];
+    snprintf(code, sizeof(code), "<0x%02X>", b);
+    if (spelt) *spelt = code;
+    auto it = v.id.find(code);
+    return it == v.id.end() ? nullptr : &it->second;
+}
+// has_unk / unk_id of a model that names its unk token
+void lookup_unk(const Vocab& v, HostModel& m) {
+    auto it = v.id.find(m.unk_token);
+    if (it != v.id.end()) { m.has_unk = true; m.unk_id = it->second; }
+}
+
+// ---- 1. truncation / padding: an epilogue over the finished token CSR (tokenizer/mod.rs:1265-1317) ----
+// reads "truncation", "padding"; writes trunc_*, pad_*.  (Its two Invalid refusals come before every other section's.)
+void parse_truncation_padding(const JsonValue* root, HostModel& m) {
     const JsonValue* trunc = root->get("truncation");
     if (trunc && !trunc->is_null()) {
         m.trunc_on = true;
@@ -1336,316 +1347,373 @@ HostModel HostModel::from_json(const char* json, size_t len) {
         m.pad_token = pad->get_str("pad_token", "[PAD]");
         if (m.pad_id >= (1u << 24)) throw Unsupported("padding id beyond 2^24");
     }
+}
 
-    // ---- normalizer ----
-    const JsonValue* norm = root->get("normalizer");
-    if (norm && !norm->is_null()) {
-        std::string t = norm->get_str("type");
-        if (t == "BertNormalizer") {
-            m.norm = NORM_BERT;
-            m.bn_clean_text = norm->get_bool("clean_text", true);
-            m.bn_handle_chinese = norm->get_bool("handle_chinese_chars", true);
-            m.bn_lowercase = norm->get_bool("lowercase", true);
-            const JsonValue* sa = norm->get("strip_accents");
-            m.bn_strip_accents = (sa && sa->is_bool()) ? sa->b : m.bn_lowercase;  // normalizers/bert.rs:124
-        } else if (t == "NFC") {
-            m.norm = NORM_NFC;
-        } else if (t == "Precompiled" || (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() && !norm->get("normalizers")->arr.empty() &&
-                                          norm->get("normalizers")->arr[0] && norm->get("normalizers")->arr[0]->is_object() &&
-                                          norm->get("normalizers")->arr[0]->get_str("type") == "Precompiled")) {
-            // Precompiled, alone or first in a Sequence whose only other member may be the Replace(Regex " {2,}" -> " ") of XLM-R / T5 files: behind
-            // WhitespaceSplit that member is inert (it touches runs of spaces alone, which the split drops), so no kernel runs for it -- the
-            // pre-tokenizer below refuses it in front of anything else
-            const JsonValue* pc = norm;
-            if (t == "Sequence") {
-                const auto& arr = norm->get("normalizers")->arr;
-                pc = arr[0].get();
-                for (size_t k = 1; k < arr.size(); ++k) {
-                    const JsonValue* r = arr[k].get();
-                    const std::string rt = (r && r->is_object()) ? r->get_str("type") : "?";
-                    const JsonValue* pat = rt == "Replace" ? r->get("pattern") : nullptr;
-                    if (k != 1 || arr.size() != 2 || !pat || !pat->is_object() || !pat->get("Regex") || pat->get_str("Regex") != " {2,}" || r->get_str("content") != " ")
-                        throw Unsupported("normalizer: '" + rt + "' behind Precompiled in a Sequence is outside the hot path (only Replace(Regex ' {2,}' -> ' ') is on it)");
-                    m.pc_space_runs = true;
-                }
-            }
-            const JsonValue* cm = pc->get("precompiled_charsmap");
-            if (!cm || !cm->is_string()) throw Unsupported("normalizer: Precompiled without a precompiled_charsmap string");
-            std::string blob;
-            if (!base64_decode(cm->str, &blob)) throw Unsupported("normalizer: Precompiled precompiled_charsmap is not base64");
-            m.set_precompiled(blob);
-            m.norm = NORM_PRECOMPILED;
-        } else if (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() && norm->get("normalizers")->arr.empty()) {
-            // Sequence[] applies nothing (normalizers/utils.rs: a loop over no normalizer): DeepSeek-V3 files carry it
-        } else if (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() &&
-                   std::any_of(norm->get("normalizers")->arr.begin(), norm->get("normalizers")->arr.end(),
-                               [](const JsonPtr& v) { return v && v->is_object() && v->get_str("type") == "NFC"; })) {
-            // NFC alone inside a Sequence is NFC; next to any other normalizer the alignment of one is the input of the other: not on the path
-            // ... but for the chain of the CLIP files, Sequence[NFC, Replace(Regex "\\s+" -> " "), Lowercase]: Lowercase is a map of single chars
-            // that the NFC core applies to what it composed (nfc_core.hpp NFC_LOWER), and the Replace only touches runs of \s chars, which the CLIP
-            // pre-tokenizer drops -- it is inert there, and no kernel runs for it (but for the normalized added tokens: nfc_ws_fold).  Whether the
-            // CLIP pre-tokenizer follows is asked below.
-            const auto& arr = norm->get("normalizers")->arr;
-            if (arr.size() != 1) {
-                const std::string base = "normalizer: NFC inside a longer Sequence is outside the hot path (only NFC alone, or Sequence[NFC], is on it; and "
-                                         "Sequence[NFC, Replace(Regex '\\s+' -> ' '), Lowercase], with or without the Replace, in front of the CLIP pre-tokenizer: ";
-                auto ty = [&](size_t k) { return (arr[k] && arr[k]->is_object()) ? arr[k]->get_str("type") : std::string("?"); };
-                const bool shape = (arr.size() == 2 && ty(0) == "NFC" && ty(1) == "Lowercase") || (arr.size() == 3 && ty(0) == "NFC" && ty(1) == "Replace" && ty(2) == "Lowercase");
-                if (!shape) throw Unsupported(base + "this Sequence has other members, or these in another order)");
-                if (arr.size() == 3) {
-                    const JsonValue* pat = arr[1]->get("pattern");
-                    if (!pat || !pat->is_object() || !pat->get("Regex") || pat->get_str("Regex") != "\\s+" || arr[1]->get_str("content") != " ")
-                        throw Unsupported(base + "this Sequence's Replace is another one)");
-                    m.nfc_ws_fold = true;
-                }
-                const JsonValue* pt = root->get("pre_tokenizer");
-                const JsonValue* seq = (pt && pt->is_object() && pt->get_str("type") == "Sequence") ? pt->get("pretokenizers") : nullptr;
-                const JsonValue* sp = (seq && seq->is_array() && seq->arr.size() == 2 && seq->arr[0] && seq->arr[0]->is_object() && seq->arr[0]->get_str("type") == "Split")
-                                          ? seq->arr[0]->get("pattern") : nullptr;
-                if (!sp || !sp->is_object() || sp->get_str("Regex") != kClipPattern) throw Unsupported(base + "this file's pre-tokenizer is another one)");
-                m.nfc_lower = true;
-            }
-            m.norm = NORM_NFC;
-        } else if (chain_member(t) >= 0 || (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() &&
-                                            std::any_of(norm->get("normalizers")->arr.begin(), norm->get("normalizers")->arr.end(),
-                                                        [](const JsonPtr& v) { return v && v->is_object() && chain_member(v->get_str("type")) >= 0; }))) {
-            // NFD, Lowercase, StripAccents: alone, or a Sequence of them.  What the file says is read here; whether it is on the path in
-            // front of this file's model and pre-tokenizer is decided below, once they are known, in the words this section was refused by
-            m.chain_spelling = t == "Sequence" ? "this Sequence" : "type '" + t + "'";
-            if (t == "Sequence") {
-                for (const JsonPtr& v : norm->get("normalizers")->arr) {
-                    const std::string mt = (v && v->is_object()) ? v->get_str("type") : "?";
-                    const int k = chain_member(mt);
-                    if (k < 0) throw Unsupported("normalizer: '" + mt + "' next to NFD / Lowercase / StripAccents in a Sequence is outside the hot path (only these three chain)");
-                    if (m.chain_has((uint8_t)k)) throw Unsupported("normalizer: '" + mt + "' twice in a Sequence is outside the hot path");
-                    if (k == CHAIN_NFD && m.chain_has(CHAIN_STRIP_ACCENTS))
-                        throw Unsupported("normalizer: 'StripAccents' in front of 'NFD' in a Sequence is outside the hot path (the marks NFD splits off afterwards stay, "
-                                          "in the order the text around them decides)");
-                    m.chain.push_back((uint8_t)k);
-                }
-            } else m.chain.push_back((uint8_t)chain_member(t));
-            m.norm = NORM_CHAIN;
-        } else if (t == "NFKC" || (t == "Sequence" && norm->get("normalizers") && norm->get("normalizers")->is_array() &&
-                                   std::any_of(norm->get("normalizers")->arr.begin(), norm->get("normalizers")->arr.end(),
-                                               [](const JsonPtr& v) { return v && v->is_object() && v->get_str("type") == "NFKC"; }))) {
-            // NFKC alone, or alone inside a Sequence.  What the file says is read here; whether it is on the path in front of this file's
-            // pre-tokenizer and model is decided below, once they are known, in the words the type was always refused by
-            if (t == "Sequence") {
-                const auto& arr = norm->get("normalizers")->arr;
-                for (const JsonPtr& v : arr) {
-                    const std::string mt = (v && v->is_object()) ? v->get_str("type") : "?";
-                    if (mt == "NFKC") continue;
-                    m.nfkc_refusal = "normalizer: '" + mt + "' next to NFKC in a Sequence is outside the hot path (only NFKC alone, or Sequence[NFKC], is on it)";
-                    break;
-                }
-                if (m.nfkc_refusal.empty() && arr.size() != 1)
-                    m.nfkc_refusal = "normalizer: 'NFKC' twice in a Sequence is outside the hot path (only NFKC alone, or Sequence[NFKC], is on it)";
-            }
-            m.norm = NORM_NFKC;
-        } else if (t == "Sequence" || t == "Replace" || t == "Prepend") {
-            // the "▁" normalizers of SentencePiece conversions: Sequence[Prepend("▁"), Replace(" " -> "▁")] (Llama-2, Mistral) or
-            // Replace(" " -> "▁") alone (Gemma-style); anything else of these types is outside the path
-            auto is_replace = [](const JsonValue* r) {
-                if (!r || r->get_str("type") != "Replace") return false;
-                const JsonValue* pat = r->get("pattern");
-                if (!pat || !pat->is_object() || !pat->get("String")) throw Unsupported("normalizer: Replace with a Regex pattern");
-                if (pat->get_str("String") != " ") throw Unsupported("normalizer: Replace of '" + pat->get_str("String") + "' (only ' ' -> U+2581 is on the path)");
-                if (r->get_str("content") != kMetaspace) throw Unsupported("normalizer: Replace with '" + r->get_str("content") + "' (only ' ' -> U+2581 is on the path)");
-                return true;
-            };
-            auto is_prepend = [](const JsonValue* r) {
-                if (!r || r->get_str("type") != "Prepend") return false;
-                if (r->get_str("prepend") != kMetaspace) throw Unsupported("normalizer: Prepend of '" + r->get_str("prepend") + "' (only U+2581 is on the path)");
-                return true;
-            };
-            const JsonValue* seq = t == "Sequence" ? norm->get("normalizers") : nullptr;
-            if (t == "Replace" && is_replace(norm)) m.ms_prepend = MS_NEVER;
-            else if (seq && seq->is_array() && seq->arr.size() == 2 && is_prepend(seq->arr[0].get()) && is_replace(seq->arr[1].get())) m.ms_prepend = MS_PIECE;
-            else throw Unsupported("normalizer: this " + t + " is outside the hot path (only Sequence[Prepend(U+2581), Replace(' ' -> U+2581)] and "
-                                   "Replace(' ' -> U+2581) are)");
-            m.norm = NORM_METASPACE;
-        } else {
-            throw Unsupported("normalizer: type '" + t + "' is outside the hot path");
+// ---- 2. normalizer: one reader per family, picked by parse_normalizer ----
+void parse_bert_normalizer(const JsonValue* norm, HostModel& m) {
+    m.norm = NORM_BERT;
+    m.bn_clean_text = norm->get_bool("clean_text", true);
+    m.bn_handle_chinese = norm->get_bool("handle_chinese_chars", true);
+    m.bn_lowercase = norm->get_bool("lowercase", true);
+    const JsonValue* sa = norm->get("strip_accents");
+    m.bn_strip_accents = (sa && sa->is_bool()) ? sa->b : m.bn_lowercase;  // normalizers/bert.rs:124
+}
+
+// Precompiled, alone or first in a Sequence (seq: its members) whose only other member may be the Replace(Regex " {2,}" -> " ") of XLM-R / T5
+// files: behind WhitespaceSplit that member is inert (it touches runs of spaces alone, which the split drops), so no kernel runs for it --
+// parse_pretok refuses it in front of anything else
+void parse_precompiled(const JsonValue* norm, const JsonValue* seq, HostModel& m) {
+    const JsonValue* pc = norm;
+    if (seq) {
+        const auto& arr = seq->arr;
+        pc = arr[0].get();
+        for (size_t k = 1; k < arr.size(); ++k) {
+            const JsonValue* r = arr[k].get();
+            const std::string rt = member_type(r);
+            const JsonValue* pat = rt == "Replace" ? r->get("pattern") : nullptr;
+            if (k != 1 || arr.size() != 2 || !pat || !pat->is_object() || !pat->get("Regex") || pat->get_str("Regex") != " {2,}" || r->get_str("content") != " ")
+                throw Unsupported("normalizer: '" + rt + "' behind Precompiled in a Sequence is outside the hot path (only Replace(Regex ' {2,}' -> ' ') is on it)");
+            m.pc_space_runs = true;
         }
     }
+    const JsonValue* cm = pc->get("precompiled_charsmap");
+    if (!cm || !cm->is_string()) throw Unsupported("normalizer: Precompiled without a precompiled_charsmap string");
+    std::string blob;
+    if (!base64_decode(cm->str, &blob)) throw Unsupported("normalizer: Precompiled precompiled_charsmap is not base64");
+    m.set_precompiled(blob);
+    m.norm = NORM_PRECOMPILED;
+}
 
-    // ---- pre-tokenizer ----
-    if (m.norm == NORM_CHAIN) {                                        // (asked of the file before the pre-tokenizers' own refusals of a normalizer)
+// A Sequence that holds NFC.  NFC alone inside a Sequence is NFC; next to any other normalizer the alignment of one is the input of the
+// other: not on the path ... but for the chain of the CLIP files, Sequence[NFC, Replace(Regex "\\s+" -> " "), Lowercase]: Lowercase is a
+// map of single chars that the NFC core applies to what it composed (nfc_core.hpp NFC_LOWER), and the Replace only touches runs of \s
+// chars, which the CLIP pre-tokenizer drops -- it is inert there, and no kernel runs for it (but for the normalized added tokens:
+// nfc_ws_fold).
+// LOOKS AHEAD: the chain is accepted only if the file's pre-tokenizer is a Sequence of two that opens with a Split of the CLIP pattern --
+// the one place the normalizer reads "pre_tokenizer", and it reads the pattern alone.  Whether that pre-tokenizer is the CLIP one in
+// full is parse_pretok's to say; finish_pretok refuses the chain if it was not.
+void parse_nfc_sequence(const JsonValue* root, const JsonValue* seq, HostModel& m) {
+    const auto& arr = seq->arr;
+    if (arr.size() != 1) {
+        const std::string base = "normalizer: NFC inside a longer Sequence is outside the hot path (only NFC alone, or Sequence[NFC], is on it; and "
+                                 "Sequence[NFC, Replace(Regex '\\s+' -> ' '), Lowercase], with or without the Replace, in front of the CLIP pre-tokenizer: ";
+        auto ty = [&](size_t k) { return member_type(arr[k].get()); };
+        const bool shape = (arr.size() == 2 && ty(0) == "NFC" && ty(1) == "Lowercase") || (arr.size() == 3 && ty(0) == "NFC" && ty(1) == "Replace" && ty(2) == "Lowercase");
+        if (!shape) throw Unsupported(base + "this Sequence has other members, or these in another order)");
+        if (arr.size() == 3) {
+            const JsonValue* pat = arr[1]->get("pattern");
+            if (!pat || !pat->is_object() || !pat->get("Regex") || pat->get_str("Regex") != "\\s+" || arr[1]->get_str("content") != " ")
+                throw Unsupported(base + "this Sequence's Replace is another one)");
+            m.nfc_ws_fold = true;
+        }
         const JsonValue* pt = root->get("pre_tokenizer");
-        const std::string ptype = (pt && pt->is_object()) ? pt->get_str("type") : "null";
+        const JsonValue* pts = member_type(pt) == "Sequence" ? members_of(pt, "pretokenizers") : nullptr;
+        const JsonValue* sp = (pts && pts->arr.size() == 2 && member_type(pts->arr[0].get()) == "Split") ? pts->arr[0]->get("pattern") : nullptr;
+        if (!sp || !sp->is_object() || sp->get_str("Regex") != kClipPattern) throw Unsupported(base + "this file's pre-tokenizer is another one)");
+        m.nfc_lower = true;
+    }
+    m.norm = NORM_NFC;
+}
+
+// NFD, Lowercase, StripAccents: alone (t), or a Sequence of them (seq).  What the file says is read here; whether it is on the path in
+// front of this file's pre-tokenizer and model is decided by check_normalizer_against_pretok_type and check_layout, once they are
+// known, in the words this section was refused by
+void parse_norm_chain(const std::string& t, const JsonValue* seq, HostModel& m) {
+    m.chain_spelling = t == "Sequence" ? "this Sequence" : "type '" + t + "'";
+    if (t == "Sequence") {
+        for (const JsonPtr& v : seq->arr) {
+            const std::string mt = member_type(v.get());
+            const int k = chain_member(mt);
+            if (k < 0) throw Unsupported("normalizer: '" + mt + "' next to NFD / Lowercase / StripAccents in a Sequence is outside the hot path (only these three chain)");
+            if (m.chain_has((uint8_t)k)) throw Unsupported("normalizer: '" + mt + "' twice in a Sequence is outside the hot path");
+            if (k == CHAIN_NFD && m.chain_has(CHAIN_STRIP_ACCENTS))
+                throw Unsupported("normalizer: 'StripAccents' in front of 'NFD' in a Sequence is outside the hot path (the marks NFD splits off afterwards stay, "
+                                  "in the order the text around them decides)");
+            m.chain.push_back((uint8_t)k);
+        }
+    } else m.chain.push_back((uint8_t)chain_member(t));
+    m.norm = NORM_CHAIN;
+}
+
+// NFKC alone, or alone inside a Sequence (seq, else null).  What the file says is read here; a Sequence with more in it is only NOTED
+// (nfkc_refusal): check_normalizer_against_pretok_type throws it once the pre-tokenizer's type is known, behind the words the type
+// was always refused by
+void parse_nfkc(const JsonValue* seq, HostModel& m) {
+    if (seq) {
+        for (const JsonPtr& v : seq->arr) {
+            const std::string mt = member_type(v.get());
+            if (mt == "NFKC") continue;
+            m.nfkc_refusal = "normalizer: '" + mt + "' next to NFKC in a Sequence is outside the hot path (only NFKC alone, or Sequence[NFKC], is on it)";
+            break;
+        }
+        if (m.nfkc_refusal.empty() && seq->arr.size() != 1)
+            m.nfkc_refusal = "normalizer: 'NFKC' twice in a Sequence is outside the hot path (only NFKC alone, or Sequence[NFKC], is on it)";
+    }
+    m.norm = NORM_NFKC;
+}
+
+// the "▁" normalizers of SentencePiece conversions: Sequence[Prepend("▁"), Replace(" " -> "▁")] (Llama-2, Mistral) or
+// Replace(" " -> "▁") alone (Gemma-style); anything else of these types is outside the path
+void parse_u2581_normalizers(const JsonValue* norm, const std::string& t, HostModel& m) {
+    auto is_replace = [](const JsonValue* r) {
+        if (!r || r->get_str("type") != "Replace") return false;
+        const JsonValue* pat = r->get("pattern");
+        if (!pat || !pat->is_object() || !pat->get("String")) throw Unsupported("normalizer: Replace with a Regex pattern");
+        if (pat->get_str("String") != " ") throw Unsupported("normalizer: Replace of '" + pat->get_str("String") + "' (only ' ' -> U+2581 is on the path)");
+        if (r->get_str("content") != kMetaspace) throw Unsupported("normalizer: Replace with '" + r->get_str("content") + "' (only ' ' -> U+2581 is on the path)");
+        return true;
+    };
+    auto is_prepend = [](const JsonValue* r) {
+        if (!r || r->get_str("type") != "Prepend") return false;
+        if (r->get_str("prepend") != kMetaspace) throw Unsupported("normalizer: Prepend of '" + r->get_str("prepend") + "' (only U+2581 is on the path)");
+        return true;
+    };
+    const JsonValue* seq = t == "Sequence" ? members_of(norm, "normalizers") : nullptr;
+    if (t == "Replace" && is_replace(norm)) m.ms_prepend = MS_NEVER;
+    else if (seq && seq->arr.size() == 2 && is_prepend(seq->arr[0].get()) && is_replace(seq->arr[1].get())) m.ms_prepend = MS_PIECE;
+    else throw Unsupported("normalizer: this " + t + " is outside the hot path (only Sequence[Prepend(U+2581), Replace(' ' -> U+2581)] and "
+                           "Replace(' ' -> U+2581) are)");
+    m.norm = NORM_METASPACE;
+}
+
+// reads "normalizer" (and, for the CLIP chain alone, the Split pattern of "pre_tokenizer": parse_nfc_sequence); writes norm and the
+// family's options (bn_*, pc_*, chain, chain_spelling, nfkc_refusal, nfc_lower, nfc_ws_fold, ms_prepend).  The families are asked in this
+// order: a Sequence that holds members of two of them belongs to the first.
+void parse_normalizer(const JsonValue* root, HostModel& m) {
+    const JsonValue* norm = root->get("normalizer");
+    if (!norm || norm->is_null()) return;
+    const std::string t = norm->get_str("type");
+    const JsonValue* seq = t == "Sequence" ? members_of(norm, "normalizers") : nullptr;
+    auto holds = [&](auto&& is_one) { return seq && std::any_of(seq->arr.begin(), seq->arr.end(), [&](const JsonPtr& v) { return is_one(member_type(v.get())); }); };
+    if (t == "BertNormalizer") parse_bert_normalizer(norm, m);
+    else if (t == "NFC") m.norm = NORM_NFC;
+    else if (t == "Precompiled" || (seq && !seq->arr.empty() && member_type(seq->arr[0].get()) == "Precompiled")) parse_precompiled(norm, seq, m);
+    else if (seq && seq->arr.empty()) {
+        // Sequence[] applies nothing (normalizers/utils.rs: a loop over no normalizer): DeepSeek-V3 files carry it
+    } else if (holds([](const std::string& ty) { return ty == "NFC"; })) parse_nfc_sequence(root, seq, m);
+    else if (chain_member(t) >= 0 || holds([](const std::string& ty) { return chain_member(ty) >= 0; })) parse_norm_chain(t, seq, m);
+    else if (t == "NFKC" || holds([](const std::string& ty) { return ty == "NFKC"; })) parse_nfkc(seq, m);
+    else if (t == "Sequence" || t == "Replace" || t == "Prepend") parse_u2581_normalizers(norm, t, m);
+    else throw Unsupported("normalizer: type '" + t + "' is outside the hot path");
+}
+
+// ---- 3. the normalizer against the pre-tokenizer's TYPE ----
+// LOOKS AHEAD: reads the type (and Metaspace's split) of "pre_tokenizer" before parse_pretok does, so that a chain or an NFKC in front of
+// the wrong pre-tokenizer is refused as the NORMALIZER it is, in front of parse_pretok's own refusals of a normalizer ("Metaspace behind
+// a normalizer", ...).  reads norm, chain_spelling, nfkc_refusal; writes nothing.
+void check_normalizer_against_pretok_type(const JsonValue* root, const HostModel& m) {
+    const JsonValue* pt = root->get("pre_tokenizer");
+    const std::string ptype = type_name_or_null(pt);
+    if (m.norm == NORM_CHAIN) {
         if (ptype != "Whitespace" && ptype != "WhitespaceSplit" && ptype != "BertPreTokenizer") throw Unsupported(chain_refusal(m, "pre_tokenizer '" + ptype + "'"));
     }
-    if (m.norm == NORM_NFKC) {                                         // (asked of the file before the pre-tokenizers' own refusals of a normalizer)
-        const JsonValue* pt = root->get("pre_tokenizer");
-        const std::string ptype = (pt && pt->is_object()) ? pt->get_str("type") : "null";
+    if (m.norm == NORM_NFKC) {
         if (ptype != "Metaspace") throw Unsupported("normalizer: type 'NFKC' is outside the hot path");
         if (!m.nfkc_refusal.empty()) throw Unsupported(m.nfkc_refusal);
         if (!pt->get_bool("split", true))
             throw Unsupported("pre_tokenizer: Metaspace(split = false) behind NFKC is outside the hot path (only split = true is on it behind the normalizer)");
     }
-    m.pretok = parse_pretok(root->get("pre_tokenizer"), m);
-    if (m.pretok == PT_LLAMA3 && m.split_rule.letters == 2) {         // the case classes of the case-split letter alternatives
-        std::vector<uint8_t> flat(0x110000, 0);
-        for (const UcRun& r : kUcCaseRuns)
-            for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
-        two_stage(flat, &m.ucc_stage1, &m.ucc_stage2);
-    }
+}
+
+// ---- 5. what follows from the pre-tokenizer's kind (4. is parse_pretok, above) ----
+// reads pretok, split_rule, norm, nfc_lower; writes the second class table ucc_stage1 / 2.  Its three refusals stand behind all of
+// parse_pretok's and in front of the post-processor's and the model's.
+void finish_pretok(HostModel& m) {
+    // the case classes of the case-split letter alternatives
+    if (m.pretok == PT_LLAMA3 && m.split_rule.letters == 2) two_stage(flat_of(kUcCaseRuns), &m.ucc_stage1, &m.ucc_stage2);
     if (m.pretok == PT_SPLIT_CHAIN) {                                  // \p{P}, \p{S}, \p{M} for the chain's third pattern: the same slot, the rule's second class table
         if (m.norm != NORM_NONE && m.norm != NORM_NFC)
             throw Unsupported("pre_tokenizer: the chained Split behind a normalizer other than NFC");
-        std::vector<uint8_t> flat(0x110000, 0);
-        for (const UcRun& r : kUcPsmRuns)
-            for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
-        two_stage(flat, &m.ucc_stage1, &m.ucc_stage2);
+        two_stage(flat_of(kUcPsmRuns), &m.ucc_stage1, &m.ucc_stage2);
     }
-
     if (m.pretok == PT_DIGITS_GPT2 && m.norm != NORM_NONE && m.norm != NORM_NFC)
         throw Unsupported("pre_tokenizer: Sequence[Digits, ByteLevel] behind a normalizer other than NFC");
-    // (the normalizer section looked at the Split's pattern alone; everything else of the CLIP pre-tokenizer was parse_pretok's to accept)
+    // (parse_nfc_sequence looked at the Split's pattern alone; everything else of the CLIP pre-tokenizer was parse_pretok's to accept)
     if (m.nfc_lower && m.pretok != PT_CLIP)
         throw Unsupported("normalizer: NFC inside a longer Sequence is outside the hot path (only NFC alone, or Sequence[NFC], is on it; and "
                           "Sequence[NFC, Replace(Regex '\\s+' -> ' '), Lowercase] in front of the CLIP pre-tokenizer, which this file's is not)");
+}
 
-    // ---- post-processor: offset trimming + the special tokens it puts around a single sequence ----
-    {
-        std::function<void(const JsonValue*)> apply = [&](const JsonValue* pp) {
-            if (!pp || pp->is_null()) return;
-            std::string t = pp->get_str("type");
-            if (t == "BertProcessing" || t == "RobertaProcessing") {
-                // PostProcessorWrapper is an untagged enum that tries Roberta before Bert and "serde does not validate tags"
-                // (processors/mod.rs:19-23): with both of Roberta's flags present it is a RobertaProcessing whatever `type` says, else Bert
-                const JsonValue* a = pp->get("trim_offsets");
-                const JsonValue* b = pp->get("add_prefix_space");
-                t = (a && a->is_bool() && b && b->is_bool()) ? "RobertaProcessing" : "BertProcessing";
-            }
-            if (t == "ByteLevel" || t == "RobertaProcessing") {
-                m.trim_offsets = pp->get_bool("trim_offsets", true);
-                m.pp_add_prefix_space = pp->get_bool("add_prefix_space", true);
-            }
-            if (t == "ByteLevel") return;
-            if (t == "BertProcessing" || t == "RobertaProcessing") {      // [cls] A [sep]   (processors/bert.rs:51-120, roberta.rs)
-                const JsonValue* cls = pp->get("cls");
-                const JsonValue* sep = pp->get("sep");
-                if (!cls || !sep || !cls->is_array() || !sep->is_array() || cls->arr.size() != 2 || sep->arr.size() != 2)
-                    throw Invalid("tokenizer.json: bad cls/sep in post_processor");
-                m.pp_prefix.insert(m.pp_prefix.begin(), (uint32_t)cls->arr[1]->num);
-                m.pp_suffix.push_back((uint32_t)sep->arr[1]->num);
-                m.pp_prefix_ty.insert(m.pp_prefix_ty.begin(), (uint8_t)0);
-                m.pp_suffix_ty.push_back((uint8_t)0);
-                if (m.pp_single_typed) m.pp_unsupported = "a TemplateProcessing with type ids combined with another post-processor";
-                if (!m.pp_pair.empty()) m.pp_pair_unsupported = "two post-processors that add special tokens";
-                const uint32_t c = (uint32_t)cls->arr[1]->num, e = (uint32_t)sep->arr[1]->num;
-                if (t == "BertProcessing")         // [CLS] A [SEP] : 0   B [SEP] : 1          (processors/bert.rs:121-150)
-                    m.pp_pair = {{2, c, 0}, {0, 0, 0}, {2, e, 0}, {1, 0, 1}, {2, e, 1}};
-                else                               // <s> A </s> </s> B </s>, all type 0        (processors/roberta.rs)
-                    m.pp_roberta = true, m.pp_pair_plain = {{0, 0, 0}, {1, 0, 0}}, m.pp_pair = {{2, c, 0}, {0, 0, 0}, {2, e, 0}, {2, e, 0}, {1, 0, 0}, {2, e, 0}};
-                return;
-            }
-            if (t == "TemplateProcessing") {                               // processors/template.rs:544-590, `single` template
-                const JsonValue* single = pp->get("single");
-                const JsonValue* sp = pp->get("special_tokens");
-                if (!single || !single->is_array()) throw Invalid("tokenizer.json: TemplateProcessing without `single`");
-                std::vector<uint32_t> pre, post;
-                std::vector<uint8_t> pre_ty, post_ty;
-                double seq_ty = 0, max_ty = 0;
-                int n_seq = 0;
-                // (a single template that is not "ids around sequence A" is refused when a single sequence is encoded with special tokens --
-                // the pair template below is parsed regardless)
-                for (auto& piece : single->arr) {
-                    if (const JsonValue* sq = piece->get("Sequence")) {
-                        if (sq->get_str("id") != "A") m.pp_unsupported = "TemplateProcessing single template refers to sequence B";
-                        seq_ty = sq->get_num("type_id", 0);
-                        max_ty = std::max(max_ty, seq_ty);
-                        ++n_seq;
-                    } else if (const JsonValue* st = piece->get("SpecialToken")) {
-                        std::string name = st->get_str("id");
-                        const JsonValue* def = sp ? sp->get(name.c_str()) : nullptr;
-                        const JsonValue* ids = def ? def->get("ids") : nullptr;
-                        if (!ids || !ids->is_array()) throw Invalid("tokenizer.json: TemplateProcessing special token '" + name + "' is not defined");
-                        const double ty = st->get_num("type_id", 0);
-                        max_ty = std::max(max_ty, ty);
-                        for (auto& x : ids->arr) { (n_seq ? post : pre).push_back((uint32_t)x->num); (n_seq ? post_ty : pre_ty).push_back((uint8_t)ty); }
-                    } else throw Invalid("tokenizer.json: bad TemplateProcessing piece");
-                }
-                if (n_seq != 1 && m.pp_unsupported.empty()) m.pp_unsupported = "TemplateProcessing single template must contain sequence A exactly once";
-                if (max_ty > 255 && m.pp_unsupported.empty()) m.pp_unsupported = "TemplateProcessing type id above 255";
-                if (max_ty > 0 && m.pp_unsupported.empty()) {
-                    // (a second post-processor would see -- and a second template overwrite -- these type ids)
-                    if (!m.pp_prefix.empty() || !m.pp_suffix.empty() || m.pp_single_typed) m.pp_unsupported = "a TemplateProcessing with type ids combined with another post-processor";
-                    else m.pp_single_typed = true, m.pp_seq_ty = (uint32_t)seq_ty;
-                } else if (m.pp_single_typed && m.pp_unsupported.empty()) {
-                    m.pp_unsupported = "a TemplateProcessing with type ids combined with another post-processor";
-                }
-                if (m.pp_unsupported.empty()) {
-                    m.pp_prefix.insert(m.pp_prefix.begin(), pre.begin(), pre.end());
-                    m.pp_suffix.insert(m.pp_suffix.end(), post.begin(), post.end());
-                    m.pp_prefix_ty.insert(m.pp_prefix_ty.begin(), pre_ty.begin(), pre_ty.end());
-                    m.pp_suffix_ty.insert(m.pp_suffix_ty.end(), post_ty.begin(), post_ty.end());
-                } else {
-                    m.pp_single_typed = false;
-                    m.pp_single_refused = true;           // (sequence A twice, or typed, comes out that way without special tokens too)
-                }
-                // the `pair` template (processors/template.rs:544-590): any order of A, B and special tokens, each with its type id
-                if (!m.pp_pair.empty()) m.pp_pair_unsupported = "two post-processors that add special tokens";
-                const JsonValue* pair = pp->get("pair");
-                if (!pair || !pair->is_array()) { m.pp_pair_unsupported = "TemplateProcessing without a `pair` template"; return; }
-                int na = 0, nb = 0;
-                for (auto& piece : pair->arr) {
-                    if (const JsonValue* sq = piece->get("Sequence")) {
-                        const bool is_a = sq->get_str("id") == "A";
-                        (is_a ? na : nb)++;
-                        m.pp_pair.push_back({is_a ? 0u : 1u, 0u, (uint32_t)sq->get_num("type_id", 0)});
-                    } else if (const JsonValue* st = piece->get("SpecialToken")) {
-                        std::string name = st->get_str("id");
-                        const JsonValue* def = sp ? sp->get(name.c_str()) : nullptr;
-                        const JsonValue* ids = def ? def->get("ids") : nullptr;
-                        if (!ids || !ids->is_array()) throw Invalid("tokenizer.json: TemplateProcessing special token '" + name + "' is not defined");
-                        for (auto& x : ids->arr) m.pp_pair.push_back({2u, (uint32_t)x->num, (uint32_t)st->get_num("type_id", 0)});
-                    } else throw Invalid("tokenizer.json: bad TemplateProcessing piece");
-                }
-                if (na != 1 || nb != 1) m.pp_pair_unsupported = "TemplateProcessing pair template must contain A and B exactly once each";
-                m.pp_pair_plain.clear();
-                for (const HostModel::TplPiece& q : m.pp_pair)
-                    if (q.kind != 2u) m.pp_pair_plain.push_back(q);
-                if (m.pp_pair.size() > 64) m.pp_pair_unsupported = "TemplateProcessing pair template with more than 64 pieces";
-                return;
-            }
-            if (t == "Sequence") {                                         // processors/sequence.rs: applied in order
-                const JsonValue* ps = pp->get("processors");
-                if (ps && ps->is_array())
-                    for (auto& q : ps->arr) apply(q.get());
-                return;
-            }
-            m.pp_unsupported = "post_processor type '" + t + "' is outside the hot path";
-        };
-        apply(root->get("post_processor"));
-        for (size_t k = 0; k < m.pp_prefix.size(); ++k) m.pp_single.push_back({2u, m.pp_prefix[k], k < m.pp_prefix_ty.size() ? (uint32_t)m.pp_prefix_ty[k] : 0u});
-        m.pp_single.push_back({0u, 0u, m.pp_single_typed ? m.pp_seq_ty : 0u});
-        for (size_t k = 0; k < m.pp_suffix.size(); ++k) m.pp_single.push_back({2u, m.pp_suffix[k], k < m.pp_suffix_ty.size() ? (uint32_t)m.pp_suffix_ty[k] : 0u});
-        m.pp_single_plain = {{0u, 0u, m.pp_single_typed ? m.pp_seq_ty : 0u}};
+// ---- 6. post-processor: offset trimming + the special tokens it puts around a single sequence and a pair ----
+// the ids a template's SpecialToken piece stands for
+const JsonValue* template_special_ids(const JsonValue* special_tokens, const std::string& name) {
+    const JsonValue* def = special_tokens ? special_tokens->get(name.c_str()) : nullptr;
+    const JsonValue* ids = def ? def->get("ids") : nullptr;
+    if (!ids || !ids->is_array()) throw Invalid("tokenizer.json: TemplateProcessing special token '" + name + "' is not defined");
+    return ids;
+}
+
+// [cls] A [sep]   (processors/bert.rs:51-120, roberta.rs); t: which of the two the untagged enum makes of the section
+void apply_bert_roberta(const JsonValue* pp, const std::string& t, HostModel& m) {
+    const JsonValue* cls = pp->get("cls");
+    const JsonValue* sep = pp->get("sep");
+    if (!cls || !sep || !cls->is_array() || !sep->is_array() || cls->arr.size() != 2 || sep->arr.size() != 2)
+        throw Invalid("tokenizer.json: bad cls/sep in post_processor");
+    m.pp_prefix.insert(m.pp_prefix.begin(), (uint32_t)cls->arr[1]->num);
+    m.pp_suffix.push_back((uint32_t)sep->arr[1]->num);
+    m.pp_prefix_ty.insert(m.pp_prefix_ty.begin(), (uint8_t)0);
+    m.pp_suffix_ty.push_back((uint8_t)0);
+    if (m.pp_single_typed) m.pp_unsupported = "a TemplateProcessing with type ids combined with another post-processor";
+    if (!m.pp_pair.empty()) m.pp_pair_unsupported = "two post-processors that add special tokens";
+    const uint32_t c = (uint32_t)cls->arr[1]->num, e = (uint32_t)sep->arr[1]->num;
+    if (t == "BertProcessing")         // [CLS] A [SEP] : 0   B [SEP] : 1          (processors/bert.rs:121-150)
+        m.pp_pair = {{2, c, 0}, {0, 0, 0}, {2, e, 0}, {1, 0, 1}, {2, e, 1}};
+    else                               // <s> A </s> </s> B </s>, all type 0        (processors/roberta.rs)
+        m.pp_roberta = true, m.pp_pair_plain = {{0, 0, 0}, {1, 0, 0}}, m.pp_pair = {{2, c, 0}, {0, 0, 0}, {2, e, 0}, {2, e, 0}, {1, 0, 0}, {2, e, 0}};
+}
+
+// TemplateProcessing's `single` template (processors/template.rs:544-590).  One that is not "ids around sequence A" is refused when a
+// single sequence is encoded with special tokens (pp_unsupported) -- the pair template is parsed regardless
+void apply_template_single(const JsonValue* pp, const JsonValue* sp, HostModel& m) {
+    const JsonValue* single = pp->get("single");
+    if (!single || !single->is_array()) throw Invalid("tokenizer.json: TemplateProcessing without `single`");
+    std::vector<uint32_t> pre, post;
+    std::vector<uint8_t> pre_ty, post_ty;
+    double seq_ty = 0, max_ty = 0;
+    int n_seq = 0;
+    for (auto& piece : single->arr) {
+        if (const JsonValue* sq = piece->get("Sequence")) {
+            if (sq->get_str("id") != "A") m.pp_unsupported = "TemplateProcessing single template refers to sequence B";
+            seq_ty = sq->get_num("type_id", 0);
+            max_ty = std::max(max_ty, seq_ty);
+            ++n_seq;
+        } else if (const JsonValue* st = piece->get("SpecialToken")) {
+            const JsonValue* ids = template_special_ids(sp, st->get_str("id"));
+            const double ty = st->get_num("type_id", 0);
+            max_ty = std::max(max_ty, ty);
+            for (auto& x : ids->arr) { (n_seq ? post : pre).push_back((uint32_t)x->num); (n_seq ? post_ty : pre_ty).push_back((uint8_t)ty); }
+        } else throw Invalid("tokenizer.json: bad TemplateProcessing piece");
     }
+    if (n_seq != 1 && m.pp_unsupported.empty()) m.pp_unsupported = "TemplateProcessing single template must contain sequence A exactly once";
+    if (max_ty > 255 && m.pp_unsupported.empty()) m.pp_unsupported = "TemplateProcessing type id above 255";
+    if (max_ty > 0 && m.pp_unsupported.empty()) {
+        // (a second post-processor would see -- and a second template overwrite -- these type ids)
+        if (!m.pp_prefix.empty() || !m.pp_suffix.empty() || m.pp_single_typed) m.pp_unsupported = "a TemplateProcessing with type ids combined with another post-processor";
+        else m.pp_single_typed = true, m.pp_seq_ty = (uint32_t)seq_ty;
+    } else if (m.pp_single_typed && m.pp_unsupported.empty()) {
+        m.pp_unsupported = "a TemplateProcessing with type ids combined with another post-processor";
+    }
+    if (m.pp_unsupported.empty()) {
+        m.pp_prefix.insert(m.pp_prefix.begin(), pre.begin(), pre.end());
+        m.pp_suffix.insert(m.pp_suffix.end(), post.begin(), post.end());
+        m.pp_prefix_ty.insert(m.pp_prefix_ty.begin(), pre_ty.begin(), pre_ty.end());
+        m.pp_suffix_ty.insert(m.pp_suffix_ty.end(), post_ty.begin(), post_ty.end());
+    } else {
+        m.pp_single_typed = false;
+        m.pp_single_refused = true;           // (sequence A twice, or typed, comes out that way without special tokens too)
+    }
+}
 
-    // ---- added tokens ----
+// the `pair` template (processors/template.rs:544-590): any order of A, B and special tokens, each with its type id
+void apply_template_pair(const JsonValue* pp, const JsonValue* sp, HostModel& m) {
+    if (!m.pp_pair.empty()) m.pp_pair_unsupported = "two post-processors that add special tokens";
+    const JsonValue* pair = pp->get("pair");
+    if (!pair || !pair->is_array()) { m.pp_pair_unsupported = "TemplateProcessing without a `pair` template"; return; }
+    int na = 0, nb = 0;
+    for (auto& piece : pair->arr) {
+        if (const JsonValue* sq = piece->get("Sequence")) {
+            const bool is_a = sq->get_str("id") == "A";
+            (is_a ? na : nb)++;
+            m.pp_pair.push_back({is_a ? 0u : 1u, 0u, (uint32_t)sq->get_num("type_id", 0)});
+        } else if (const JsonValue* st = piece->get("SpecialToken")) {
+            const JsonValue* ids = template_special_ids(sp, st->get_str("id"));
+            for (auto& x : ids->arr) m.pp_pair.push_back({2u, (uint32_t)x->num, (uint32_t)st->get_num("type_id", 0)});
+        } else throw Invalid("tokenizer.json: bad TemplateProcessing piece");
+    }
+    if (na != 1 || nb != 1) m.pp_pair_unsupported = "TemplateProcessing pair template must contain A and B exactly once each";
+    m.pp_pair_plain.clear();
+    for (const HostModel::TplPiece& q : m.pp_pair)
+        if (q.kind != 2u) m.pp_pair_plain.push_back(q);
+    if (m.pp_pair.size() > 64) m.pp_pair_unsupported = "TemplateProcessing pair template with more than 64 pieces";
+}
+
+// one post-processor section; a Sequence applies its members in order (processors/sequence.rs)
+void apply_post_processor(const JsonValue* pp, HostModel& m) {
+    if (!pp || pp->is_null()) return;
+    std::string t = pp->get_str("type");
+    if (t == "BertProcessing" || t == "RobertaProcessing") {
+        // PostProcessorWrapper is an untagged enum that tries Roberta before Bert and "serde does not validate tags"
+        // (processors/mod.rs:19-23): with both of Roberta's flags present it is a RobertaProcessing whatever `type` says, else Bert
+        const JsonValue* a = pp->get("trim_offsets");
+        const JsonValue* b = pp->get("add_prefix_space");
+        t = (a && a->is_bool() && b && b->is_bool()) ? "RobertaProcessing" : "BertProcessing";
+    }
+    if (t == "ByteLevel" || t == "RobertaProcessing") {
+        m.trim_offsets = pp->get_bool("trim_offsets", true);
+        m.pp_add_prefix_space = pp->get_bool("add_prefix_space", true);
+    }
+    if (t == "ByteLevel") return;
+    if (t == "BertProcessing" || t == "RobertaProcessing") return apply_bert_roberta(pp, t, m);
+    if (t == "TemplateProcessing") {
+        const JsonValue* sp = pp->get("special_tokens");
+        apply_template_single(pp, sp, m);
+        apply_template_pair(pp, sp, m);
+        return;
+    }
+    if (t == "Sequence") {
+        if (const JsonValue* ps = members_of(pp, "processors"))
+            for (auto& q : ps->arr) apply_post_processor(q.get(), m);
+        return;
+    }
+    m.pp_unsupported = "post_processor type '" + t + "' is outside the hot path";
+}
+
+// reads "post_processor"; writes trim_offsets, pp_*.  Most of what it cannot take is NOTED (pp_unsupported, pp_pair_unsupported) and
+// refused by the encode call that needs it; read_vocab's trim-offsets check relies on trim_offsets being known here.
+void parse_post_processor(const JsonValue* root, HostModel& m) {
+    apply_post_processor(root->get("post_processor"), m);
+    for (size_t k = 0; k < m.pp_prefix.size(); ++k) m.pp_single.push_back({2u, m.pp_prefix[k], k < m.pp_prefix_ty.size() ? (uint32_t)m.pp_prefix_ty[k] : 0u});
+    m.pp_single.push_back({0u, 0u, m.pp_single_typed ? m.pp_seq_ty : 0u});
+    for (size_t k = 0; k < m.pp_suffix.size(); ++k) m.pp_single.push_back({2u, m.pp_suffix[k], k < m.pp_suffix_ty.size() ? (uint32_t)m.pp_suffix_ty[k] : 0u});
+    m.pp_single_plain = {{0u, 0u, m.pp_single_typed ? m.pp_seq_ty : 0u}};
+}
+
+// ---- 7. added tokens ----
+// reads "added_tokens"; writes added_tokens as the file has them (assign_added_token_ids gives them the reference's ids)
+void parse_added_tokens(const JsonValue* root, HostModel& m) {
     const JsonValue* at = root->get("added_tokens");
-    if (at && at->is_array()) {
-        for (auto& e : at->arr) {
-            AddedToken a;
-            a.content = e->get_str("content");
-            a.id = (uint32_t)e->get_num("id", 0);
-            if (e->get_num("id", 0) < 0 || a.id >= (1u << 24)) throw Unsupported("added token id beyond 2^24");
-            a.special = e->get_bool("special", false);
-            a.single_word = e->get_bool("single_word", false);
-            a.lstrip = e->get_bool("lstrip", false);
-            a.rstrip = e->get_bool("rstrip", false);
-            a.normalized = e->get_bool("normalized", false);
-            m.added_tokens.push_back(std::move(a));
-        }
+    if (!at || !at->is_array()) return;
+    for (auto& e : at->arr) {
+        AddedToken a;
+        a.content = e->get_str("content");
+        a.id = (uint32_t)e->get_num("id", 0);
+        if (e->get_num("id", 0) < 0 || a.id >= (1u << 24)) throw Unsupported("added token id beyond 2^24");
+        a.special = e->get_bool("special", false);
+        a.single_word = e->get_bool("single_word", false);
+        a.lstrip = e->get_bool("lstrip", false);
+        a.rstrip = e->get_bool("rstrip", false);
+        a.normalized = e->get_bool("normalized", false);
+        m.added_tokens.push_back(std::move(a));
     }
+}
 
-    // ---- model ----
-    const JsonValue* model = root->get("model");
+// ---- 8. the model's type and vocabulary ----
+// a trimming post-processor (ByteLevel / RobertaProcessing) on a model that is not byte-level: process_offsets moves the offsets of every
+// token whose STRING starts or ends with whitespace or 'Ġ' (byte_level.rs:202-234).  The added tokens' raw slices can (k_token_meta
+// trims those); a vocabulary entry that could is outside the path
+void check_trim_offsets_vocab(const Vocab& v, HostModel& m) {
+    if (m.uc_stage1.empty()) build_unicode(m);
+    for (auto& kv : v.id) {
+        const uint8_t* b = (const uint8_t*)kv.first.data();
+        const size_t n = kv.first.size();
+        if (!n) continue;
+        uint32_t c0 = 0, c1 = 0;
+        utf8_decode(b, n, &c0);
+        size_t q = n - 1;
+        while (q > 0 && (b[q] & 0xC0u) == 0x80u) --q;
+        utf8_decode(b + q, n - q, &c1);
+        auto trimmed = [&](uint32_t c) { return c == 0x120u || (uc_flags(m, c) & UC_RUST_WS); };
+        if (trimmed(c0) || trimmed(c1)) throw Unsupported("post_processor with trim_offsets on a vocabulary that is not byte-level and holds an entry with leading / trailing whitespace or 'Ġ' ('" + kv.first + "')");
+    }
+}
+
+// reads "model" (type, vocab), pretok, trim_offsets, byte_level; writes v (model, mtype, unigram, id, uni_pieces), vocab_size, uni_score,
+// uni_unk_score.  The pre-tokenizers that go with one model type alone refuse every other type HERE, in front of the vocabulary's own
+// refusals and long before the model's parser could say "outside the hot path" of a type it does not know.
+void read_vocab(const JsonValue* root, HostModel& m, Vocab& v) {
+    const JsonValue* model = v.model = root->get("model");
     if (!model || !model->is_object()) throw Invalid("tokenizer.json: missing model");
-    std::string mtype = model->get_str("type");
+    std::string& mtype = v.mtype = model->get_str("type");
     const JsonValue* vocab = model->get("vocab");
     if (mtype.empty()) {
         // legacy untagged models (models/mod.rs:71-136): BPE has merges, WordPiece has a prefix
@@ -1654,8 +1722,8 @@ HostModel HostModel::from_json(const char* json, size_t len) {
         else mtype = "WordLevel";
     }
     // Unigram keeps its vocabulary as an ARRAY of [piece, score], id = index (models/unigram/serialization.rs:13-30); every other model
-    // as an object piece -> id.  Both fill the same map `v` that added tokens, templates, padding and the decode tables read.
-    const bool unigram = mtype == "Unigram";
+    // as an object piece -> id.  Both fill the same map v.id
+    const bool unigram = v.unigram = mtype == "Unigram";
     if (m.pretok == PT_CLIP && mtype != "BPE")
         throw Unsupported("pre_tokenizer: the CLIP Split + ByteLevel in front of a " + mtype + " model (only in front of byte-level BPE with an end_of_word_suffix is it on the path)");
     if (m.pretok == PT_BLOOM && mtype != "BPE")
@@ -1664,8 +1732,6 @@ HostModel HostModel::from_json(const char* json, size_t len) {
         throw Unsupported("pre_tokenizer: Sequence[Digits, ByteLevel] in front of a " + mtype + " model (only in front of byte-level BPE is it on the path)");
     if (unigram ? !(vocab && vocab->is_array()) : !(vocab && vocab->is_object())) throw Invalid("tokenizer.json: model.vocab missing");
 
-    std::unordered_map<std::string, uint32_t> v;
-    std::vector<std::string> uni_pieces;      // Unigram: id -> piece, per index (id_to_token, unigram/model.rs:483-485)
     if (unigram) {
         // Unigram::from (unigram/model.rs:104-151): token_to_ids.insert in index order -- of two equal pieces the LATER id encodes --,
         // min_score over every entry (the shadowed and the unk piece included); scores are f64 as the reference's own JSON reader rounds them
@@ -1673,292 +1739,284 @@ HostModel HostModel::from_json(const char* json, size_t len) {
         const size_t n = vocab->arr.size();
         if (n == 0) throw Unsupported("model: Unigram with an empty vocab (EmptyVocabulary) is outside the hot path");
         if (n >= ((size_t)1 << 24)) throw Unsupported("token id beyond 2^24 (Unigram vocab of " + std::to_string(n) + " pieces)");
-        v.reserve(n * 2);
-        uni_pieces.reserve(n);
+        v.id.reserve(n * 2);
+        v.uni_pieces.reserve(n);
         m.uni_score.reserve(n);
         double min_score = std::numeric_limits<double>::infinity();
         for (size_t i = 0; i < n; ++i) {
             const JsonValue* e = vocab->arr[i].get();
             if (!e->is_array() || e->arr.size() != 2 || !e->arr[0]->is_string() || !e->arr[1]->is_number())
                 throw Invalid("tokenizer.json: Unigram vocab entry " + std::to_string(i) + " is not [piece, score]");
-            v[e->arr[0]->str] = (uint32_t)i;
-            uni_pieces.push_back(e->arr[0]->str);
+            v.id[e->arr[0]->str] = (uint32_t)i;
+            v.uni_pieces.push_back(e->arr[0]->str);
             const double score = serde_json_f64(e->arr[1]->str);
             m.uni_score.push_back(score);
             if (score < min_score) min_score = score;
         }
         m.uni_unk_score = min_score - 10.0;      // K_UNK_PENALTY, unigram/model.rs:277
     } else {
-        v.reserve(vocab->obj.size() * 2);
+        v.id.reserve(vocab->obj.size() * 2);
         for (auto& kv : vocab->obj) {
             if (!kv.second->is_number()) throw Invalid("tokenizer.json: vocab id is not a number");
-            v[kv.first] = (uint32_t)kv.second->num;   // duplicate keys: last wins, like serde's map
+            v.id[kv.first] = (uint32_t)kv.second->num;   // duplicate keys: last wins, like serde's map
             // the pair hashes (tables.hpp) multiply 24-bit operands and the result rows keep ids in 24 bits: larger ids would
             // collide for every seed, so they are refused here with the reason instead of failing table construction
             if (kv.second->num < 0 || kv.second->num >= (double)(1u << 24)) throw Unsupported("token id beyond 2^24 (vocab entry '" + kv.first + "')");
         }
     }
-    m.vocab_size = unigram ? (uint32_t)uni_pieces.size() : (uint32_t)v.size();      // (get_vocab_size: the array's length, duplicates and all, unigram/model.rs:439-441)
-    if (m.trim_offsets && !m.byte_level) {
-        // a trimming post-processor (ByteLevel / RobertaProcessing) on a model that is not byte-level: process_offsets moves the offsets
-        // of every token whose STRING starts or ends with whitespace or 'Ġ' (byte_level.rs:202-234).  The added tokens' raw slices
-        // can (k_token_meta trims those); a vocabulary entry that could is outside the path
-        if (m.uc_stage1.empty()) build_unicode(m);
-        for (auto& kv : v) {
-            const uint8_t* b = (const uint8_t*)kv.first.data();
-            const size_t n = kv.first.size();
-            if (!n) continue;
-            uint32_t c0 = 0, c1 = 0;
-            utf8_decode(b, n, &c0);
-            size_t q = n - 1;
-            while (q > 0 && (b[q] & 0xC0u) == 0x80u) --q;
-            utf8_decode(b + q, n - q, &c1);
-            auto trimmed = [&](uint32_t c) { return c == 0x120u || (c < 0x110000u && (m.uc_stage2[((size_t)m.uc_stage1[c >> 8] << 8) | (c & 255u)] & UC_RUST_WS)); };
-            if (trimmed(c0) || trimmed(c1)) throw Unsupported("post_processor with trim_offsets on a vocabulary that is not byte-level and holds an entry with leading / trailing whitespace or 'Ġ' ('" + kv.first + "')");
+    m.vocab_size = unigram ? (uint32_t)v.uni_pieces.size() : (uint32_t)v.id.size();      // (get_vocab_size: the array's length, duplicates and all, unigram/model.rs:439-441)
+    if (m.trim_offsets && !m.byte_level) check_trim_offsets_vocab(v, m);
+}
+
+// ---- 9. the ids of the added tokens ----
+// The ids the reference gives the added tokens are not the ones in the file: deserialisation hands them, in file order, to
+// AddedVocabulary::add_tokens (serialization.rs:153-167 -- it only WARNS when the outcome differs from the file), which gives a
+// token whose content the model knows the model's id and every other one the next free id from the model's vocabulary size on; a
+// content seen twice keeps its first id and its last properties (added_vocabulary.rs:272-360).  Files the library wrote agree with
+// that already.
+// reads v.id, vocab_size; rewrites added_tokens (build_decode_tables and build_added_patterns read the result)
+void assign_added_token_ids(const Vocab& v, HostModel& m) {
+    std::unordered_map<std::string, size_t> seen;
+    std::vector<AddedToken> kept;
+    uint32_t next_id = m.vocab_size;
+    for (AddedToken& a : m.added_tokens) {
+        if (a.content.empty()) continue;
+        auto it = seen.find(a.content);
+        if (it != seen.end()) {
+            AddedToken& old = kept[it->second];
+            a.id = old.id;
+            old = a;
+            continue;
         }
+        auto vit = v.id.find(a.content);
+        a.id = vit != v.id.end() ? vit->second : next_id++;
+        if (a.id >= (1u << 24)) throw Unsupported("added token id beyond 2^24");
+        seen[a.content] = kept.size();
+        kept.push_back(a);
     }
+    m.added_tokens = std::move(kept);
+}
 
-    // The ids the reference gives the added tokens are not the ones in the file: deserialisation hands them, in file order, to
-    // AddedVocabulary::add_tokens (serialization.rs:153-167 -- it only WARNS when the outcome differs from the file), which gives a
-    // token whose content the model knows the model's id and every other one the next free id from the model's vocabulary size on; a
-    // content seen twice keeps its first id and its last properties (added_vocabulary.rs:272-360).  Files the library wrote agree with
-    // that already.
-    {
-        std::unordered_map<std::string, size_t> seen;
-        std::vector<AddedToken> kept;
-        uint32_t next_id = m.vocab_size;
-        for (AddedToken& a : m.added_tokens) {
-            if (a.content.empty()) continue;
-            auto it = seen.find(a.content);
-            if (it != seen.end()) {
-                AddedToken& old = kept[it->second];
-                a.id = old.id;
-                old = a;
-                continue;
-            }
-            auto vit = v.find(a.content);
-            a.id = vit != v.end() ? vit->second : next_id++;
-            if (a.id >= (1u << 24)) throw Unsupported("added token id beyond 2^24");
-            seen[a.content] = kept.size();
-            kept.push_back(a);
-        }
-        m.added_tokens = std::move(kept);
-    }
-
-    uint32_t b2c[256];
-    build_bytes_char(b2c);
-    std::unordered_map<uint32_t, uint8_t> c2b;
-    for (int b = 0; b < 256; ++b) c2b[b2c[b]] = (uint8_t)b;
-
-    // raw-byte view of the vocab
-    m.raw_tokens.reserve(v.size());
-    m.raw_ids.reserve(v.size());
-    for (auto& kv : v) {
+// ---- 10. the raw-byte view of the vocabulary ----
+// reads v.id IN ITS ITERATION ORDER, byte_level; writes raw_tokens / raw_ids -- the order every table below is laid out in
+void build_raw_tokens(const Vocab& v, HostModel& m) {
+    m.raw_tokens.reserve(v.id.size());
+    m.raw_ids.reserve(v.id.size());
+    for (auto& kv : v.id) {
         if (m.byte_level) {
             std::string raw;
-            if (!bytelevel_to_raw(kv.first, c2b, &raw)) continue;   // not producible from bytes
+            if (!bytelevel_to_raw(kv.first, v.c2b, &raw)) continue;   // not producible from bytes
             m.raw_tokens.push_back(std::move(raw));
         } else {
             m.raw_tokens.push_back(kv.first);
         }
         m.raw_ids.push_back(kv.second);
     }
-    const size_t n_raw_plain = m.raw_tokens.size();
+}
 
-    build_decode_tables(m, root.get(), v, c2b, unigram ? &uni_pieces : nullptr);
-
-    auto opt_str = [&](const char* key, std::string* out) -> bool {
-        const JsonValue* x = model->get(key);
-        if (x && x->is_string()) { *out = x->str; return true; }
-        return false;
-    };
-
-    if (mtype == "BPE") {
-        m.model = MODEL_BPE;
-        const JsonValue* dr = model->get("dropout");
-        if (dr && dr->is_number() && dr->num != 0.0) throw Unsupported("BPE dropout needs the reference's RNG (bpe/word.rs:181)");
-        opt_str("continuing_subword_prefix", &m.bpe_prefix);
-        opt_str("end_of_word_suffix", &m.bpe_suffix);
-        m.fuse_unk = model->get_bool("fuse_unk", false);
-        m.byte_fallback = model->get_bool("byte_fallback", false);
-        m.ignore_merges = model->get_bool("ignore_merges", false);
-        if (opt_str("unk_token", &m.unk_token)) {
-            m.unk_configured = true;
-            auto it = v.find(m.unk_token);
-            if (it != v.end()) { m.has_unk = true; m.unk_id = it->second; }
+// ---- 12. the model's options (11. is build_decode_tables, above) ----
+// BPE over characters (BPE::merge_word, bpe/model.rs:465-550): a char's initial symbol is the vocabulary entry of the char with the
+// affixes its place in the word glues on.  Every (char, affix combination) the vocabulary knows goes into one direct indexed table;
+// with byte_fallback, byte_id[] holds the <0xXX> tokens
+void build_char_ids(const Vocab& v, HostModel& m) {
+    if (m.bpe_prefix.size() > 31 || m.bpe_suffix.size() > 31) throw Unsupported("BPE continuing_subword_prefix / end_of_word_suffix longer than 31 bytes");
+    m.char_id.assign(CHAR_TABLE_WORDS, CHAR_NONE);
+    for (auto& kv : v.id) {
+        const std::string& e = kv.first;
+        for (uint32_t var = 0; var < 4; ++var) {
+            if ((var & 1u) && m.bpe_prefix.empty()) continue;
+            if ((var & 2u) && m.bpe_suffix.empty()) continue;
+            size_t a = 0, b = e.size();
+            if (var & 1u) { if (e.compare(0, m.bpe_prefix.size(), m.bpe_prefix) != 0 || e.size() < m.bpe_prefix.size()) continue; a = m.bpe_prefix.size(); }
+            if (var & 2u) { if (b - a < m.bpe_suffix.size() || e.compare(b - m.bpe_suffix.size(), m.bpe_suffix.size(), m.bpe_suffix) != 0) continue; b -= m.bpe_suffix.size(); }
+            if (b <= a || b - a > 4) continue;
+            uint32_t cp = 0;
+            const size_t l = utf8_decode((const uint8_t*)e.data() + a, b - a, &cp);
+            if (l != b - a || cp >= 0x110000u) continue;                  // exactly one char between the affixes
+            m.char_id[((size_t)cp << 2) | var] = kv.second;
         }
-        m.char_bpe = !m.byte_level;
-        if (m.byte_level && (!m.bpe_prefix.empty() || !m.bpe_suffix.empty()) && (m.pretok != PT_CLIP || !m.bpe_prefix.empty()))
-            throw Unsupported("byte-level BPE with continuing_subword_prefix / end_of_word_suffix (an end_of_word_suffix is on the path behind the CLIP "
-                              "pre-tokenizer alone, with no continuing_subword_prefix)");
-        if (m.byte_level && m.byte_fallback) throw Unsupported("byte-level BPE with byte_fallback");
-        if (m.pretok == PT_CLIP) {
-            if (m.bpe_suffix.empty()) throw Unsupported("pre_tokenizer: the CLIP Split + ByteLevel in front of a BPE without end_of_word_suffix is outside the hot path");
-            if (m.bpe_suffix.size() > 31) throw Unsupported("BPE continuing_subword_prefix / end_of_word_suffix longer than 31 bytes");
-            // (vocab.get(sequence) would look the text up without the suffix its entry carries: not built)
-            if (m.ignore_merges) throw Unsupported("byte-level BPE with end_of_word_suffix and ignore_merges");
-            m.byte_suffix = true;
-        }
-        if (m.char_bpe) {
-            // BPE over characters (BPE::merge_word, bpe/model.rs:465-550): a char's initial symbol is the vocabulary entry of the char with
-            // the affixes its place in the word glues on.  Every (char, affix combination) the vocabulary knows goes into one direct
-            // indexed table
-            if (m.bpe_prefix.size() > 31 || m.bpe_suffix.size() > 31) throw Unsupported("BPE continuing_subword_prefix / end_of_word_suffix longer than 31 bytes");
-            m.char_id.assign(CHAR_TABLE_WORDS, CHAR_NONE);
-            for (auto& kv : v) {
-                const std::string& e = kv.first;
-                for (uint32_t var = 0; var < 4; ++var) {
-                    if ((var & 1u) && m.bpe_prefix.empty()) continue;
-                    if ((var & 2u) && m.bpe_suffix.empty()) continue;
-                    size_t a = 0, b = e.size();
-                    if (var & 1u) { if (e.compare(0, m.bpe_prefix.size(), m.bpe_prefix) != 0 || e.size() < m.bpe_prefix.size()) continue; a = m.bpe_prefix.size(); }
-                    if (var & 2u) { if (b - a < m.bpe_suffix.size() || e.compare(b - m.bpe_suffix.size(), m.bpe_suffix.size(), m.bpe_suffix) != 0) continue; b -= m.bpe_suffix.size(); }
-                    if (b <= a || b - a > 4) continue;
-                    uint32_t cp = 0;
-                    const size_t l = utf8_decode((const uint8_t*)e.data() + a, b - a, &cp);
-                    if (l != b - a || cp >= 0x110000u) continue;                  // exactly one char between the affixes
-                    m.char_id[((size_t)cp << 2) | var] = kv.second;
-                }
-            }
-            for (int b = 0; b < 256; ++b) m.byte_id[b] = CHAR_NONE;
-            if (m.byte_fallback) {
-                // (merge_word glues the affixes on BEFORE it falls back to bytes, so they would be spelt out as <0xXX> tokens too --
-                // symbols the word has no bytes for; and a byte without its token sends the char on to the unk path behind symbols
-                // already added: both corners are refused)
-                if (!m.bpe_prefix.empty() || !m.bpe_suffix.empty()) throw Unsupported("BPE byte_fallback together with continuing_subword_prefix / end_of_word_suffix");
-                for (int b = 0; b < 256; ++b) {
-                    char code[8];
-                    snprintf(code, sizeof(code), "<0x%02X>", b);
-                    auto it = v.find(code);
-                    if (it == v.end()) throw Unsupported(std::string("BPE byte_fallback without the byte token ") + code);
-                    m.byte_id[b] = it->second;
-                }
-            }
-        }
-        // byte -> initial symbol id (bpe/model.rs:494-499 with the byte-level alphabet)
-        for (int b = 0; b < 256 && m.byte_level; ++b) {
-            std::string ch;
-            uint32_t cp = b2c[b];
-            if (cp < 0x80) ch.push_back((char)cp);
-            else { ch.push_back((char)(0xC0 | (cp >> 6))); ch.push_back((char)(0x80 | (cp & 0x3F))); }
-            auto it = v.find(ch);
-            if (it == v.end())
-                throw Unsupported("byte-level BPE vocab lacks a byte symbol (unk / byte_fallback / dropped-char paths, bpe/model.rs:501-541)" +
-                                  (m.byte_suffix ? ": '" + ch + "'" : std::string()));
-            m.byte_id[b] = it->second;
-            // (with all 256 chars and all 256 char + suffix entries no word ever needs the unk_token)
-            if (m.byte_suffix) {
-                it = v.find(ch + m.bpe_suffix);
-                if (it == v.end()) throw Unsupported("byte-level BPE with end_of_word_suffix: the vocab lacks '" + ch + m.bpe_suffix + "' (a byte's char with the suffix)");
-                m.byte_sfx_id[b] = it->second;
-            }
-        }
-        // merges (bpe/model.rs:252-275): rank = position, new_id = vocab[a+b]; duplicate pairs: last wins
-        const JsonValue* mg = model->get("merges");
-        if (!mg || !mg->is_array()) throw Invalid("tokenizer.json: BPE merges missing");
-        std::unordered_map<uint64_t, std::pair<uint32_t, uint32_t>> mm;
-        mm.reserve(mg->arr.size() * 2);
-        uint32_t rank = 0;
-        for (auto& e : mg->arr) {
-            std::string a, b;
-            if (e->is_array() && e->arr.size() == 2 && e->arr[0]->is_string() && e->arr[1]->is_string()) {
-                a = e->arr[0]->str; b = e->arr[1]->str;
-            } else if (e->is_string()) {     // legacy "a b" (bpe/serialization.rs:141-149)
-                size_t sp = e->str.find(' ');
-                if (sp == std::string::npos || e->str.find(' ', sp + 1) != std::string::npos)
-                    throw Invalid("tokenizer.json: bad legacy merge entry");
-                a = e->str.substr(0, sp); b = e->str.substr(sp + 1);
-            } else throw Invalid("tokenizer.json: bad merge entry");
-            // (new token = a + b minus the continuing_subword_prefix's LENGTH in bytes, whatever b starts with: BpeBuilder::build :246-271)
-            if (b.size() < m.bpe_prefix.size()) throw Invalid("tokenizer.json: a merge's right-hand token is shorter than continuing_subword_prefix");
-            auto ia = v.find(a), ib = v.find(b), in = v.find(a + b.substr(m.bpe_prefix.size()));
-            if (ia == v.end() || ib == v.end() || in == v.end())
-                throw Invalid("tokenizer.json: merge token out of vocabulary (MergeTokenOutOfVocabulary)");
-            // the "▁" front's unit split (PT_METASPACE without split): exact only if no merge joins a char other than "▁" to a symbol that
-            // starts with "▁" -- then no pair across a cut ever merges, and every unit runs its merges on its own (bpe/word.rs:162-250)
-            if (m.pretok == PT_METASPACE && !m.ms_split && m.char_bpe && b.compare(0, 3, kMetaspace) == 0 && !(a.size() >= 3 && a.compare(a.size() - 3, 3, kMetaspace) == 0))
-                throw Unsupported("pre_tokenizer: the merge ('" + a + "', '" + b + "') joins a char other than U+2581 to a U+2581: whole-piece BPE "
-                                  "(no split at U+2581) is outside the hot path for this vocabulary");
-            mm[((uint64_t)ia->second << 32) | ib->second] = {rank, in->second};
-            ++rank;
-        }
-        if (rank >= (1u << 20)) throw Unsupported("more than 2^20 merges");
-        m.n_merges = rank;
-        std::vector<MergeSlot> merges;
-        merges.reserve(mm.size());
-        for (auto& kv : mm) merges.push_back(MergeSlot{(uint32_t)(kv.first >> 32), (uint32_t)kv.first, kv.second.first, kv.second.second});
-        std::sort(merges.begin(), merges.end(), [](const MergeSlot& x, const MergeSlot& y) { return x.rank < y.rank; });
-        build_merge_table(m, merges);
-    } else if (mtype == "WordPiece") {
-        m.model = MODEL_WORDPIECE;
-        if (m.byte_level) throw Unsupported("WordPiece behind ByteLevel");
-        m.unk_token = model->get_str("unk_token", "[UNK]");
-        m.cont_prefix = model->get_str("continuing_subword_prefix", "##");
-        m.max_input_chars = (uint32_t)model->get_num("max_input_chars_per_word", 100);
-        auto it = v.find(m.unk_token);
-        if (it != v.end()) { m.has_unk = true; m.unk_id = it->second; }
-    } else if (mtype == "WordLevel") {
-        m.model = MODEL_WORDLEVEL;
-        if (m.byte_level) throw Unsupported("WordLevel behind ByteLevel");
-        m.unk_token = model->get_str("unk_token", "<unk>");
-        auto it = v.find(m.unk_token);
-        if (it != v.end()) { m.has_unk = true; m.unk_id = it->second; }
-    } else if (unigram) {
-        // Unigram (models/unigram/model.rs): a Viterbi search per pre-token over f64 scores (unigram_core.hpp, kernels/unigram.hip).  On the
-        // path behind Metaspace(split = true) alone: the front's other layouts cut a piece into units, and a comparison of prefix + score
-        // sums made on a unit alone can round differently from the reference's, made over the whole piece
-        m.model = MODEL_UNIGRAM;
-        if (m.pretok != PT_METASPACE) {
-            const JsonValue* pt = root->get("pre_tokenizer");
-            const std::string ptype = (pt && pt->is_object()) ? pt->get_str("type") : "null";
-            throw Unsupported("model: Unigram (a vocab of scored pieces) is on the path behind Metaspace(split = true) only; pre_tokenizer '" + ptype + "' is not");
-        }
-        if ((m.norm != NORM_NONE && m.norm != NORM_PRECOMPILED && m.norm != NORM_NFKC) || !m.ms_split)
-            throw Unsupported("model: Unigram (a vocab of scored pieces) over whole pieces -- Metaspace(split = false), or a null pre_tokenizer behind the U+2581 "
-                              "normalizers -- is outside the hot path: the front cuts such a piece into units, and the reference compares f64 sums of "
-                              "prefix + score over the whole piece, which a unit alone can round differently (only Metaspace(split = true) is on the path)");
-        const JsonValue* uk = model->get("unk_id");
-        if (uk && uk->is_number()) {
-            if (uk->num < 0 || uk->num >= (double)uni_pieces.size()) throw Unsupported("model: Unigram unk_id " + std::to_string((long long)uk->num) + " is beyond the vocab (UnkIdNotInVocabulary)");
-            m.has_unk = true;
-            m.unk_id = (uint32_t)uk->num;
-            m.unk_token = uni_pieces[m.unk_id];
-        }
-        m.byte_fallback = model->get_bool("byte_fallback", false);
-        for (int b = 0; b < 256; ++b) m.byte_id[b] = CHAR_NONE;
-        if (m.byte_fallback) {
-            // a run the vocabulary lacks becomes the <0xXX> tokens of its bytes only if ALL of them exist (unigram/model.rs:453-468: per
-            // run in the reference; every byte of valid UTF-8 but 0xC0, 0xC1, 0xF5.. can occur, so the flag asks for all 256 and a file
-            // that lacks one keeps its unk runs -- what the reference does for every run that holds such a byte; the others are refused)
-            int have = 0;
-            for (int b = 0; b < 256; ++b) {
-                char code[8];
-                snprintf(code, sizeof(code), "<0x%02X>", b);
-                auto it = v.find(code);
-                if (it != v.end()) { m.byte_id[b] = it->second; ++have; }
-            }
-            m.uni_bytes = have == 256;
-            if (have != 0 && have != 256)
-                throw Unsupported("model: Unigram byte_fallback with " + std::to_string(have) + " of the 256 <0xXX> pieces (all or none are on the path)");
-        }
-        if (v.count("")) throw Unsupported("model: Unigram vocab with an empty piece is outside the hot path");
-        // (the offsets of a byte-fallback run are put together from the result itself, kernels/unigram.hip k_unigram_run_offsets: no run may
-        // begin with the U+2581 that opens a pre-token, which holds when U+2581 is a piece and the unk piece does not begin with one)
-        if (m.uni_bytes && (!v.count(kMetaspace) || (m.has_unk && m.unk_token.compare(0, 3, kMetaspace) == 0)))
-            throw Unsupported("model: Unigram byte_fallback with a vocab that lacks the piece U+2581 (or whose unk piece begins with it) is outside the hot path");
-    } else {
-        throw Unsupported("model: type '" + mtype + "' is outside the hot path");
     }
+    for (int b = 0; b < 256; ++b) m.byte_id[b] = CHAR_NONE;
+    if (m.byte_fallback) {
+        // (merge_word glues the affixes on BEFORE it falls back to bytes, so they would be spelt out as <0xXX> tokens too --
+        // symbols the word has no bytes for; and a byte without its token sends the char on to the unk path behind symbols
+        // already added: both corners are refused)
+        if (!m.bpe_prefix.empty() || !m.bpe_suffix.empty()) throw Unsupported("BPE byte_fallback together with continuing_subword_prefix / end_of_word_suffix");
+        for (int b = 0; b < 256; ++b) {
+            std::string code;
+            const uint32_t* id = byte_token_id(v, b, &code);
+            if (!id) throw Unsupported("BPE byte_fallback without the byte token " + code);
+            m.byte_id[b] = *id;
+        }
+    }
+}
+
+// byte-level BPE: byte -> initial symbol id (bpe/model.rs:494-499 with the byte-level alphabet), and with an end_of_word_suffix the id of
+// (the byte's char + the suffix)
+void build_byte_ids(const Vocab& v, HostModel& m) {
+    for (int b = 0; b < 256; ++b) {
+        uint8_t u[4];
+        const std::string ch((const char*)u, nfc_utf8_put(u, v.b2c[b]));
+        auto it = v.id.find(ch);
+        if (it == v.id.end())
+            throw Unsupported("byte-level BPE vocab lacks a byte symbol (unk / byte_fallback / dropped-char paths, bpe/model.rs:501-541)" +
+                              (m.byte_suffix ? ": '" + ch + "'" : std::string()));
+        m.byte_id[b] = it->second;
+        // (with all 256 chars and all 256 char + suffix entries no word ever needs the unk_token)
+        if (m.byte_suffix) {
+            it = v.id.find(ch + m.bpe_suffix);
+            if (it == v.id.end()) throw Unsupported("byte-level BPE with end_of_word_suffix: the vocab lacks '" + ch + m.bpe_suffix + "' (a byte's char with the suffix)");
+            m.byte_sfx_id[b] = it->second;
+        }
+    }
+}
+
+// merges (bpe/model.rs:252-275): rank = position, new_id = vocab[a+b]; duplicate pairs: last wins.  Writes n_merges and the merge table
+void parse_merges(const Vocab& v, HostModel& m) {
+    const JsonValue* mg = v.model->get("merges");
+    if (!mg || !mg->is_array()) throw Invalid("tokenizer.json: BPE merges missing");
+    std::unordered_map<uint64_t, std::pair<uint32_t, uint32_t>> mm;
+    mm.reserve(mg->arr.size() * 2);
+    uint32_t rank = 0;
+    for (auto& e : mg->arr) {
+        std::string a, b;
+        if (e->is_array() && e->arr.size() == 2 && e->arr[0]->is_string() && e->arr[1]->is_string()) {
+            a = e->arr[0]->str; b = e->arr[1]->str;
+        } else if (e->is_string()) {     // legacy "a b" (bpe/serialization.rs:141-149)
+            size_t sp = e->str.find(' ');
+            if (sp == std::string::npos || e->str.find(' ', sp + 1) != std::string::npos)
+                throw Invalid("tokenizer.json: bad legacy merge entry");
+            a = e->str.substr(0, sp); b = e->str.substr(sp + 1);
+        } else throw Invalid("tokenizer.json: bad merge entry");
+        // (new token = a + b minus the continuing_subword_prefix's LENGTH in bytes, whatever b starts with: BpeBuilder::build :246-271)
+        if (b.size() < m.bpe_prefix.size()) throw Invalid("tokenizer.json: a merge's right-hand token is shorter than continuing_subword_prefix");
+        auto ia = v.id.find(a), ib = v.id.find(b), in = v.id.find(a + b.substr(m.bpe_prefix.size()));
+        if (ia == v.id.end() || ib == v.id.end() || in == v.id.end())
+            throw Invalid("tokenizer.json: merge token out of vocabulary (MergeTokenOutOfVocabulary)");
+        // the "▁" front's unit split (PT_METASPACE without split): exact only if no merge joins a char other than "▁" to a symbol that
+        // starts with "▁" -- then no pair across a cut ever merges, and every unit runs its merges on its own (bpe/word.rs:162-250)
+        if (m.pretok == PT_METASPACE && !m.ms_split && m.char_bpe && b.compare(0, 3, kMetaspace) == 0 && !(a.size() >= 3 && a.compare(a.size() - 3, 3, kMetaspace) == 0))
+            throw Unsupported("pre_tokenizer: the merge ('" + a + "', '" + b + "') joins a char other than U+2581 to a U+2581: whole-piece BPE "
+                              "(no split at U+2581) is outside the hot path for this vocabulary");
+        mm[((uint64_t)ia->second << 32) | ib->second] = {rank, in->second};
+        ++rank;
+    }
+    if (rank >= (1u << 20)) throw Unsupported("more than 2^20 merges");
+    m.n_merges = rank;
+    std::vector<MergeSlot> merges;
+    merges.reserve(mm.size());
+    for (auto& kv : mm) merges.push_back(MergeSlot{(uint32_t)(kv.first >> 32), (uint32_t)kv.first, kv.second.first, kv.second.second});
+    std::sort(merges.begin(), merges.end(), [](const MergeSlot& x, const MergeSlot& y) { return x.rank < y.rank; });
+    build_merge_table(m, merges);
+}
+
+// reads the BPE options, byte_level, pretok; writes model, the bpe_* / unk options, char_bpe, byte_suffix, char_id, byte_id, byte_sfx_id,
+// the merge table.  check_layout's questions about char_bpe and the affixes rely on these refusals having been made first.
+void parse_bpe(const Vocab& v, HostModel& m) {
+    const JsonValue* model = v.model;
+    m.model = MODEL_BPE;
+    const JsonValue* dr = model->get("dropout");
+    if (dr && dr->is_number() && dr->num != 0.0) throw Unsupported("BPE dropout needs the reference's RNG (bpe/word.rs:181)");
+    opt_str(model, "continuing_subword_prefix", &m.bpe_prefix);
+    opt_str(model, "end_of_word_suffix", &m.bpe_suffix);
+    m.fuse_unk = model->get_bool("fuse_unk", false);
+    m.byte_fallback = model->get_bool("byte_fallback", false);
+    m.ignore_merges = model->get_bool("ignore_merges", false);
+    if (opt_str(model, "unk_token", &m.unk_token)) {
+        m.unk_configured = true;
+        lookup_unk(v, m);
+    }
+    m.char_bpe = !m.byte_level;
+    if (m.byte_level && (!m.bpe_prefix.empty() || !m.bpe_suffix.empty()) && (m.pretok != PT_CLIP || !m.bpe_prefix.empty()))
+        throw Unsupported("byte-level BPE with continuing_subword_prefix / end_of_word_suffix (an end_of_word_suffix is on the path behind the CLIP "
+                          "pre-tokenizer alone, with no continuing_subword_prefix)");
+    if (m.byte_level && m.byte_fallback) throw Unsupported("byte-level BPE with byte_fallback");
+    if (m.pretok == PT_CLIP) {
+        if (m.bpe_suffix.empty()) throw Unsupported("pre_tokenizer: the CLIP Split + ByteLevel in front of a BPE without end_of_word_suffix is outside the hot path");
+        if (m.bpe_suffix.size() > 31) throw Unsupported("BPE continuing_subword_prefix / end_of_word_suffix longer than 31 bytes");
+        // (vocab.get(sequence) would look the text up without the suffix its entry carries: not built)
+        if (m.ignore_merges) throw Unsupported("byte-level BPE with end_of_word_suffix and ignore_merges");
+        m.byte_suffix = true;
+    }
+    if (m.char_bpe) build_char_ids(v, m);
+    if (m.byte_level) build_byte_ids(v, m);
+    parse_merges(v, m);
+}
+
+// WordPiece and WordLevel: over characters alone; each names its unk token, with its own default
+void parse_wordpiece_or_wordlevel(const Vocab& v, HostModel& m) {
+    const bool wp = v.mtype == "WordPiece";
+    m.model = wp ? MODEL_WORDPIECE : MODEL_WORDLEVEL;
+    if (m.byte_level) throw Unsupported(v.mtype + " behind ByteLevel");
+    m.unk_token = v.model->get_str("unk_token", wp ? "[UNK]" : "<unk>");
+    if (wp) m.cont_prefix = v.model->get_str("continuing_subword_prefix", "##");
+    if (wp) m.max_input_chars = (uint32_t)v.model->get_num("max_input_chars_per_word", 100);
+    lookup_unk(v, m);
+}
+
+// Unigram (models/unigram/model.rs): a Viterbi search per pre-token over f64 scores (unigram_core.hpp, kernels/unigram.hip).  On the
+// path behind Metaspace(split = true) alone: the front's other layouts cut a piece into units, and a comparison of prefix + score
+// sums made on a unit alone can round differently from the reference's, made over the whole piece.
+// reads the Unigram options, pretok, norm, ms_split (and the pre-tokenizer's type, for a message); writes model, the unk fields,
+// byte_fallback, byte_id, uni_bytes.  check_layout skips the U+2581 front's BPE questions for this model.
+void parse_unigram(const JsonValue* root, const Vocab& v, HostModel& m) {
+    m.model = MODEL_UNIGRAM;
+    if (m.pretok != PT_METASPACE)
+        throw Unsupported("model: Unigram (a vocab of scored pieces) is on the path behind Metaspace(split = true) only; pre_tokenizer '" +
+                          type_name_or_null(root->get("pre_tokenizer")) + "' is not");
+    if ((m.norm != NORM_NONE && m.norm != NORM_PRECOMPILED && m.norm != NORM_NFKC) || !m.ms_split)
+        throw Unsupported("model: Unigram (a vocab of scored pieces) over whole pieces -- Metaspace(split = false), or a null pre_tokenizer behind the U+2581 "
+                          "normalizers -- is outside the hot path: the front cuts such a piece into units, and the reference compares f64 sums of "
+                          "prefix + score over the whole piece, which a unit alone can round differently (only Metaspace(split = true) is on the path)");
+    const JsonValue* uk = v.model->get("unk_id");
+    if (uk && uk->is_number()) {
+        if (uk->num < 0 || uk->num >= (double)v.uni_pieces.size()) throw Unsupported("model: Unigram unk_id " + std::to_string((long long)uk->num) + " is beyond the vocab (UnkIdNotInVocabulary)");
+        m.has_unk = true;
+        m.unk_id = (uint32_t)uk->num;
+        m.unk_token = v.uni_pieces[m.unk_id];
+    }
+    m.byte_fallback = v.model->get_bool("byte_fallback", false);
+    for (int b = 0; b < 256; ++b) m.byte_id[b] = CHAR_NONE;
+    if (m.byte_fallback) {
+        // a run the vocabulary lacks becomes the <0xXX> tokens of its bytes only if ALL of them exist (unigram/model.rs:453-468: per
+        // run in the reference; every byte of valid UTF-8 but 0xC0, 0xC1, 0xF5.. can occur, so the flag asks for all 256 and a file
+        // that lacks one keeps its unk runs -- what the reference does for every run that holds such a byte; the others are refused)
+        int have = 0;
+        for (int b = 0; b < 256; ++b)
+            if (const uint32_t* id = byte_token_id(v, b)) { m.byte_id[b] = *id; ++have; }
+        m.uni_bytes = have == 256;
+        if (have != 0 && have != 256)
+            throw Unsupported("model: Unigram byte_fallback with " + std::to_string(have) + " of the 256 <0xXX> pieces (all or none are on the path)");
+    }
+    if (v.id.count("")) throw Unsupported("model: Unigram vocab with an empty piece is outside the hot path");
+    // (the offsets of a byte-fallback run are put together from the result itself, kernels/unigram.hip k_unigram_run_offsets: no run may
+    // begin with the U+2581 that opens a pre-token, which holds when U+2581 is a piece and the unk piece does not begin with one)
+    if (m.uni_bytes && (!v.id.count(kMetaspace) || (m.has_unk && m.unk_token.compare(0, 3, kMetaspace) == 0)))
+        throw Unsupported("model: Unigram byte_fallback with a vocab that lacks the piece U+2581 (or whose unk piece begins with it) is outside the hot path");
+}
+
+// picks the model's parser by v.mtype (read_vocab resolved it); the last refusal is for a type nothing here knows
+void parse_model(const JsonValue* root, const Vocab& v, HostModel& m) {
+    if (v.mtype == "BPE") parse_bpe(v, m);
+    else if (v.mtype == "WordPiece" || v.mtype == "WordLevel") parse_wordpiece_or_wordlevel(v, m);
+    else if (v.unigram) parse_unigram(root, v, m);
+    else throw Unsupported("model: type '" + v.mtype + "' is outside the hot path");
+}
+
+// ---- 13. normalizer x pre-tokenizer x model: what each component accepted alone but the three are not built for together ----
+// reads norm, pretok, model and their options, added_tokens, v.id; writes nothing.  IN THIS ORDER -- a file these questions apply to two
+// of gets the first one's words -- and behind every refusal of the components' own parsers.
+void check_layout(const Vocab& v, const HostModel& m) {
     if (m.pretok == PT_METASPACE && m.model != MODEL_UNIGRAM) {
         if (m.model != MODEL_BPE || !m.char_bpe)
             throw Unsupported("pre_tokenizer: the U+2581 front (Metaspace, or null behind the U+2581 normalizers) is only on the path in front of BPE over characters");
         if (!m.bpe_prefix.empty() || !m.bpe_suffix.empty())
             throw Unsupported("pre_tokenizer: the U+2581 front with continuing_subword_prefix / end_of_word_suffix");
         if (!m.ms_split) {
-            // (the device cuts every piece at each U+2581 behind another char: exact by the merge check above, if the vocabulary has the U+2581
+            // (the device cuts every piece at each U+2581 behind another char: exact by parse_merges' check, if the vocabulary has the U+2581
             // symbol itself -- and not for ignore_merges, whose whole-word lookup is of the whole piece)
             if (m.ignore_merges) throw Unsupported("pre_tokenizer: ignore_merges over whole pieces (no split at U+2581) is outside the hot path");
-            if (v.find(kMetaspace) == v.end()) throw Unsupported("pre_tokenizer: whole-piece BPE (no split at U+2581) with a vocabulary that lacks U+2581 is outside the hot path");
+            if (v.id.find(kMetaspace) == v.id.end()) throw Unsupported("pre_tokenizer: whole-piece BPE (no split at U+2581) with a vocabulary that lacks U+2581 is outside the hot path");
         }
     }
     if (m.norm == NORM_NFC &&
@@ -1981,78 +2039,83 @@ HostModel HostModel::from_json(const char* json, size_t len) {
     if (m.norm == NORM_METASPACE)
         for (const AddedToken& a : m.added_tokens)
             if (a.normalized) throw Unsupported("added token '" + a.content + "' is normalized = true behind the U+2581 normalizer (matched on the normalized text: not on the path)");
+}
 
-    // BPE over characters with an end_of_word_suffix: the vocabulary entry of a WHOLE word carries the suffix its text does not.  The
-    // whole-word table (below) is keyed by text: the merge-stable shortcut's candidates are the entries minus their suffix (an entry
-    // without it cannot be a word's last symbol, let alone the whole word) -- each is then run through the device's merge kernel and
-    // only kept if the result is exactly its own id (capi.cpp verify_direct_words).  ignore_merges looks the TEXT up as it stands
-    // (vocab.get(sequence), bpe/model.rs:559-567): no stripping there.
-    // Byte-level BPE with a suffix (behind PT_CLIP) alike: raw_tokens are the entries' raw bytes, so the suffix is taken off in its raw form.
-    if ((m.char_bpe || m.byte_suffix) && !m.ignore_merges && !m.bpe_suffix.empty()) {
-        (void)n_raw_plain;
-        std::string sfx = m.bpe_suffix;
-        if (m.byte_suffix && !bytelevel_to_raw(m.bpe_suffix, c2b, &sfx))
-            throw Unsupported("byte-level BPE with an end_of_word_suffix that holds a char outside the byte-level alphabet");
-        for (std::string& r : m.raw_tokens) {
-            if (r.size() > sfx.size() && r.compare(r.size() - sfx.size(), sfx.size(), sfx) == 0) r.resize(r.size() - sfx.size());
-            else r.clear();
-        }
-        // (two entries may now share a text -- "ab</w>" and a stray "ab</w></w>" -- : the table wants distinct keys, the first one stays)
-        std::unordered_map<std::string, size_t> seen;
-        for (size_t i = 0; i < m.raw_tokens.size(); ++i)
-            if (!m.raw_tokens[i].empty() && !seen.emplace(m.raw_tokens[i], i).second) m.raw_tokens[i].clear();
+// ---- 14. BPE with an end_of_word_suffix: the whole-word candidates lose it ----
+// BPE over characters with an end_of_word_suffix: the vocabulary entry of a WHOLE word carries the suffix its text does not.  The
+// whole-word table (build_word_tables) is keyed by text: the merge-stable shortcut's candidates are the entries minus their suffix (an
+// entry without it cannot be a word's last symbol, let alone the whole word) -- each is then run through the device's merge kernel and
+// only kept if the result is exactly its own id (capi/tables.cpp verify_direct_words).  ignore_merges looks the TEXT up as it stands
+// (vocab.get(sequence), bpe/model.rs:559-567): no stripping there.
+// Byte-level BPE with a suffix (behind PT_CLIP) alike: raw_tokens are the entries' raw bytes, so the suffix is taken off in its raw form.
+// reads the BPE options; rewrites raw_tokens in place (an entry that is no candidate becomes "", which the table builders skip)
+void strip_suffix_from_raw_tokens(const Vocab& v, HostModel& m) {
+    if (!((m.char_bpe || m.byte_suffix) && !m.ignore_merges && !m.bpe_suffix.empty())) return;
+    std::string sfx = m.bpe_suffix;
+    if (m.byte_suffix && !bytelevel_to_raw(m.bpe_suffix, v.c2b, &sfx))
+        throw Unsupported("byte-level BPE with an end_of_word_suffix that holds a char outside the byte-level alphabet");
+    for (std::string& r : m.raw_tokens) {
+        if (r.size() > sfx.size() && r.compare(r.size() - sfx.size(), sfx.size(), sfx) == 0) r.resize(r.size() - sfx.size());
+        else r.clear();
     }
+    // (two entries may now share a text -- "ab</w>" and a stray "ab</w></w>" -- : the table wants distinct keys, the first one stays)
+    std::unordered_map<std::string, size_t> seen;
+    for (size_t i = 0; i < m.raw_tokens.size(); ++i)
+        if (!m.raw_tokens[i].empty() && !seen.emplace(m.raw_tokens[i], i).second) m.raw_tokens[i].clear();
+}
 
-    // ---- whole-word tables (BPE: ignore_merges + merge-stable shortcut; WordLevel: the model) ----
-    if (m.model == MODEL_BPE || m.model == MODEL_WORDLEVEL || m.model == MODEL_WORDPIECE || m.model == MODEL_UNIGRAM) {
-        // (WordPiece: the longest candidate piece is the whole word, so a whole-word hit ends the match at once)
-        // (Unigram: a whole-word hit is final only where the Viterbi of that word alone yields [id] -- proved on the device at load)
-        std::vector<WordSlot> words;
-        m.long_off.push_back(0);
-        for (size_t i = 0; i < m.raw_tokens.size(); ++i) {
-            const std::string& r = m.raw_tokens[i];
-            if (r.empty()) continue;
-            if (r.size() <= (size_t)WORD_MAX_KEY) {
-                uint8_t buf[16] = {0};
-                memcpy(buf, r.data(), r.size());
-                WordSlot s{};
-                memcpy(&s.lo, buf, 8);
-                memcpy(&s.hi, buf + 8, 8);
-                s.len = (uint32_t)r.size();
-                s.id = m.raw_ids[i];
-                s.flags = 0;
-                words.push_back(s);
-            } else {
-                m.long_blob.insert(m.long_blob.end(), r.begin(), r.end());
-                m.long_off.push_back((uint32_t)m.long_blob.size());
-                m.long_id.push_back(m.raw_ids[i]);
-            }
+// ---- 15. the tables keyed by the vocabulary's raw bytes ----
+// whole-word tables (BPE: ignore_merges + merge-stable shortcut; WordLevel: the model; WordPiece: the longest candidate piece is the
+// whole word, so a whole-word hit ends the match at once; Unigram: a whole-word hit is final only where the Viterbi of that word alone
+// yields [id] -- proved on the device at load).  reads raw_tokens / raw_ids in order; writes word_table, long_*, n_words
+void build_word_tables(HostModel& m) {
+    std::vector<WordSlot> words;
+    m.long_off.push_back(0);
+    for (size_t i = 0; i < m.raw_tokens.size(); ++i) {
+        const std::string& r = m.raw_tokens[i];
+        if (r.empty()) continue;
+        if (r.size() <= (size_t)WORD_MAX_KEY) {
+            uint8_t buf[16] = {0};
+            memcpy(buf, r.data(), r.size());
+            WordSlot s{};
+            memcpy(&s.lo, buf, 8);
+            memcpy(&s.hi, buf + 8, 8);
+            s.len = (uint32_t)r.size();
+            s.id = m.raw_ids[i];
+            s.flags = 0;
+            words.push_back(s);
+        } else {
+            m.long_blob.insert(m.long_blob.end(), r.begin(), r.end());
+            m.long_off.push_back((uint32_t)m.long_blob.size());
+            m.long_id.push_back(m.raw_ids[i]);
         }
-        m.n_words = (uint32_t)words.size();
-        build_word_table(m, words);
-        build_long_table(m);
     }
-    if (m.model == MODEL_WORDPIECE) {
-        std::vector<std::pair<std::string, uint32_t>> ini, cont;
-        for (size_t i = 0; i < m.raw_tokens.size(); ++i) {
-            const std::string& r = m.raw_tokens[i];
-            if (r.empty()) continue;
-            ini.emplace_back(r, m.raw_ids[i]);
-            if (!m.cont_prefix.empty() && r.size() > m.cont_prefix.size() && r.compare(0, m.cont_prefix.size(), m.cont_prefix) == 0)
-                cont.emplace_back(r.substr(m.cont_prefix.size()), m.raw_ids[i]);
-            else if (m.cont_prefix.empty())
-                cont.emplace_back(r, m.raw_ids[i]);
-        }
-        build_trie(m, ini, cont);
-    }
-    if (m.model == MODEL_UNIGRAM) {
-        // the byte trie over all pieces (the reference's common_prefix_search, unigram/model.rs:285-288): the WordPiece table, word-initial root only
-        std::vector<std::pair<std::string, uint32_t>> ini, cont;
-        for (size_t i = 0; i < m.raw_tokens.size(); ++i)
-            if (!m.raw_tokens[i].empty()) ini.emplace_back(m.raw_tokens[i], m.raw_ids[i]);
-        build_trie(m, ini, cont);
-    }
+    m.n_words = (uint32_t)words.size();
+    build_word_table(m, words);
+    build_long_table(m);
+}
 
+// the byte trie of WordPiece (two roots: word-initial pieces, continuation pieces without their prefix) and of Unigram (every piece under
+// root 0: the reference's common_prefix_search, unigram/model.rs:285-288).  reads raw_tokens / raw_ids in order, cont_prefix; writes trie
+void build_model_trie(HostModel& m) {
+    if (m.model != MODEL_WORDPIECE && m.model != MODEL_UNIGRAM) return;
+    std::vector<std::pair<std::string, uint32_t>> ini, cont;
+    for (size_t i = 0; i < m.raw_tokens.size(); ++i) {
+        const std::string& r = m.raw_tokens[i];
+        if (r.empty()) continue;
+        ini.emplace_back(r, m.raw_ids[i]);
+        if (m.model != MODEL_WORDPIECE) continue;
+        if (!m.cont_prefix.empty() && r.size() > m.cont_prefix.size() && r.compare(0, m.cont_prefix.size(), m.cont_prefix) == 0)
+            cont.emplace_back(r.substr(m.cont_prefix.size()), m.raw_ids[i]);
+        else if (m.cont_prefix.empty())
+            cont.emplace_back(r, m.raw_ids[i]);
+    }
+    build_trie(m, ini, cont);
+}
+
+// ---- 16. the class tables and the normalizer's tables ----
+// reads norm, nfc_lower, chain, pretok; writes uc_*, bn_*, nfc_*, nfk_* (build_added_patterns normalizes through them)
+void build_normalizer_tables(HostModel& m) {
     build_unicode(m);
     if (m.norm == NORM_BERT) build_bert_norm(m);
     if (m.norm == NORM_NFC) build_nfc_tables(m);
@@ -2063,80 +2126,118 @@ HostModel HostModel::from_json(const char* json, size_t len) {
         build_nfc_tables(m);
         if (m.chain_has(CHAIN_LOWERCASE)) build_norm_chain(m, {CHAIN_LOWERCASE});
     }
+}
 
-    // ---- AddedVocabulary pattern sets (needs the normalizer tables: normalized tokens match by their normalized form) ----
-    {
-        struct Pat { std::string s; uint32_t id, flags; };
-        std::vector<Pat> pats[2];
-        // the automaton is built over the special tokens first, then the others, each in the order they were added
-        // (refresh_added_tokens, added_vocabulary.rs:379-399): of two tokens with one pattern -- "Ab" and "AB" behind a lowercasing
-        // normalizer -- the first in THAT order is the one a match reports
-        std::vector<const AddedToken*> order;
-        for (int pass = 0; pass < 2; ++pass)
-            for (const AddedToken& a : m.added_tokens)
-                if ((pass == 0) == a.special) order.push_back(&a);
-        for (const AddedToken* ap : order) {
-            const AddedToken& a = *ap;
-            if (a.content.empty()) continue;                       // add_tokens ignores empty contents (added_vocabulary.rs:288-291)
-            std::string pat = a.content;
-            if (a.normalized && m.norm == NORM_BERT) {
-                bool refused = false;
-                pat = m.bert_normalize(a.content, &refused);
-                if (refused) throw Unsupported("added token '" + a.content + "' holds a character whose NFD reordering is context dependent");
-                if (pat.empty()) continue;                         // normalizes to nothing: the automaton has nothing to match
-            }
-            if (a.normalized && m.norm == NORM_CHAIN) {
-                bool refused = false;
-                pat = m.chain_normalize(a.content, nullptr, &refused);
-                if (refused) throw Unsupported("added token '" + a.content + "' holds a run of more than 48 combining characters (NFD of such a run is not built)");
-                if (pat.empty()) continue;
-            }
-            if (a.normalized && m.norm == NORM_NFC) {
-                bool refused = false;
-                pat = m.nfc_normalize(a.content, nullptr, &refused);
-                if (refused) throw Unsupported("added token '" + a.content + "' holds a run of more than 48 combining characters (NFC of such a run is not built)");
-                if (m.nfc_ws_fold) {                               // Replace(Regex "\\s+" -> " ") of the CLIP chain: every \s run of the pattern is one ' '
-                    std::string folded;
-                    bool in_run = false;
-                    for (size_t i = 0; i < pat.size();) {
-                        uint32_t cp = 0;
-                        const int l = std::max(1, utf8_decode((const uint8_t*)pat.data() + i, pat.size() - i, &cp));
-                        const bool ws = cp < 0x110000u && (m.uc_stage2[((size_t)m.uc_stage1[cp >> 8] << 8) | (cp & 255u)] & UC_RX_S);
-                        if (!ws) folded.append(pat, i, (size_t)l);
-                        else if (!in_run) folded.push_back(' ');
-                        in_run = ws;
-                        i += (size_t)l;
-                    }
-                    pat = folded;
-                }
-            }
-            if (a.normalized && m.norm == NORM_NFKC) {
-                bool refused = false;
-                pat = m.nfkc_normalize(a.content, nullptr, &refused);
-                if (refused) throw Unsupported("added token '" + a.content + "' holds a run of more than 48 combining characters (NFKC of such a run is not built)");
-                if (pat.empty()) continue;
-            }
-            pats[a.normalized ? 1 : 0].push_back(Pat{pat, a.id, (a.single_word ? 1u : 0u) | (a.lstrip ? 2u : 0u) | (a.rstrip ? 4u : 0u) | (a.special ? 8u : 0u)});
-        }
-        for (int c = 0; c < 2; ++c) {
-            std::vector<Pat>& ps = pats[c];
-            // equal patterns: the first one in the automaton's order is reported
-            std::stable_sort(ps.begin(), ps.end(), [](const Pat& x, const Pat& y) { return x.s < y.s; });
-            std::vector<Pat> uniq;
-            for (const Pat& p : ps) { if (uniq.empty() || uniq.back().s != p.s) uniq.push_back(p); }
-            PatternSet& S = m.at[c];
-            S.first.assign(257, 0);
-            S.off.push_back(0);
-            for (const Pat& p : uniq) {
-                S.first[(uint8_t)p.s[0] + 1]++;
-                S.blob.insert(S.blob.end(), p.s.begin(), p.s.end());
-                S.off.push_back((uint32_t)S.blob.size());
-                S.id.push_back(p.id);
-                S.flags.push_back(p.flags);
-            }
-            for (int b = 0; b < 256; ++b) S.first[b + 1] += S.first[b];
-        }
+// ---- 17. AddedVocabulary pattern sets ----
+// Replace(Regex "\\s+" -> " ") of the CLIP chain: every \s run of a pattern is one ' '
+std::string fold_whitespace_runs(const HostModel& m, const std::string& pat) {
+    std::string folded;
+    bool in_run = false;
+    for (size_t i = 0; i < pat.size();) {
+        uint32_t cp = 0;
+        const int l = std::max(1, utf8_decode((const uint8_t*)pat.data() + i, pat.size() - i, &cp));
+        const bool ws = uc_flags(m, cp) & UC_RX_S;
+        if (!ws) folded.append(pat, i, (size_t)l);
+        else if (!in_run) folded.push_back(' ');
+        in_run = ws;
+        i += (size_t)l;
     }
+    return folded;
+}
+
+// the pattern of a normalized added token: its content through the file's normalizer.  Each normalizer refuses in its own words what
+// its core does not build; false: the token normalizes to nothing, and the automaton has nothing to match.  (NFC keeps even an empty
+// pattern -- it never makes one of a non-empty content -- and alone folds the CLIP chain's whitespace.)
+bool normalized_pattern(const HostModel& m, const AddedToken& a, std::string* pat) {
+    bool refused = false;
+    const char* form = nullptr;
+    if (m.norm == NORM_BERT) *pat = m.bert_normalize(a.content, &refused);
+    else if (m.norm == NORM_CHAIN) { *pat = m.chain_normalize(a.content, nullptr, &refused); form = "NFD"; }
+    else if (m.norm == NORM_NFC) { *pat = m.nfc_normalize(a.content, nullptr, &refused); form = "NFC"; }
+    else if (m.norm == NORM_NFKC) { *pat = m.nfkc_normalize(a.content, nullptr, &refused); form = "NFKC"; }
+    else return true;
+    if (refused && !form) throw Unsupported("added token '" + a.content + "' holds a character whose NFD reordering is context dependent");
+    if (refused) throw Unsupported("added token '" + a.content + "' holds a run of more than 48 combining characters (" + form + " of such a run is not built)");
+    if (m.norm != NORM_NFC) return !pat->empty();
+    if (m.nfc_ws_fold) *pat = fold_whitespace_runs(m, *pat);
+    return true;
+}
+
+// reads added_tokens and the normalizer's tables (normalized tokens match by their normalized form); writes at[0], at[1]
+void build_added_patterns(HostModel& m) {
+    struct Pat { std::string s; uint32_t id, flags; };
+    std::vector<Pat> pats[2];
+    // the automaton is built over the special tokens first, then the others, each in the order they were added
+    // (refresh_added_tokens, added_vocabulary.rs:379-399): of two tokens with one pattern -- "Ab" and "AB" behind a lowercasing
+    // normalizer -- the first in THAT order is the one a match reports
+    std::vector<const AddedToken*> order;
+    for (int pass = 0; pass < 2; ++pass)
+        for (const AddedToken& a : m.added_tokens)
+            if ((pass == 0) == a.special) order.push_back(&a);
+    for (const AddedToken* ap : order) {
+        const AddedToken& a = *ap;
+        if (a.content.empty()) continue;                       // add_tokens ignores empty contents (added_vocabulary.rs:288-291)
+        std::string pat = a.content;
+        if (a.normalized && !normalized_pattern(m, a, &pat)) continue;
+        pats[a.normalized ? 1 : 0].push_back(Pat{pat, a.id, (a.single_word ? 1u : 0u) | (a.lstrip ? 2u : 0u) | (a.rstrip ? 4u : 0u) | (a.special ? 8u : 0u)});
+    }
+    for (int c = 0; c < 2; ++c) {
+        std::vector<Pat>& ps = pats[c];
+        // equal patterns: the first one in the automaton's order is reported
+        std::stable_sort(ps.begin(), ps.end(), [](const Pat& x, const Pat& y) { return x.s < y.s; });
+        std::vector<Pat> uniq;
+        for (const Pat& p : ps) { if (uniq.empty() || uniq.back().s != p.s) uniq.push_back(p); }
+        HostModel::PatternSet& S = m.at[c];
+        S.first.assign(257, 0);
+        S.off.push_back(0);
+        for (const Pat& p : uniq) {
+            S.first[(uint8_t)p.s[0] + 1]++;
+            S.blob.insert(S.blob.end(), p.s.begin(), p.s.end());
+            S.off.push_back((uint32_t)S.blob.size());
+            S.id.push_back(p.id);
+            S.flags.push_back(p.flags);
+        }
+        for (int b = 0; b < 256; ++b) S.first[b + 1] += S.first[b];
+    }
+}
+
+}  // namespace
+
+// The load, as its table of contents.  Every stage says in its header what it reads and writes; the order is the order of the refusals
+// and of the tables' layout (see the top of this part).
+HostModel HostModel::from_json(const char* json, size_t len) {
+    JsonPtr root_owner;
+    try {
+        root_owner = json_parse(json, len);
+    } catch (const std::exception& e) {
+        throw Invalid(e.what());
+    }
+    const JsonValue* root = root_owner.get();
+    if (!root->is_object()) throw Invalid("tokenizer.json: top level is not an object");
+    HostModel m;
+    std::fill(m.byte_id, m.byte_id + 256, 0xFFFFFFFFu);
+
+    parse_truncation_padding(root, m);
+    parse_normalizer(root, m);
+    check_normalizer_against_pretok_type(root, m);
+    m.pretok = parse_pretok(root->get("pre_tokenizer"), m);
+    finish_pretok(m);
+    parse_post_processor(root, m);
+    parse_added_tokens(root, m);
+
+    Vocab v;
+    read_vocab(root, m, v);
+    assign_added_token_ids(v, m);
+    build_raw_tokens(v, m);
+    build_decode_tables(m, root, v.id, v.c2b, v.unigram ? &v.uni_pieces : nullptr);
+    parse_model(root, v, m);
+    check_layout(v, m);
+
+    strip_suffix_from_raw_tokens(v, m);
+    build_word_tables(m);
+    build_model_trie(m);
+    build_normalizer_tables(m);
+    build_added_patterns(m);
     return m;
 }
 
@@ -2207,12 +2308,7 @@ std::string HostModel::chain_normalize(const std::string& s, std::vector<uint32_
         const size_t before = out.size();
         for (int q = 0; q < k; ++q) {
             uint8_t b[4];
-            const uint32_t c = o[q], l = bn_core_utf8_len(c);
-            if (l == 1u) b[0] = (uint8_t)c;
-            else if (l == 2u) { b[0] = (uint8_t)(0xC0u | (c >> 6)); b[1] = (uint8_t)(0x80u | (c & 0x3Fu)); }
-            else if (l == 3u) { b[0] = (uint8_t)(0xE0u | (c >> 12)); b[1] = (uint8_t)(0x80u | ((c >> 6) & 0x3Fu)); b[2] = (uint8_t)(0x80u | (c & 0x3Fu)); }
-            else { b[0] = (uint8_t)(0xF0u | (c >> 18)); b[1] = (uint8_t)(0x80u | ((c >> 12) & 0x3Fu)); b[2] = (uint8_t)(0x80u | ((c >> 6) & 0x3Fu)); b[3] = (uint8_t)(0x80u | (c & 0x3Fu)); }
-            out.append((const char*)b, l);
+            out.append((const char*)b, nfc_utf8_put(b, o[q]));
         }
         if (norig) norig->insert(norig->end(), out.size() - before, (uint32_t)i);
         i += len;
@@ -2281,10 +2377,7 @@ void HostModel::set_precompiled(const std::string& blob) {
             if (!seen[next] && nd.depth < 64u) { seen[next] = 1; stack.push_back({next, nd.depth + 1u}); }
         }
     }
-    std::vector<uint8_t> flat(0x110000, 0);
-    for (const UcRun& r : kGcRuns)
-        for (uint32_t cp = r.first; cp <= r.last; ++cp) flat[cp] = r.flags;
-    two_stage(flat, &gc_stage1, &gc_stage2);
+    two_stage(flat_of(kGcRuns), &gc_stage1, &gc_stage2);
 }
 
 std::string HostModel::precompiled_normalize(const std::string& s, std::vector<uint32_t>* norig) const {
@@ -2400,11 +2493,8 @@ std::string HostModel::bert_normalize(const std::string& s, bool* refused) const
                              bn_core_flags(bn_stage1.data(), bn_stage2.data(), cp), nullptr))
             *refused = true;
         for (int q = 0; q < n; ++q) {
-            const uint32_t c = o[q];
-            if (c < 0x80u) out.push_back((char)c);
-            else if (c < 0x800u) { out.push_back((char)(0xC0u | (c >> 6))); out.push_back((char)(0x80u | (c & 0x3Fu))); }
-            else if (c < 0x10000u) { out.push_back((char)(0xE0u | (c >> 12))); out.push_back((char)(0x80u | ((c >> 6) & 0x3Fu))); out.push_back((char)(0x80u | (c & 0x3Fu))); }
-            else { out.push_back((char)(0xF0u | (c >> 18))); out.push_back((char)(0x80u | ((c >> 12) & 0x3Fu))); out.push_back((char)(0x80u | ((c >> 6) & 0x3Fu))); out.push_back((char)(0x80u | (c & 0x3Fu))); }
+            uint8_t b[4];
+            out.append((const char*)b, nfc_utf8_put(b, o[q]));
         }
     }
     return out;
