@@ -290,6 +290,41 @@ int tkamd_encode_batch_words_device(tkamd_tokenizer* tok, const uint8_t* d_text,
                                     tkamd_device_result* out);
 int tkamd_device_sync(tkamd_tokenizer* tok, void* hip_stream, int64_t* n_tokens, int64_t* n_pretokens);
 
+/* ---- dense entry: text in HBM in, padded [n_rows, width] arrays in the CALLER's HBM out ---------------------------
+ * What a model's forward pass reads -- transformers' input_ids / attention_mask / token_type_ids / special_tokens_mask / offset_mapping
+ * / word_ids -- written by one more stage behind the epilogue (kernels/dense.hip) into memory the caller owns (a torch tensor's
+ * data_ptr), every array as int64 or every array as int32.  tkamd_encode_batch_device_dense is tkamd_encode_batch_device with
+ * TKAMD_WANT_DENSE | TKAMD_NO_SPECULATION set by the call itself: flags takes the offsets mode, TKAMD_WANT_WORD_IDS, TKAMD_ADD_SPECIAL
+ * and TKAMD_PAIRS (documents 2i / 2i + 1 -> row i).  The call only enqueues: no synchronisation, no copy to the host, and after a first
+ * call of the same size no allocation; the arrays are final when `hip_stream` reaches them.  The one exception is a batch whose work
+ * queue overflowed (natural text does not): tkamd_device_sync runs it again, as for every device call, and the re-run fills the same
+ * arrays -- `d_text`, `d_doc_offsets` and the arrays of `dst` must stay alive until the batch has been synchronised or the next call on
+ * the stream was made.  `out` is filled as by tkamd_encode_batch_device (the padded CSR in the workspace; ids_capacity = n_rows * width).
+ *   input_ids           the ids, pad_id on padding
+ *   attention_mask      0 on padding, else 1
+ *   token_type_ids      the template's type ids (pairs, typed single templates); else 0, pad_type_id on padding
+ *   special_tokens_mask 1 on special tokens and on padding
+ *   offsets             [n_rows][width][2] (start, end) in the call's offsets mode -- refused with TKAMD_OFFSETS_NONE; (0, 0) on special
+ *                       tokens and padding
+ *   word_ids            the word index, -1 for none -- refused without TKAMD_WANT_WORD_IDS
+ * The row width must be known before the call, so the handle needs a `truncation` section and a `padding` section with a Fixed
+ * strategy: width = its length rounded up to pad_to_multiple_of, max_length <= width, and with TKAMD_ADD_SPECIAL max_length must be at
+ * least the number of special tokens the (single or pair) template adds.  tkamd_dense_width answers that width for `flags`
+ * (TKAMD_ADD_SPECIAL and TKAMD_PAIRS matter) or fails with TKAMD_ERR_INVALID naming the missing piece.  Refused up front, with
+ * TKAMD_ERR_INVALID and before any device work: TKAMD_WANT_OVERFLOW (the number of rows would be known on the device only),
+ * dst->n_rows != n_docs (n_docs / 2 for pairs), dst->width != that width, a multi-device handle.  Pre-tokenized and mixed inputs have
+ * no dense entry.  TKAMD_WANT_DENSE itself is refused by every other entry. */
+#define TKAMD_WANT_DENSE 128u
+#define TKAMD_DENSE_I32 1u
+typedef struct tkamd_dense_out {
+    void *input_ids, *attention_mask, *token_type_ids, *special_tokens_mask, *offsets, *word_ids;  /* device; all but input_ids may be NULL */
+    int64_t n_rows, width;
+    uint32_t dtype_flags;     /* 0: int64 elements, TKAMD_DENSE_I32: int32 */
+} tkamd_dense_out;
+int tkamd_dense_width(const tkamd_tokenizer* tok, uint32_t flags, int64_t* width);
+int tkamd_encode_batch_device_dense(tkamd_tokenizer* tok, const uint8_t* d_text, const int64_t* d_doc_offsets, int64_t n_docs, int64_t n_bytes,
+                                    uint32_t flags, void* hip_stream, const tkamd_dense_out* dst, tkamd_device_result* out);
+
 /* ---- decode_batch: token ids -> text -----------------------------------------------------------
  * Replaces Tokenizer::decode_batch (tokenizer/mod.rs:1404-1416) = map of Tokenizer::decode (mod.rs:935-953):
  * id -> token string (added vocabulary first, added_vocabulary.rs:239-246; ids without a token are dropped),

@@ -25,6 +25,8 @@ ADD_SPECIAL = 8
 PAIRS = 16
 WANT_OVERFLOW = 32
 NO_SPECULATION = 64      # device entry, results consumed stream-ordered without tkamd_device_sync: the added tokens' matching passes and the NFC normalizer outright
+WANT_DENSE = 128         # set by tkamd_encode_batch_device_dense itself: the dense stage behind the epilogue
+DENSE_I32 = 1             # tkamd_dense_out.dtype_flags: int32 elements (0: int64)
 SKIP_SPECIAL = 1          # tkamd_decode_batch flag
 DECODE_IDS_I64 = 2        # tkamd_decode_batch_device: the ids are int64
 STREAM_IDS_HOST = 4       # tkamd_decode_stream_step: the ids and the mask are host arrays
@@ -47,6 +49,7 @@ SYMBOLS = [
     "tkamd_decode_batch_device", "tkamd_device_text_read", "tkamd_probe_utf8_lossy",
     "tkamd_decode_stream_new", "tkamd_decode_stream_free", "tkamd_decode_stream_reset", "tkamd_decode_stream_seed", "tkamd_decode_stream_step",
     "tkamd_decode_stream_read", "tkamd_decode_stream_peek", "tkamd_decode_stream_info",
+    "tkamd_dense_width", "tkamd_encode_batch_device_dense",
 ]
 COLLECT_HOST, COLLECT_ROOT_P2P, COLLECT_ROOT_RCCL = 0, 1, 2
 
@@ -67,6 +70,11 @@ class DeviceResult(C.Structure):
 
 class DeviceText(C.Structure):
     _fields_ = [("d_bytes", C.c_void_p), ("d_doc_offsets", C.c_void_p), ("d_n_bytes", C.c_void_p), ("n_bytes", C.c_int64)]
+
+
+class DenseOut(C.Structure):
+    _fields_ = [("input_ids", C.c_void_p), ("attention_mask", C.c_void_p), ("token_type_ids", C.c_void_p), ("special_tokens_mask", C.c_void_p),
+                ("offsets", C.c_void_p), ("word_ids", C.c_void_p), ("n_rows", C.c_int64), ("width", C.c_int64), ("dtype_flags", C.c_uint32)]
 
 
 class StageTime(C.Structure):
@@ -150,6 +158,10 @@ def load() -> C.CDLL:
     lib.tkamd_batch_free.restype = None
     lib.tkamd_encode_batch_device.argtypes = [vp, vp, vp, i64, i64, u32, vp, C.POINTER(DeviceResult)]
     lib.tkamd_encode_batch_device.restype = i32
+    lib.tkamd_dense_width.argtypes = [vp, u32, C.POINTER(i64)]
+    lib.tkamd_dense_width.restype = i32
+    lib.tkamd_encode_batch_device_dense.argtypes = [vp, vp, vp, i64, i64, u32, vp, C.POINTER(DenseOut), C.POINTER(DeviceResult)]
+    lib.tkamd_encode_batch_device_dense.restype = i32
     lib.tkamd_word_cache.argtypes = [vp, i32, i32]
     lib.tkamd_word_cache.restype = i32
     lib.tkamd_device_sync.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64)]

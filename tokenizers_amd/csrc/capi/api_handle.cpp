@@ -190,7 +190,8 @@ int tkamd_tokenizer_pair_template(const tkamd_tokenizer* t, int with_specials, u
 }
 
 static int encode_device(tkamd_tokenizer* t, const uint8_t* d_text, const int64_t* d_doc_offsets, int64_t n_docs, int64_t n_bytes,
-                         const int64_t* d_seq_offsets, int64_t n_seqs, uint32_t flags, void* hip_stream, tkamd_device_result* out) {
+                         const int64_t* d_seq_offsets, int64_t n_seqs, uint32_t flags, void* hip_stream, tkamd_device_result* out,
+                         const tkamd_dense_out* dst = nullptr) {
     if (!t || !out || !d_doc_offsets || n_docs < 0 || n_bytes < 0 || (n_bytes > 0 && !d_text))
         return set_error(TKAMD_ERR_INVALID, "bad argument");
     if (t->device < 0) return set_error(TKAMD_ERR_DEVICE, "host-only tokenizer handle: no HIP device bound (there is no CPU fallback)");
@@ -199,6 +200,8 @@ static int encode_device(tkamd_tokenizer* t, const uint8_t* d_text, const int64_
         Workspace* w = workspace_of_stream(t, (hipStream_t)hip_stream, true);
         std::lock_guard<std::mutex> lk(w->mu);
         HIP_CHECK(hipSetDevice(t->device));
+        w->has_dense = dst != nullptr;                       // (in front of the pipeline: check_request reads the destination)
+        if (dst) w->last_dense = *dst;
         run_pipeline(t, w, d_text, d_doc_offsets, n_docs, n_bytes, d_seq_offsets, n_seqs, flags, (hipStream_t)hip_stream, out);
         w->last_text = d_text; w->last_doc_off = d_doc_offsets; w->last_n_bytes = n_bytes; w->last_flags = flags; w->last_result = *out;
         return TKAMD_OK;
@@ -212,6 +215,21 @@ int tkamd_encode_batch_words_device(tkamd_tokenizer* t, const uint8_t* d_text, c
                                     const int64_t* d_seq_offsets, int64_t n_seqs, uint32_t flags, void* hip_stream, tkamd_device_result* out) {
     if (!d_seq_offsets || n_seqs < 0) return set_error(TKAMD_ERR_INVALID, "bad argument");
     return encode_device(t, d_text, d_word_offsets, n_words, n_bytes, d_seq_offsets, n_seqs, flags, hip_stream, out);
+}
+
+// The dense entry: the device entry with the dense stage behind its epilogue.  Its results are consumed stream-ordered, so nothing is
+// left to a later synchronisation but the queue overflow every device call shares (TKAMD_NO_SPECULATION).
+int tkamd_encode_batch_device_dense(tkamd_tokenizer* t, const uint8_t* d_text, const int64_t* d_doc_offsets, int64_t n_docs, int64_t n_bytes,
+                                    uint32_t flags, void* hip_stream, const tkamd_dense_out* dst, tkamd_device_result* out) {
+    if (!dst) return set_error(TKAMD_ERR_INVALID, "bad argument");
+    return encode_device(t, d_text, d_doc_offsets, n_docs, n_bytes, nullptr, -1, flags | TKAMD_WANT_DENSE | TKAMD_NO_SPECULATION, hip_stream, out, dst);
+}
+int tkamd_dense_width(const tkamd_tokenizer* t, uint32_t flags, int64_t* width) {
+    if (!t || !width) return set_error(TKAMD_ERR_INVALID, "null argument");
+    return guarded([&]() -> int {
+        *width = dense_width_of(t->hm, flags);
+        return TKAMD_OK;
+    });
 }
 
 int tkamd_device_sync(tkamd_tokenizer* t, void* hip_stream, int64_t* n_tokens, int64_t* n_pretokens) {

@@ -263,11 +263,30 @@ Step Batch::finalize() {
     return Step::Done;
 }
 
+// TKAMD_WANT_DENSE: the published result -> the caller's padded [n_rows, width] arrays (kernels/dense.hip).  check_request has settled
+// that every row is `width` tokens long and that the arrays asked for have a source; the kernel reports a row that is not (ERR_INTERNAL).
+void Batch::dense_rows() {
+    const tkamd_dense_out& dd = w->last_dense;
+    DenseArgs da{};
+    da.tok_offsets = out->d_tok_offsets; da.ids = out->d_ids; da.pad_count = out->d_pad_counts; da.type_ids = out->d_type_ids; da.seq_ids = out->d_seq_ids;
+    da.offsets = dd.offsets ? out->d_offsets : nullptr; da.word_ids = dd.word_ids ? out->d_word_ids : nullptr;
+    da.input_ids = dd.input_ids; da.attention_mask = dd.attention_mask; da.token_type_ids = dd.token_type_ids; da.special_tokens_mask = dd.special_tokens_mask;
+    da.offset_mapping = da.offsets ? dd.offsets : nullptr; da.out_word_ids = da.word_ids ? dd.word_ids : nullptr;
+    da.n_rows = dd.n_rows; da.width = dd.width;
+    da.pad_left = hm.pad_left ? 1u : 0u; da.n_prefix = add_special ? (uint32_t)hm.pp_prefix.size() : 0u; da.n_suffix = add_special ? (uint32_t)hm.pp_suffix.size() : 0u;
+    da.pad_id = hm.pad_id; da.pad_type_id = hm.pad_type_id; da.err = d_err;
+    pf.begin("dense_rows");
+    launch_dense_rows(st, grid, da, (dd.dtype_flags & TKAMD_DENSE_I32) != 0);
+    pf.end();
+    out->ids_capacity = dd.n_rows * dd.width;
+}
+
 Step Batch::epilogue() {
     Step step = Step::Done;
     if (pairs) step = finalize_pairs();
     else if (has_epilogue) step = finalize();
     else if (add_special) add_specials();
     if (step == Step::Done) w->last_ntok_slot = (add_special || has_epilogue) ? SC_NTOK2 : SC_NTOK;
+    if (step == Step::Done && want_dense) dense_rows();
     return step;
 }

@@ -57,6 +57,10 @@ struct Workspace {
     DevBuf w_mask_dirty;                        // one word: the four added-token match masks may hold bits (Batch::scatter_masks, capi/pipeline.cpp)
     int64_t last_n_bytes = 0;
     uint32_t last_flags = 0;
+    // the dense entry's destination (tkamd_encode_batch_device_dense): kept next to last_flags because a batch that is run again
+    // (finish_batch) runs from them and refills the caller's arrays; has_dense: the call being enqueued came through that entry
+    tkamd_dense_out last_dense{};
+    bool has_dense = false;
     tkamd_device_result last_result{};
     int64_t last_n_docs = 0;
     int64_t last_n_enc = -1;                    // encodings of the last call when it materialised overflowing ones, else -1

@@ -88,6 +88,7 @@ struct Batch {
     // check_request
     bool mixed = false, want_words = false, want_meta = false, add_special = false, prefix_space = false, metaspace = false, words_in = false, pairs = false;
     bool typed_single = false, has_epilogue = false, want_overflow = false;
+    bool want_dense = false;       // TKAMD_WANT_DENSE: the dense stage ends the epilogue (w->last_dense says where to)
     bool precomp = false;          // behind a Precompiled or an NFKC normalizer: the "▁" front reads its output (normalize_precompiled / normalize_nfkc)
     bool nfkc = false;             // ... the second of the two: normalized added tokens are matched over that output (pass 2)
     int64_t n_p = 0;               // ... the host's bound of that text
@@ -130,13 +131,38 @@ struct Batch {
     void* phases_of(int which);
     void open_word_cache();
     // the epilogues and what they share
-    void add_specials(); Step finalize(); Step finalize_pairs();
+    void add_specials(); Step finalize(); Step finalize_pairs(); void dense_rows();
     uint64_t batch_longest(uint32_t* d_target, bool* again);
     int64_t read_overflow_count(int64_t n_min);
     size_t padded_capacity(const FinalArgs& fa, bool overflow, int64_t n_rows, size_t T2, const char* noun, bool* again);
     void publish_results(uint32_t* ids2, int64_t capacity, int64_t* tok_offsets2, uint32_t* offsets2, uint32_t* word_ids2, int64_t* n_tok2, uint32_t* pad_count = nullptr,
                          uint8_t* type_ids2 = nullptr, uint8_t* seq_ids2 = nullptr, int64_t n_enc = -1, const uint32_t* enc_doc = nullptr, const uint32_t* enc_idx = nullptr);
 };
+
+// The row width a handle guarantees for dense output (tkamd_dense_width), or why it guarantees none: every encoding must come out of the
+// epilogue exactly that long, and the caller must know the number before the call.
+int64_t dense_width_of(const HostModel& hm, uint32_t flags) {
+    if (!hm.trunc_on) throw Invalid("dense output needs a `truncation` section (enable_truncation): without one a row has no upper bound");
+    if (!hm.pad_on) throw Invalid("dense output needs a `padding` section (enable_padding with a length)");
+    if (!hm.pad_fixed) throw Invalid("dense output needs Fixed padding (enable_padding(length=...)): with BatchLongest the width is known on the device only");
+    uint64_t width = hm.pad_length;
+    if (hm.pad_multiple > 0 && width % hm.pad_multiple > 0) width += hm.pad_multiple - width % hm.pad_multiple;
+    if (width < 1) throw Invalid("dense output: the padding length is 0");
+    if ((uint64_t)hm.trunc_max_length > width)
+        throw Invalid("dense output: truncation max_length " + std::to_string(hm.trunc_max_length) + " exceeds the padded width " + std::to_string(width) + ": rows would differ in length");
+    if (flags & TKAMD_ADD_SPECIAL) {
+        // (below the number of special tokens the reference's max_length - n_added_tokens wraps and nothing is cut: Batch::finalize)
+        uint64_t n_add = hm.pp_prefix.size() + hm.pp_suffix.size();
+        if (flags & TKAMD_PAIRS) {
+            n_add = 0;
+            for (const HostModel::TplPiece& q : hm.pp_pair) n_add += q.kind == 2u;
+        }
+        if ((uint64_t)hm.trunc_max_length < n_add)
+            throw Invalid("dense output: truncation max_length " + std::to_string(hm.trunc_max_length) + " is below the " + std::to_string(n_add) +
+                          " special tokens the template adds: nothing would be truncated");
+    }
+    return (int64_t)width;
+}
 
 // Decodes the flags and refuses what the build or the batch's size does not allow, in front of all device work.
 void Batch::check_request() {
@@ -214,6 +240,22 @@ void Batch::check_request() {
     // Encoding.overflowing: what a truncation cuts off, as further encodings of the result (a pair leaves every combination of its two
     // sequences' windows, Encoding::merge_with encoding.rs:408-432)
     want_overflow = (flags & TKAMD_WANT_OVERFLOW) != 0 && hm.trunc_on;
+    want_dense = (flags & TKAMD_WANT_DENSE) != 0;
+    if (want_dense) {
+        // everything the dense stage relies on is settled here, in front of all device work (the width's conditions: dense_width_of)
+        if (!w->has_dense) throw Invalid("TKAMD_WANT_DENSE: only tkamd_encode_batch_device_dense takes this flag");
+        const tkamd_dense_out& dd = w->last_dense;
+        if (flags & TKAMD_WANT_OVERFLOW) throw Invalid("dense output with TKAMD_WANT_OVERFLOW: the number of rows would be known on the device only");
+        if (words_in || mixed) throw Invalid("dense output of pre-tokenized or mixed inputs: these entries do not exist yet");
+        if (!t->replicas.empty()) throw Invalid("dense output on a multi-device handle: the dense entry runs on one device, make a handle for it");
+        if (!dd.input_ids) throw Invalid("dense output: input_ids is null");
+        if (dd.dtype_flags & ~TKAMD_DENSE_I32) throw Invalid("dense output: unknown dtype_flags");
+        if (dd.offsets && off_mode == TKAMD_OFFSETS_NONE) throw Invalid("dense output: offsets asked for without an offsets mode in flags (TKAMD_OFFSETS_BYTE / TKAMD_OFFSETS_CHAR)");
+        if (dd.word_ids && !want_words) throw Invalid("dense output: word_ids asked for without TKAMD_WANT_WORD_IDS in flags");
+        const int64_t width = dense_width_of(hm, flags), rows = pairs ? e_n / 2 : e_n;
+        if (dd.n_rows != rows) throw Invalid("dense output: n_rows is " + std::to_string(dd.n_rows) + ", the batch has " + std::to_string(rows) + (pairs ? " pairs" : " documents"));
+        if (dd.width != width) throw Invalid("dense output: width is " + std::to_string(dd.width) + ", tkamd_dense_width says " + std::to_string(width));
+    }
     W0 = (n_bytes >> 6) + 1;
     W = (n_x >> 6) + 1;
     grid = t->n_cu * 8;

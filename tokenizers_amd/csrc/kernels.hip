@@ -20,6 +20,7 @@
 //        │──────scan_emit──────► pt_start[P+1] only when offsets / word ids are requested          kernels/scan_emit.hip
 //        │──────output─────────► ids[T] (single-pass compaction over published chunk totals), per-document CSR,      kernels/output.hip, results.hip
 //        │                       offsets, word ids, specials
+//   result ─────dense──────────► input_ids / attention_mask / ... as padded [B, L] int64 / int32 arrays (TKAMD_WANT_DENSE)   kernels/dense.hip
 //   ids ────────decode─────────► text (decode_batch)                                              kernels/decode.hip
 //   id per stream ─decode_stream► the text that became printable (DecodeStream, around the range decode)   kernels/decode_stream.hip
 //
@@ -34,6 +35,7 @@
 #include "device_utils.hpp"
 #include "kernels.hpp"
 #include "overflow_core.hpp"
+#include "dense_core.hpp"
 #include "merge_pair_plan_core.hpp"
 #include "bert_norm_core.hpp"
 #include "nfc_core.hpp"
@@ -113,6 +115,7 @@ static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)(
 #include "kernels/bpe_huge.hip"
 #include "kernels/output.hip"
 #include "kernels/epilogue.hip"
+#include "kernels/dense.hip"
 #include "kernels/decode.hip"
 #include "kernels/decode_stream.hip"
 #include "kernels/launch.hip"

@@ -252,6 +252,22 @@ struct FinalArgs {
     uint32_t pad_type_id;
 };
 
+// arguments of the dense stage (k_dense_rows, kernels/dense.hip; TKAMD_WANT_DENSE): the published result of a batch in, up to six
+// [n_rows, width] arrays of int64 or int32 in caller-owned memory out (dense_core.hpp decides every element)
+struct DenseArgs {
+    const int64_t* tok_offsets;       // [n_rows + 1] the published CSR: row r is tokens [tok_offsets[r], tok_offsets[r + 1])
+    const uint32_t* ids;
+    const uint32_t* pad_count;        // [n_rows]
+    const uint8_t* type_ids;          // null: 0, pad_type_id on padding
+    const uint8_t* seq_ids;           // null: the layout follows from pad_count, pad_left, n_prefix, n_suffix
+    const uint32_t* offsets;          // null unless offset_mapping is written
+    const uint32_t* word_ids;         // null unless out_word_ids is written
+    void *input_ids, *attention_mask, *token_type_ids, *special_tokens_mask, *offset_mapping, *out_word_ids;      // all but input_ids may be null
+    int64_t n_rows, width;
+    uint32_t pad_left, n_prefix, n_suffix, pad_id, pad_type_id;
+    int* err;
+};
+
 // arguments of the PAIR epilogue (k_pair_*): documents 2i / 2i+1 are sequence A / B of encoding i (tokenizer/mod.rs:871-889)
 struct PairArgs {
     const int64_t* tok_offsets;       // token CSR over the 2 * n_pairs documents
@@ -442,6 +458,8 @@ void launch_overflow_count(hipStream_t st, const FinalArgs& a, int64_t* n_enc);
 void launch_overflow_ranges(hipStream_t st, const FinalArgs& a);
 void launch_final_offsets(hipStream_t st, const FinalArgs& a);
 void launch_finalize(hipStream_t st, int grid, const FinalArgs& a);
+// the dense stage: i32 = the outputs hold int32 elements, else int64; nothing is launched for an empty batch
+void launch_dense_rows(hipStream_t st, int grid, const DenseArgs& a, bool i32);
 void launch_pair_lens(hipStream_t st, const PairArgs& a);
 // overflowing encodings of pairs: launch_pair_lens (with ovf_parts set) counts them; this numbers them (*n_enc = how many), then
 // launch_pair_ranges -- a.n_pairs still the number of PAIRS -- writes every encoding's windows, its length and the batch maximum

@@ -441,6 +441,15 @@ void launch_zero_tail(hipStream_t st, uint8_t* p, const int64_t* len_dev, int n,
 void launch_zero_regions(hipStream_t st, int grid, const ZeroRegions& z) {
     if (z.n > 0) hipLaunchKernelGGL(k_zero_regions, dim3(grid), dim3(256), 0, st, z);
 }
+void launch_dense_rows(hipStream_t st, int grid, const DenseArgs& a, bool i32) {
+    const int64_t total = a.n_rows * a.width;
+    if (total <= 0) return;
+    // a lane owns 16 bytes of every output (2 int64 or 4 int32 elements); beyond `grid` workgroups the kernel strides
+    const int64_t groups = (total + (i32 ? 3 : 1)) / (i32 ? 4 : 2);
+    const unsigned nb = (unsigned)std::min<int64_t>((groups + 255) / 256, (int64_t)std::max(grid, 1));
+    if (i32) hipLaunchKernelGGL((k_dense_rows<int32_t>), dim3(nb), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_dense_rows<int64_t>), dim3(nb), dim3(256), 0, st, a);
+}
 int compact_grid(int n_cu) {
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_compact<CP_ITEMS_PER_LANE>, CP_NT, 0) != hipSuccess || per_cu < 1) per_cu = 1;

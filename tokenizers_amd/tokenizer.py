@@ -515,6 +515,46 @@ class DeviceText:
         return [buf[off[i]:off[i + 1]].decode("utf-8") for i in range(self.n_docs)]
 
 
+class TensorBatch:
+    """Result of :meth:`Tokenizer.encode_tensor`: a read-only mapping with transformers' key names -- ``input_ids``, ``attention_mask``
+    and, as asked for, ``token_type_ids``, ``special_tokens_mask``, ``offset_mapping``, ``word_ids`` -- onto ``[B, L]`` torch tensors
+    on the tokenizer's device.  The tensors are final when the stream the call ran on reaches them; nothing has waited for it.  The
+    batch holds on to the text it was encoded from: :meth:`sync` may read it again."""
+
+    def __init__(self, tensors: dict, batch: DeviceBatch, keep: tuple):
+        self._tensors, self._batch, self._keep = tensors, batch, keep
+
+    def __getitem__(self, key: str):
+        return self._tensors[key]
+
+    def __iter__(self):
+        return iter(self._tensors)
+
+    def __len__(self) -> int:
+        return len(self._tensors)
+
+    def __contains__(self, key) -> bool:
+        return key in self._tensors
+
+    def keys(self):
+        return self._tensors.keys()
+
+    def values(self):
+        return self._tensors.values()
+
+    def items(self):
+        return self._tensors.items()
+
+    def sync(self) -> "TensorBatch":
+        """``tkamd_device_sync``: waits for the batch and raises what its error word says.  The one thing it may repair is a work
+        queue that overflowed: the batch then runs again and fills the same tensors."""
+        self._batch.sync()
+        return self
+
+    def __repr__(self) -> str:
+        return "TensorBatch(%s)" % ", ".join(f"{k}: {tuple(v.shape)}" for k, v in self._tensors.items())
+
+
 class DecodeStreams:
     """``tokenizers.decoders.DecodeStream`` for ``n_streams`` running sequences at once (:meth:`Tokenizer.decode_stream`): one new id
     per stream and step in, the text that just became printable out -- what ``n_streams`` DecodeStreams of the reference return, with
@@ -1326,6 +1366,155 @@ class Tokenizer:
         # `truncation` / `padding` section runs the epilogue, whose output the text does not bound: the library reports 0, no
         # unsynchronised view then.
         return DeviceBatch(self, res, n_docs, stream, capacity=int(res.ids_capacity))
+
+    # ---- dense output: padded [B, L] arrays in the caller's HBM (tkamd_encode_batch_device_dense) ----
+    def _dense_flags(self, offsets: str, word_ids: bool, add_special_tokens: bool, pairs: bool) -> int:
+        flags = {"none": _lib.OFFSETS_NONE, "byte": _lib.OFFSETS_BYTE, "char": _lib.OFFSETS_CHAR}[offsets]
+        if word_ids:
+            flags |= _lib.WANT_WORD_IDS
+        if pairs:
+            flags |= _lib.PAIRS
+        if add_special_tokens:
+            if not pairs:
+                self._check_special(True)
+            flags |= _lib.ADD_SPECIAL
+        return flags
+
+    def dense_width(self, add_special_tokens: bool = True, pairs: bool = False) -> int:
+        """The row width ``L`` of this tokenizer's dense output (``tkamd_dense_width``): the Fixed padding length rounded up to
+        ``pad_to_multiple_of``.  ``ValueError`` naming the missing piece where the handle guarantees no width: it needs
+        ``enable_truncation(max_length)`` and ``enable_padding(length=...)`` with ``max_length <= L``."""
+        width = C.c_int64(0)
+        _lib.check(self._lib.tkamd_dense_width(self._h, self._dense_flags("none", False, add_special_tokens, pairs), C.byref(width)))
+        return width.value
+
+    def encode_batch_device_dense(self, d_text_ptr: int, d_doc_offsets_ptr: int, n_docs: int, n_bytes: int, out_ptrs: dict, width: int,
+                                  dtype: str = "int64", pairs: bool = False, add_special_tokens: bool = True, offsets: str = "none",
+                                  word_ids: bool = False, stream: int = 0) -> DeviceBatch:
+        """Text already in HBM (raw device pointers; TEXT_PAD readable slack behind it) -> ``[n_rows, width]`` arrays of ``dtype``
+        (``int64`` / ``int32``) at the raw device pointers of ``out_ptrs``: ``input_ids`` (required) and any of ``attention_mask``,
+        ``token_type_ids``, ``special_tokens_mask``, ``offset_mapping`` (``[n_rows, width, 2]``; needs ``offsets``), ``word_ids`` (-1:
+        None; needs ``word_ids=True``).  ``n_rows`` is ``n_docs``, or ``n_docs // 2`` with ``pairs`` (documents 2i / 2i + 1 -> row i).
+        Enqueue only; the arrays are final when ``stream`` reaches them (only a work-queue overflow is left to
+        :meth:`DeviceBatch.sync`, which then fills them again).  The text and the arrays must outlive the batch."""
+        if dtype not in ("int64", "int32"):
+            raise ValueError("dtype must be 'int64' or 'int32'")
+        known = ("input_ids", "attention_mask", "token_type_ids", "special_tokens_mask", "offset_mapping", "word_ids")
+        unknown = [k for k in out_ptrs if k not in known]
+        if unknown:
+            raise ValueError(f"out_ptrs: unknown outputs {unknown}; known: {list(known)}")
+        p = lambda k: int(out_ptrs.get(k) or 0) or None
+        n_rows = n_docs // 2 if pairs else n_docs
+        dst = _lib.DenseOut(p("input_ids"), p("attention_mask"), p("token_type_ids"), p("special_tokens_mask"), p("offset_mapping"), p("word_ids"),
+                            n_rows, int(width), _lib.DENSE_I32 if dtype == "int32" else 0)
+        res = _lib.DeviceResult()
+        _lib.check(self._lib.tkamd_encode_batch_device_dense(self._h, d_text_ptr, d_doc_offsets_ptr, n_docs, n_bytes,
+                                                             self._dense_flags(offsets, word_ids, add_special_tokens, pairs), stream,
+                                                             C.byref(dst), C.byref(res)))
+        return DeviceBatch(self, res, n_rows, stream, capacity=int(res.ids_capacity))
+
+    def _device_text_of(self, input, dev):
+        """(uint8 text tensor with TEXT_PAD readable bytes behind the text, int64 offsets tensor, n_docs, n_bytes, pairs, what to keep
+        alive) of any input :meth:`encode_tensor` takes."""
+        import torch
+        if isinstance(input, DeviceText):
+            if input.n_bytes < 0:
+                raise ValueError("encode_tensor: the text of a fused stream step has no host-side byte count; pass (bytes_tensor(), doc_offsets_tensor())")
+            # (the decode leaves TEXT_PAD zero bytes behind its text)
+            text = input._tensor(input.bytes_ptr, (input.n_bytes + _lib.TEXT_PAD,), "|u1")
+            return text, input.doc_offsets_tensor(), input.n_docs, input.n_bytes, False, (input,)
+        if isinstance(input, (tuple, list)) and len(input) == 2 and all(isinstance(x, torch.Tensor) for x in input):
+            text, off = input
+            if text.dtype != torch.uint8 or off.dtype != torch.int64 or text.dim() != 1 or off.dim() != 1 or off.numel() < 1:
+                raise ValueError("encode_tensor: a device text is a (1-D uint8 text tensor, 1-D int64 offsets tensor of n_docs + 1 entries) pair")
+            if text.device != dev or off.device != dev:
+                raise ValueError(f"encode_tensor: the text and its offsets must live on {dev}")
+            return text.contiguous(), off.contiguous(), off.numel() - 1, None, False, ()
+        items = list(input)
+        pairs = len(items) > 0 and isinstance(items[0], (tuple, list))
+        if pairs:
+            flat = []
+            for it in items:
+                if not isinstance(it, (tuple, list)) or len(it) != 2 or not isinstance(it[0], str) or not isinstance(it[1], str):
+                    raise UnsupportedError("encode_tensor: a batch holds either single sequences (str) or pairs (str, str)")
+                flat.extend(it)
+            items = flat
+        # one page-locked block: the text (with its slack), then the offsets at the next multiple of 8 -- one copy down, nothing comes back
+        with self._stage_lock:
+            buf, off = self._pack_staged(items)
+            n_text = len(buf)
+            at = (n_text + 7) & ~7
+            block = pinned_empty(at + 8 * len(off), dtype=np.uint8) if self.device >= 0 and not _FORKED[0] else np.empty(at + 8 * len(off), dtype=np.uint8)
+            block[:n_text] = buf
+            block[at:] = np.frombuffer(np.ascontiguousarray(off, dtype=np.int64), dtype=np.uint8)
+            n_bytes = int(off[-1])
+        down = torch.from_numpy(block).to(dev, non_blocking=True)
+        return down[:n_text], down[at:].view(torch.int64), len(items), n_bytes, pairs, (down, block)
+
+    def encode_tensor(self, input, add_special_tokens: bool = True, dtype=None, return_token_type_ids: bool = True,
+                      return_special_tokens_mask: bool = False, return_offsets_mapping: bool = False, return_word_ids: bool = False,
+                      out: dict | None = None) -> "TensorBatch":
+        """Encode straight into padded ``[B, L]`` torch tensors on this tokenizer's device, on the current stream, without waiting for it.
+
+        ``input``: a ``list[str]``; a ``list[tuple[str, str]]`` (pairs); a :class:`DeviceText` (what :meth:`decode_tensor` returns); or
+        a ``(uint8 text tensor, int64 offsets tensor)`` pair on the device.  Host strings go down once, in one page-locked block;
+        nothing comes back.  ``dtype``: ``torch.int64`` (default) or ``torch.int32`` for every tensor.  ``return_offsets_mapping``
+        gives char offsets, like :meth:`encode_batch`.  ``out``: preallocated tensors by key (``input_ids``, ``attention_mask``, ...)
+        to write into instead of fresh ones.  The tokenizer needs ``enable_truncation`` and ``enable_padding(length=...)``
+        (:meth:`dense_width`)."""
+        import torch
+        dtype = torch.int64 if dtype is None else dtype
+        if dtype not in (torch.int64, torch.int32):
+            raise ValueError("encode_tensor: dtype must be torch.int64 or torch.int32")
+        if self.device < 0:
+            raise DeviceError("host-only tokenizer handle: no HIP device bound (there is no CPU fallback)")
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            text, off, n_docs, n_bytes, pairs, keep = self._device_text_of(input, dev)
+            width = self.dense_width(add_special_tokens, pairs)
+            if n_docs % 2 and pairs:
+                raise ValueError("encode_tensor: an odd number of documents cannot be pairs")
+            n_rows = n_docs // 2 if pairs else n_docs
+            if n_bytes is None:
+                # a (text, offsets) pair: the tensor is the text (offsets[-1] == its length).  The kernels read whole words up to TEXT_PAD
+                # bytes beyond it: a tensor whose storage goes on that far (a slice of a larger buffer) is read where it lies, any
+                # other is copied into one that has the slack
+                n_bytes = text.numel()
+                if text.untyped_storage().nbytes() - text.storage_offset() < n_bytes + _lib.TEXT_PAD:
+                    padded = torch.zeros(n_bytes + _lib.TEXT_PAD, dtype=torch.uint8, device=dev)
+                    padded[:n_bytes] = text
+                    keep = keep + (text,)
+                    text = padded
+            want = {"input_ids": True, "attention_mask": True, "token_type_ids": return_token_type_ids, "special_tokens_mask": return_special_tokens_mask,
+                    "offset_mapping": return_offsets_mapping, "word_ids": return_word_ids}
+            out = dict(out or {})
+            unknown = [k for k in out if k not in want]
+            if unknown:
+                raise ValueError(f"encode_tensor: out holds unknown keys {unknown}; known: {list(want)}")
+            tensors = {}
+            for k, on in want.items():
+                shape = (n_rows, width, 2) if k == "offset_mapping" else (n_rows, width)
+                if k in out:
+                    x = out[k]
+                    if not isinstance(x, torch.Tensor) or tuple(x.shape) != shape:
+                        raise ValueError(f"encode_tensor: out[{k!r}] must be a tensor of shape {shape}, got {tuple(getattr(x, 'shape', ()))}")
+                    if x.dtype != dtype:
+                        raise ValueError(f"encode_tensor: out[{k!r}] must be {dtype}, got {x.dtype}")
+                    if x.device != dev:
+                        raise ValueError(f"encode_tensor: out[{k!r}] must live on {dev}, got {x.device}")
+                    if not x.is_contiguous():
+                        raise ValueError(f"encode_tensor: out[{k!r}] must be contiguous (strides {tuple(x.stride())})")
+                    tensors[k] = x
+                elif on:
+                    tensors[k] = torch.empty(shape, dtype=dtype, device=dev)
+            ptrs = {k: x.data_ptr() for k, x in tensors.items() if x.numel()}
+            if not n_rows:
+                ptrs["input_ids"] = tensors["input_ids"].data_ptr() or text.data_ptr()      # (nothing is written: any device address)
+            batch = self.encode_batch_device_dense(text.data_ptr(), off.data_ptr(), n_docs, n_bytes, ptrs, width,
+                                                   "int64" if dtype == torch.int64 else "int32", pairs, add_special_tokens,
+                                                   "char" if "offset_mapping" in tensors else "none", "word_ids" in tensors,
+                                                   torch.cuda.current_stream(dev).cuda_stream)
+        return TensorBatch(tensors, batch, keep + (text, off))
 
     def word_cache(self, enable: bool = True, clear: bool = False) -> None:
         """The device-side counterpart of the reference's per-thread BPE word cache (models/bpe/model.rs:573-586): words of <= 16
