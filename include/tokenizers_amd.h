@@ -524,6 +524,27 @@ int tkamd_encode_special_tokens(tkamd_tokenizer* tok, int value);
  * : on text that never repeats a word they only cost. */
 int tkamd_word_cache(tkamd_tokenizer* tok, int enable, int clear);
 
+/* ---- the hot-word table learns the handle's text ---------------------------------------------
+ * The lookup kernel keeps 960 settled words of <= 12 bytes in LDS (csrc/tables.hpp); a pre-token that is one of them costs no memory
+ * round trip.  At load these are the lowest ids.  The handle's first batch of >= 8 MiB of text, and every 1024th such batch after it,
+ * also counts which words stand as whole pre-tokens in a 1 MiB sample of it (k_hot_census, csrc/kernels/lookup.hip); the call that
+ * synchronises that batch (tkamd_device_sync, or any host entry) reads the counts, and if the table they select would have settled two
+ * points more of the sample it replaces the one in use, for every later batch of the handle on any stream.  Results never depend on
+ * what the table holds.  A caller that never synchronises through the library keeps the load-time table; so does a multi-device handle.
+ * `enable` == 0 stops the censuses (the table in use stays); the environment variable TKAMD_HOT_ADAPT=0, read when a handle is made,
+ * does the same from the start.  At most seven tables replace the load-time one in a handle's life (old ones are kept until it is
+ * freed: a launch enqueued on another stream may still read one); after that it keeps what it has. */
+int tkamd_hot_adapt(tkamd_tokenizer* tok, int enable);
+/* Diagnostics: the table in use (`blob`, up to blob_cap bytes: 1024 16-byte slots {key bytes 0..11, id | len << 24}, then 256 16-bit
+ * displacements), the ids of the words that may ever stand in it (`eligible_ids`, up to ids_cap; *n_eligible: how many there are), and
+ * stats[8] = {rebuilds so far, words in the table, pre-tokens the last census sampled, 1/10000ths of them the table then in use settles,
+ * ... the table its counts selected, the tables' hash seed, 1 if the handle adapts, slots}.  Any pointer may be null.  Returns the
+ * table's size in bytes (0 on a host-only handle). */
+int tkamd_hot_table_read(tkamd_tokenizer* tok, void* blob, int64_t blob_cap, uint32_t* eligible_ids, int64_t ids_cap, int64_t* n_eligible, uint32_t* stats);
+/* ... and what the last census counted: counts[i] = sampled pre-tokens that were the word eligible_ids[i].  Returns how many counts
+ * there are (0 before the first census was read). */
+int64_t tkamd_hot_census_counts(tkamd_tokenizer* tok, uint32_t* counts, int64_t cap);
+
 /* ---- measurement hooks (bench.py roofline leg; not part of the reference surface) -----------
  * With profiling on, every kernel launch of the next device/host encode calls is bracketed by
  * HIP events on the launch stream.  tkamd_profile_read returns, per kernel, the accumulated
@@ -542,7 +563,8 @@ int tkamd_profile_read(tkamd_tokenizer* tok, tkamd_stage_time* stages, int max_s
  * adaptive settings (out[13..17]), the shape of the load-time tables, filled from the handle also before its first batch:
  * out[18] = slots of the short-word table, out[19] = its displacement buckets, out[20] = its largest displacement,
  * out[21] = slots of the merge table (out[18..20] are 0 on a host-only handle).  out[22] = the grid of the last batch's launch that
- * merges both LDS queues side by side (0: the batch ran none). */
+ * merges both LDS queues side by side (0: the batch ran none).  out[23..27]: the hot-word table -- rebuilds so far, words in it, and
+ * of the last census the sampled pre-tokens and the 1/10000ths of them the table then in use / the table selected settle. */
 int tkamd_profile_counters(tkamd_tokenizer* tok, uint32_t* out, int n);
 
 /* Where the two longest kernels spend their time.  With the test hook TKAMD_PHASES (TKAMD_TEST_HOOKS=1 TKAMD_PHASES=1) the whole-word

@@ -50,6 +50,7 @@ SYMBOLS = [
     "tkamd_decode_stream_new", "tkamd_decode_stream_free", "tkamd_decode_stream_reset", "tkamd_decode_stream_seed", "tkamd_decode_stream_step",
     "tkamd_decode_stream_read", "tkamd_decode_stream_peek", "tkamd_decode_stream_info",
     "tkamd_dense_width", "tkamd_encode_batch_device_dense",
+    "tkamd_hot_adapt", "tkamd_hot_table_read", "tkamd_hot_census_counts",
 ]
 COLLECT_HOST, COLLECT_ROOT_P2P, COLLECT_ROOT_RCCL = 0, 1, 2
 
@@ -162,6 +163,12 @@ def load() -> C.CDLL:
     lib.tkamd_dense_width.restype = i32
     lib.tkamd_encode_batch_device_dense.argtypes = [vp, vp, vp, i64, i64, u32, vp, C.POINTER(DenseOut), C.POINTER(DeviceResult)]
     lib.tkamd_encode_batch_device_dense.restype = i32
+    lib.tkamd_hot_adapt.argtypes = [vp, i32]
+    lib.tkamd_hot_adapt.restype = i32
+    lib.tkamd_hot_table_read.argtypes = [vp, vp, i64, C.POINTER(u32), i64, C.POINTER(i64), C.POINTER(u32)]
+    lib.tkamd_hot_table_read.restype = i32
+    lib.tkamd_hot_census_counts.argtypes = [vp, C.POINTER(u32), i64]
+    lib.tkamd_hot_census_counts.restype = i64
     lib.tkamd_word_cache.argtypes = [vp, i32, i32]
     lib.tkamd_word_cache.restype = i32
     lib.tkamd_device_sync.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64)]

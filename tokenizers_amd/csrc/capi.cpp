@@ -27,6 +27,7 @@
 #include "overflow_core.hpp"
 #include "bert_norm_core.hpp"
 #include "utf8_lossy_core.hpp"
+#include "hot_table_core.hpp"
 
 using namespace tkamd;
 static_assert(TEXT_PAD == TKAMD_TEXT_PAD, "the kernels rely on the slack the ABI promises");

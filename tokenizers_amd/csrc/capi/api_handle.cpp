@@ -29,6 +29,12 @@ static std::unique_ptr<tkamd_tokenizer> make_tokenizer(const char* json, size_t 
         if (!primary) verify_direct_words(t.get());
         build_shortw_table(t.get());
         build_hot_table(t.get());
+        // the hot table's adaptation: TKAMD_HOT_ADAPT=0 keeps the load-time table for the handle's life; a replica of a multi-device handle
+        // never adapts (its shards synchronise on threads of their own: DESIGN section 2)
+        if (const char* e = getenv("TKAMD_HOT_ADAPT")) t->hot_adapt = strcmp(e, "0") != 0;
+        if (primary) t->hot_adapt_allowed = false;
+        if (const char* e = test_hook("TKAMD_HOT_CENSUS_MIN_BYTES")) t->hot_min_bytes = std::max<int64_t>(0, atoll(e));
+        if (const char* e = test_hook("TKAMD_HOT_CENSUS_PERIOD")) t->hot_period = std::max<int64_t>(1, atoll(e));
         if (const char* e = test_hook("TKAMD_CLAIMS_PAUSE")) t->claims_pause_len = std::max(0, atoi(e));
         if (const char* e = test_hook("TKAMD_ADDED_SPEC")) t->added_spec_len = std::max(0, atoi(e));
         if (const char* e = test_hook("TKAMD_NFC_SPEC")) t->nfc_spec_len = std::max(0, atoi(e));      // (0: always normalize; n: the pause behind a failed quick check)
@@ -83,6 +89,7 @@ int tkamd_tokenizer_from_json_devices(const char* json, size_t json_len, const i
         std::unique_ptr<tkamd_tokenizer> t = make_tokenizer(json, json_len, devs[0], nullptr);
         for (size_t r = 1; r < devs.size(); ++r) {
             t->replicas.push_back(make_tokenizer(nullptr, 0, devs[r], t.get()));
+            t->hot_adapt_allowed = false;
             // the peers push their shards to devices[0] over xGMI (COLLECT_ROOT_P2P): let them map its memory
             if (devs[r] != devs[0]) {
                 const hipError_t e = hipDeviceEnablePeerAccess(devs[0], 0);

@@ -72,6 +72,9 @@ struct Workspace {
     bool last_note_nfc = false;                  // the batch synchronised last was run over the text as it came and holds a lane that is not known to be NFC
     bool last_note_added = false;                // the batch synchronised last was speculative and met an added token's content (read_scalars)
     bool last_used_claims = false;               // the batch enqueued last ran with the in-batch claims
+    DevBuf w_hot_hist;                           // the hot table's census (kernels/lookup.hip k_hot_census): a count per short-word slot, then the sampled pre-tokens
+    std::vector<uint32_t> h_hot_hist;            // ... on the host, copied at the synchronisation of a batch that took one
+    bool census_pending = false;                 // a batch enqueued since the last synchronisation took a census (read_scalars reads it)
     ~Workspace() {
         if (own_stream) (void)hipStreamDestroy(own_stream);
         if (io_in) (void)hipStreamDestroy(io_in);
@@ -123,6 +126,28 @@ struct tkamd_tokenizer {
     int nfc_spec_len = 32;
     int added_spec_len = 32;     // (test hook TKAMD_ADDED_SPEC: 0 never speculate; n: the pause behind a miss)
     int claims_pause_len = 32;   // (test hook TKAMD_CLAIMS_PAUSE; 0: never pause)
+    // The hot table LEARNS which words stand as whole pre-tokens in this handle's text.  The handle's first batch of
+    // hot_min_bytes of text or more (the caller's bytes), and every hot_period-th such batch after it, takes a census behind its mask scan (Batch::hot_census);
+    // the synchronisation of that batch reads the counts, and if the table they select would have settled hot_gain more of the sample than
+    // the table in use, it is built, uploaded into a buffer of its own and becomes the one every later launch reads (hot_census_read).
+    // Old buffers are kept until the handle goes -- a launch enqueued on another stream may still read one -- so the ring bounds the number
+    // of rebuilds: HOT_RING tables, then the handle keeps what it has.  Results never depend on the table's contents.
+    std::atomic<bool> hot_adapt{true};           // tkamd_hot_adapt / TKAMD_HOT_ADAPT=0; never on a multi-device handle
+    bool hot_adapt_allowed = true;
+    int64_t hot_min_bytes = 8 << 20;             // (test hook TKAMD_HOT_CENSUS_MIN_BYTES.  The sample is 1 MiB of the batch; the threshold is 8 MiB because the claims' races
+                                                 // queue a few percent more words behind a learned table and an existing GPU test of 4 MB batches holds the queue length to 2 %)
+    int64_t hot_period = 1024;                   // (test hook TKAMD_HOT_CENSUS_PERIOD)
+    std::atomic<uint64_t> hot_eligible{0};       // eligible batches enqueued so far
+    std::atomic<const void*> hot_cur{nullptr};   // the table the lookup launches read
+    std::vector<std::unique_ptr<DevBuf>> hot_ring;       // the tables that replaced t_hot, oldest first (under mu)
+    std::atomic<uint32_t> hot_gen{0};            // rebuilds so far
+    std::vector<HotWord> hot_words;              // the eligible words: settled, <= 12 bytes (weights 0)
+    std::vector<int32_t> hot_of_slot;            // short-word slot -> index into hot_words, -1: empty or not eligible
+    std::vector<uint32_t> shortw_of_word;        // index into hm.word_table -> short-word slot
+    std::vector<uint8_t> hot_member;             // per hot_words entry: in the table in use
+    std::vector<uint32_t> hot_counts;            // per hot_words entry: its count in the last census read (diagnostics)
+    std::vector<uint8_t> hot_blob;               // the table in use, as uploaded
+    uint32_t hot_sample = 0, hot_rate_cur = 0, hot_rate_sel = 0;     // last census: sampled pre-tokens; 1/10000ths of them the table in use / the selected table settles
     std::atomic<uint32_t> q16_div{4};    // capacity of the <= 16-byte queue = n_bytes / q16_div (raised to the worst case when a batch overflows it)
     // profiling
     std::atomic<bool> prof{false};
@@ -144,6 +169,8 @@ struct tkamd_tokenizer {
     std::vector<int64_t> shard_bytes;
 };
 
+constexpr size_t HOT_RING = 8;                  // hot tables a handle ever uploads, the load-time one included
+constexpr double HOT_GAIN = 0.02;               // a rebuild must settle this much more of the sample than the table in use
 constexpr size_t PHASE_WGS = 1 << 17;           // workgroups the phase table has rows for (per kernel)
 constexpr size_t MAX_HOST_WORKSPACES = 4;       // concurrent host-entry calls per handle; further callers wait for a free one
 

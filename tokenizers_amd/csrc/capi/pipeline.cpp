@@ -130,6 +130,7 @@ struct Batch {
     // helpers of run_model / compact_and_meta
     void* phases_of(int which);
     void open_word_cache();
+    void hot_census(const DevTables& lt, const ull* endmask);
     // the epilogues and what they share
     void add_specials(); Step finalize(); Step finalize_pairs(); void dense_rows();
     uint64_t batch_longest(uint32_t* d_target, bool* again);
@@ -914,6 +915,23 @@ void Batch::open_word_cache() {
     wc = WordCache{(CacheKey*)w->w_cache_keys.p, w->w_cache_rows.p, nullptr, 0u, nullptr};
 }
 
+// The census behind the hot table (tkamd_tokenizer::hot_adapt): on the handle's first batch of hot_min_bytes of text or more (the caller's bytes: n_x is a host-side BOUND, three
+// times the text behind a normalizer) and on every
+// hot_period-th such batch after it, on the batch's own stream in front of its lookup.  lt: the tables as this batch's lookup reads them
+// (ignore_merges says whether every hit is final).  The synchronisation of the batch reads the counts (read_scalars).
+void Batch::hot_census(const DevTables& lt, const ull* endmask) {
+    if (!t->hot_adapt || !t->hot_adapt_allowed || n_bytes < t->hot_min_bytes || t->hot_of_slot.empty()) return;
+    if (t->hot_gen.load() + 1 >= HOT_RING) return;             // (every buffer of the ring is in use: the handle keeps the table it has)
+    if (t->hot_eligible.fetch_add(1) % (uint64_t)t->hot_period) return;
+    const size_t words = t->hot_of_slot.size() + 1;
+    w->w_hot_hist.reserve(words * 4);
+    HIP_CHECK(hipMemsetAsync(w->w_hot_hist.p, 0, words * 4, st));
+    pf.begin("hot_census");
+    launch_hot_census(st, lt, x_text, n_x, x_len_dev, w->w_startmask.as<ull>(), endmask, matchmask, w->w_hot_hist.as<uint32_t>());
+    pf.end();
+    w->census_pending = true;
+}
+
 void Batch::run_model() {
     tmp_end = (off_mode != TKAMD_OFFSETS_NONE) ? w->w_tmp_end.as<uint32_t>() : nullptr;
     const size_t N = (size_t)n_x;
@@ -937,11 +955,12 @@ void Batch::run_model() {
         if (wc.claims) { mdt.pub_rows = wc.rows; mdt.pub_mask = wc.claim_mask; mdt.pub_pos = wc.claim_pos; }
     };
     if (hm.model == MODEL_BPE) {
+        hot_census(t->dt, endmask);
         pf.begin("lookup");
         open_word_cache();
         set_publish();
         launch_lookup(st, lookup_grid(t), t->dt, x_text, n_x, x_len_dev, w->w_startmask.as<ull>(), endmask, w->w_wprefix.as<uint32_t>(),
-                      w->w_tok0.as<uint32_t>(), plan, d_err, matchmask, t->t_hot.p, wc, 0u, 0u, phases_of(0), d_counters);
+                      w->w_tok0.as<uint32_t>(), plan, d_err, matchmask, t->hot_cur.load(), wc, 0u, 0u, phases_of(0), d_counters);
         pf.end();
         if (hm.ignore_merges)                              // vocab.get(sequence) for pre-tokens beyond the 16-byte keys (bpe/model.rs:559-567)
             launch_long_vocab3(st, t->n_cu, t->dt, x_text, plan.v[1], plan.v[2], plan.v[3], w->w_rows.p, 0u, d_err, wc);
@@ -1027,9 +1046,10 @@ void Batch::run_model() {
         // runs the search on those.  (The reference's per-model cache changes no result; the word cache across batches stays closed.)
         if (use_claims) open_word_cache();
         set_publish();
+        hot_census(t->dt, endmask);
         pf.begin("lookup");
         launch_lookup(st, lookup_grid(t), t->dt, x_text, n_x, x_len_dev, w->w_startmask.as<ull>(), endmask, w->w_wprefix.as<uint32_t>(),
-                      w->w_tok0.as<uint32_t>(), plan, d_err, matchmask, t->t_hot.p, wc, 0u, 0u, phases_of(0), d_counters);
+                      w->w_tok0.as<uint32_t>(), plan, d_err, matchmask, t->hot_cur.load(), wc, 0u, 0u, phases_of(0), d_counters);
         pf.end();
         w->w_uni_state.reserve(N > 64 ? (N + 2) * 16 : 64);      // (a word beyond 64 bytes keeps its state at its own bytes: kernels/unigram.hip)
         pf.begin("unigram");
@@ -1039,9 +1059,10 @@ void Batch::run_model() {
         // WordLevel::tokenize (wordlevel/mod.rs:162-178) is the lookup itself: every hit is final, a miss is the unk id
         DevTables wt = t->dt;
         wt.ignore_merges = 1;
+        hot_census(wt, endmask);
         pf.begin("wordlevel_lookup");
         launch_lookup(st, lookup_grid(t), wt, x_text, n_x, x_len_dev, w->w_startmask.as<ull>(), endmask, w->w_wprefix.as<uint32_t>(),
-                      w->w_tok0.as<uint32_t>(), plan, d_err, matchmask, t->t_hot.p, WordCache{nullptr, nullptr, nullptr, 0u, nullptr}, 0u, 1u, nullptr, nullptr);
+                      w->w_tok0.as<uint32_t>(), plan, d_err, matchmask, t->hot_cur.load(), WordCache{nullptr, nullptr, nullptr, 0u, nullptr}, 0u, 1u, nullptr, nullptr);
         launch_long_vocab3(st, t->n_cu, wt, x_text, plan.v[1], plan.v[2], plan.v[3], w->w_rows.p, 1u, d_err, WordCache{nullptr, nullptr, nullptr, 0u, nullptr});      // words longer than 16 bytes
         pf.end();
     } else {
@@ -1056,9 +1077,10 @@ void Batch::run_model() {
         // every word taking the walk -- max_input_chars_per_word < 16 -- the lookup probes nothing, the cache included.)
         if (shortcut) open_word_cache();
         set_publish();
+        if (shortcut) hot_census(wt, endmask);                 // (without the shortcut the lookup probes no table)
         pf.begin("wordpiece_word_lookup");
         launch_lookup(st, lookup_grid(t), wt, x_text, n_x, x_len_dev, w->w_startmask.as<ull>(), endmask, w->w_wprefix.as<uint32_t>(),
-                      w->w_tok0.as<uint32_t>(), plan, d_err, matchmask, t->t_hot.p, wc, shortcut ? 0u : 1u, 0u, phases_of(0), d_counters);
+                      w->w_tok0.as<uint32_t>(), plan, d_err, matchmask, t->hot_cur.load(), wc, shortcut ? 0u : 1u, 0u, phases_of(0), d_counters);
         pf.end();
         pf.begin("wordpiece");
         launch_wordpiece_all(st, grid, t->n_cu, mdt, x_text, plan, w->w_rows.p, w->w_tmp_ids.as<uint32_t>(), tmp_end, d_err);      // the <= 16-byte queue and the words longer than that, side by side
@@ -1233,8 +1255,17 @@ int finish_batch(tkamd_tokenizer* t, Workspace* w, hipStream_t st, int64_t* n_to
 
 int read_scalars(tkamd_tokenizer* t, Workspace* w, hipStream_t st, int64_t* n_tok, int64_t* n_pretok) {
     int64_t host[SC_SLOTS];
+    const bool census = w->census_pending && w->w_hot_hist.p;      // the batch took a census: its counts come with the scalars, behind the same wait
+    if (census) {
+        w->h_hot_hist.assign(t->hot_of_slot.size() + 1, 0u);
+        HIP_CHECK(hipMemcpyAsync(w->h_hot_hist.data(), w->w_hot_hist.p, w->h_hot_hist.size() * 4, hipMemcpyDeviceToHost, st));
+    }
     HIP_CHECK(hipMemcpyAsync(host, w->w_scalars.p, sizeof(host), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
+    if (census) {
+        w->census_pending = false;
+        hot_census_read(t, w->h_hot_hist, st);
+    }
     int err = *(int*)&host[SC_ERR] & ~NOTE_BITS;             // (notes of the normalizer and of the added tokens' speculation, not errors)
     w->last_note_added = (*(int*)&host[SC_ERR] & NOTE_ADDED_SEEN) != 0;
     w->last_note_nfc = (*(int*)&host[SC_ERR] & NOTE_NFC_SEEN) != 0;

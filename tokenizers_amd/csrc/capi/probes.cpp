@@ -180,6 +180,33 @@ int tkamd_word_cache(tkamd_tokenizer* t, int enable, int clear) {
     return TKAMD_OK;
 }
 
+int tkamd_hot_adapt(tkamd_tokenizer* t, int enable) {
+    if (!t) return set_error(TKAMD_ERR_INVALID, "null argument");
+    t->hot_adapt = enable != 0;
+    return TKAMD_OK;
+}
+
+int tkamd_hot_table_read(tkamd_tokenizer* t, void* blob, int64_t blob_cap, uint32_t* eligible_ids, int64_t ids_cap, int64_t* n_eligible, uint32_t* stats) {
+    if (!t) return set_error(TKAMD_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(t->mu);
+    if (blob && blob_cap > 0) memcpy(blob, t->hot_blob.data(), std::min<size_t>((size_t)blob_cap, t->hot_blob.size()));
+    if (n_eligible) *n_eligible = (int64_t)t->hot_words.size();
+    for (int64_t i = 0; eligible_ids && i < ids_cap && i < (int64_t)t->hot_words.size(); ++i) eligible_ids[i] = t->hot_words[(size_t)i].id;
+    if (stats) {
+        const uint32_t v[8] = {t->hot_gen.load(), (uint32_t)t->n_hot, t->hot_sample, t->hot_rate_cur, t->hot_rate_sel, t->hm.word_seed,
+                               (t->hot_adapt && t->hot_adapt_allowed) ? 1u : 0u, (uint32_t)HOT_SLOTS};
+        memcpy(stats, v, sizeof(v));
+    }
+    return (int)t->hot_blob.size();
+}
+
+int64_t tkamd_hot_census_counts(tkamd_tokenizer* t, uint32_t* counts, int64_t cap) {
+    if (!t) return set_error(TKAMD_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(t->mu);
+    for (int64_t i = 0; counts && i < cap && i < (int64_t)t->hot_counts.size(); ++i) counts[i] = t->hot_counts[(size_t)i];
+    return (int64_t)t->hot_counts.size();
+}
+
 int tkamd_profile_enable(tkamd_tokenizer* t, int on) {
     if (!t) return set_error(TKAMD_ERR_INVALID, "null argument");
     t->prof = on != 0;
@@ -257,6 +284,13 @@ int tkamd_profile_counters(tkamd_tokenizer* t, uint32_t* out, int n) {
         if (n > 19) out[19] = t->dt.shortw ? t->dt.shortw_bmask + 1u : 0u; // (short-word displacement buckets)
         if (n > 20) out[20] = t->shortw_max_disp;                          // (the largest short-word displacement: above 255, the placement needed its 16 bits)
         if (n > 21) out[21] = (uint32_t)t->hm.merge_table.size();          // (merge-table slots)
+        // the hot table: rebuilds so far, words in the table in use, and the last census -- its sampled pre-tokens and how many 1/10000ths
+        // of them the table then in use / the table its counts selected settle
+        if (n > 23) out[23] = t->hot_gen.load();
+        if (n > 24) out[24] = (uint32_t)t->n_hot;
+        if (n > 25) out[25] = t->hot_sample;
+        if (n > 26) out[26] = t->hot_rate_cur;
+        if (n > 27) out[27] = t->hot_rate_sel;
         if (!w) return TKAMD_OK;
         for (int i = 0; i < n && i < CNT_COUNT; ++i) out[i] = w->last_counters[i];
         if (n > 13) out[13] = (uint32_t)pair_merge_occupancy();            // (workgroups of k_bpe_merge_lds_pair resident per CU: its grid is that x the CUs)

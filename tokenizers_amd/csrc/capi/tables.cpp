@@ -318,6 +318,8 @@ void build_shortw_table(tkamd_tokenizer* t) {
         tab[where[i]] = HotSlot{(uint32_t)w->lo, (uint32_t)(w->lo >> 32), (uint32_t)w->hi, w->id | (w->len << SHORTW_LEN_SHIFT) | ((w->flags & WORD_DIRECT) ? SHORTW_DIRECT : 0u)};
     }
     for (size_t i = 0; i < ws.size(); ++i) k3[where[i]] = (uint32_t)(ws[i]->hi >> 32);
+    t->shortw_of_word.assign(hm.word_table.size(), 0xFFFFFFFFu);      // (the host's side of a census: hot_census_read)
+    for (size_t i = 0; i < ws.size(); ++i) t->shortw_of_word[(size_t)(ws[i] - hm.word_table.data())] = where[i];
     upload(t->t_shortw, tab, 64);
     upload(t->t_shortw_k3, k3, 64);
     t->dt.shortw_k3 = t->t_shortw_k3.as<uint32_t>();
@@ -328,56 +330,71 @@ void build_shortw_table(tkamd_tokenizer* t) {
     t->dt.shortw_bmask = n_buckets - 1u;
 }
 
-// Hot-word table of the lookup kernel: the settled words of <= 12 bytes with the lowest ids, direct mapped (tables.hpp).
+// Hot-word table of the lookup kernel: settled words of <= 12 bytes, hash-and-displace (tables.hpp; the builder: hot_table_core.hpp).
 // "Settled" = a hit needs no further work: every word for WordLevel / WordPiece / ignore_merges, the WORD_DIRECT ones for
-// byte-level BPE.  Trainers hand out ids in frequency order, so low ids are the frequent words; a word that loses its slot
-// to a lower id stays reachable through the perfect-hash table.
+// byte-level BPE.  At load every word weighs the same and the lowest ids win (trainers hand out ids in frequency order -- true of tokens);
+// a census of the handle's own text (kernels/lookup.hip k_hot_census) then weighs the words by how often they stand as whole pre-tokens,
+// and hot_census_read below builds the table again from those weights.  A word that is not in the table stays reachable through the
+// short-word table: what the table holds never changes a result.
+void hot_install(tkamd_tokenizer* t, const HotTableBuild& b) {
+    t->n_hot = b.n_hot;
+    t->hot_blob = b.blob;
+    t->hot_member.assign(t->hot_words.size(), 0);
+    for (uint32_t i : b.placed) t->hot_member[i] = 1;
+}
+
 void build_hot_table(tkamd_tokenizer* t) {
     HostModel& hm = t->hm;
-    const uint32_t slots = (uint32_t)HOT_SLOTS, n_buckets = slots / 4u;
-    std::vector<HotSlot> hot(slots, HotSlot{0u, 0u, 0u, 0u});
-    std::vector<uint16_t> disp(n_buckets, 0);
-    std::vector<const WordSlot*> cand;
     const bool all_final = (hm.model != MODEL_BPE && hm.model != MODEL_UNIGRAM) || hm.ignore_merges;
-    for (const WordSlot& w : hm.word_table)
-        if (w.len && w.len <= (uint32_t)HOT_MAX_KEY && (all_final || (w.flags & WORD_DIRECT))) cand.push_back(&w);
-    // the lowest ids (= the most frequent words: the trainers append tokens in frequency order), as many as fit at 15/16 full
-    std::sort(cand.begin(), cand.end(), [](const WordSlot* a, const WordSlot* b) { return a->id < b->id; });
-    if (cand.size() > (size_t)slots * 15 / 16) cand.resize((size_t)slots * 15 / 16);
-    auto hash_of = [&](const WordSlot* w) { return hot_hash((uint32_t)w->lo, (uint32_t)(w->lo >> 32), (uint32_t)w->hi, w->len, hm.word_seed); };
-    // hash-and-displace: the fullest buckets first, each takes the first displacement that drops all of its words on free slots; a
-    // bucket nothing fits loses its highest id and tries again (that word is then answered by the table in HBM, like every other)
-    std::vector<std::vector<const WordSlot*>> buckets(n_buckets);
-    for (const WordSlot* w : cand) buckets[hot_bucket(hash_of(w), slots)].push_back(w);      // (ascending ids inside a bucket)
-    std::vector<uint32_t> order(n_buckets);
-    for (uint32_t i = 0; i < n_buckets; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return buckets[a].size() > buckets[b].size(); });
-    int n = 0;
-    for (uint32_t bi : order) {
-        std::vector<const WordSlot*>& bk = buckets[bi];
-        while (!bk.empty()) {
-            uint32_t d = 0;
-            for (; d < slots; ++d) {
-                bool ok = true;
-                for (size_t i = 0; i < bk.size() && ok; ++i) {
-                    const uint32_t s = hot_slot(hash_of(bk[i]), d, slots);
-                    ok = hot[s].id_len == 0u;
-                    for (size_t j = 0; j < i && ok; ++j) ok = hot_slot(hash_of(bk[j]), d, slots) != s;
-                }
-                if (ok) break;
-            }
-            if (d < slots) {
-                disp[bi] = (uint16_t)d;
-                for (const WordSlot* w : bk) hot[hot_slot(hash_of(w), d, slots)] = HotSlot{(uint32_t)w->lo, (uint32_t)(w->lo >> 32), (uint32_t)w->hi, w->id | (w->len << 24)};
-                n += (int)bk.size();
-                break;
-            }
-            bk.pop_back();
-        }
+    t->hot_words.clear();
+    t->hot_of_slot.assign((size_t)t->dt.shortw_mask + 1u, -1);
+    for (size_t i = 0; i < hm.word_table.size(); ++i) {
+        const WordSlot& w = hm.word_table[i];
+        if (!(w.len && w.len <= (uint32_t)HOT_MAX_KEY && (all_final || (w.flags & WORD_DIRECT)))) continue;
+        const uint32_t slot = i < t->shortw_of_word.size() ? t->shortw_of_word[i] : 0xFFFFFFFFu;
+        if (slot < t->hot_of_slot.size()) t->hot_of_slot[slot] = (int32_t)t->hot_words.size();
+        t->hot_words.push_back(HotWord{(uint32_t)w.lo, (uint32_t)(w.lo >> 32), (uint32_t)w.hi, w.len, w.id, 0ull});
     }
-    t->n_hot = n;
-    std::vector<uint8_t> blob((size_t)hot_table_bytes((int)slots));
-    memcpy(blob.data(), hot.data(), (size_t)slots * 16);
-    memcpy(blob.data() + (size_t)slots * 16, disp.data(), (size_t)n_buckets * 2);
-    upload(t->t_hot, blob);
+    const HotTableBuild b = build_hot_table_core(t->hot_words, (uint32_t)HOT_SLOTS, hm.word_seed);
+    hot_install(t, b);
+    upload(t->t_hot, b.blob);
+    t->hot_cur = t->t_hot.p;
+}
+
+// The synchronisation of a batch that took a census (read_scalars, behind its wait): h = the counts by short-word slot, then the sampled
+// pre-tokens.  Nothing the device wrote is trusted: a count is taken only for a slot of the host's own table whose word is <= 12 bytes and
+// settled by the rule above (hot_of_slot) -- a word that is not could change ids from inside the hot table -- and the rates are
+// clamped.  The table the counts select replaces the one in use only if it would have settled HOT_GAIN more of the sample: text whose
+// words stay what they were settles after one rebuild.
+void hot_census_read(tkamd_tokenizer* t, const std::vector<uint32_t>& h, hipStream_t st) {
+    std::lock_guard<std::mutex> lk(t->mu);
+    const size_t n_slots = t->hot_of_slot.size();
+    if (h.size() != n_slots + 1) return;
+    const uint64_t total = h[n_slots];
+    if (total == 0) return;
+    std::vector<HotWord> words = t->hot_words;
+    t->hot_counts.assign(words.size(), 0u);
+    uint64_t cur = 0;
+    for (size_t s = 0; s < n_slots; ++s) {
+        if (!h[s] || t->hot_of_slot[s] < 0) continue;
+        const size_t e = (size_t)t->hot_of_slot[s];
+        words[e].weight = h[s];
+        t->hot_counts[e] = h[s];
+        if (t->hot_member[e]) cur += h[s];
+    }
+    const HotTableBuild b = build_hot_table_core(words, (uint32_t)HOT_SLOTS, t->hm.word_seed);
+    auto rate = [&](uint64_t x) { return (uint32_t)(std::min(x, total) * 10000ull / total); };
+    t->hot_sample = (uint32_t)std::min<uint64_t>(total, 0xFFFFFFFFull);
+    t->hot_rate_cur = rate(cur);
+    t->hot_rate_sel = rate(b.weight_placed);
+    if (t->hot_rate_sel < t->hot_rate_cur + (uint32_t)(HOT_GAIN * 10000.0) || t->hot_ring.size() + 1 >= HOT_RING) return;
+    // a buffer of its own, complete before any launch can be given its address
+    std::unique_ptr<DevBuf> nb(new DevBuf());
+    nb->reserve(b.blob.size());
+    HIP_CHECK(hipMemcpyAsync(nb->p, b.blob.data(), b.blob.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    hot_install(t, b);
+    t->hot_cur = nb->p;
+    t->hot_ring.push_back(std::move(nb));
+    ++t->hot_gen;
 }

@@ -375,6 +375,10 @@ void launch_lookup(hipStream_t st, int grid, const DevTables& t, const uint8_t* 
                    const unsigned long long* startmask, const unsigned long long* endmask, const uint32_t* wprefix, uint32_t* tok0,
                    const QueuePlan& plan, int* err, const unsigned long long* matchmask, const void* hot, const WordCache& wc,
                    uint32_t no_hits, uint32_t miss_is_unk, void* phases = nullptr, uint32_t* counters = nullptr);      // phases: [grid][8] u64, diagnostic instantiation (lookup.hip)
+// the census behind the hot table (kernels/lookup.hip k_hot_census): hist[slot of the short-word table] += the sampled pre-tokens of <= 12 bytes
+// that are that slot's word and settled by it, hist[slots] += the sampled pre-tokens; the caller zeroes hist ((slots + 1) words) in front
+void launch_hot_census(hipStream_t st, const DevTables& t, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* startmask,
+                       const unsigned long long* endmask, const unsigned long long* matchmask, uint32_t* hist);
 // group: 64 = a wavefront per pre-token; 1 / 2 = one lane per pre-token, Word in registers (16 / 32 symbols: vocabularies whose new ids are not rank + c);
 // 5 / 6 = one lane per pre-token, keys in LDS (16 / 32 symbols; needs new_id = rank + c)
 // also (group 6 only): a second queue for the same launch

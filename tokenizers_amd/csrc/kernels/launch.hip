@@ -78,6 +78,26 @@ void launch_lookup(hipStream_t st, int grid, const DevTables& t, const uint8_t* 
     else if (endmask) hipLaunchKernelGGL((k_lookup<true, false>), dim3(grid), dim3(LU_NT), lds, st, a);
     else hipLaunchKernelGGL((k_lookup<false, false>), dim3(grid), dim3(LU_NT), lds, st, a);
 }
+void launch_hot_census(hipStream_t st, const DevTables& t, const uint8_t* text, int64_t n_bytes, const int64_t* len_dev, const unsigned long long* startmask,
+                       const unsigned long long* endmask, const unsigned long long* matchmask, uint32_t* hist) {
+    CensusArgs a{};
+    a.text = text;
+    a.n_bytes_host = n_bytes;
+    a.len_dev = len_dev;
+    a.startmask = startmask;
+    a.endmask = endmask;
+    a.matchmask = matchmask;
+    a.shortw = (const uint4*)t.shortw;
+    a.shortw_disp = t.shortw_disp;
+    a.shortw_mask = t.shortw_mask;
+    a.shortw_bmask = t.shortw_bmask;
+    a.word_seed = t.word_seed;
+    a.any_hit_final = t.ignore_merges;
+    a.hist = hist;
+    // (a fixed grid: the text's length may exist on the device only; the workgroups beyond the sample leave at once)
+    if (endmask) hipLaunchKernelGGL(k_hot_census<true>, dim3(HC_TILES * HC_QUARTERS), dim3(HC_NT), 0, st, a);
+    else hipLaunchKernelGGL(k_hot_census<false>, dim3(HC_TILES * HC_QUARTERS), dim3(HC_NT), 0, st, a);
+}
 void launch_bpe_merge(hipStream_t st, int grid, int group, const DevTables& t, const uint8_t* text, const QView& v, void* rows,
                       uint32_t* tmp_ids, uint32_t* tmp_end, const QView* also) {
     uint4* r = (uint4*)rows;

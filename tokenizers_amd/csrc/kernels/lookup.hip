@@ -667,3 +667,101 @@ __global__ __launch_bounds__(256) void k_word_cache_insert(DevTables t, const ui
         ck->state = it.len;                                                         // (read by later kernels only: no fence needed)
     }
 }
+
+// =================================================================================================
+// K_hot_census: which words stand as whole pre-tokens in the text this handle sees.  The hot table of k_lookup holds 960 settled words of
+// <= 12 bytes; WHICH ones is the host's choice (hot_table_core.hpp), and the lowest ids -- the load-time choice -- are mostly fragments
+// that never stand alone.  Once in a great many batches (capi/pipeline.cpp Batch::hot_census) this kernel counts a sample of the batch:
+// up to HC_TILES tiles of LU_TILE bytes, strided evenly over the text.  Every pre-token that STARTS in a sampled tile (wherever it ends),
+// has 1 .. 12 bytes and is not under an added-token match probes the short-word table exactly as pass 2 of k_lookup does; a word found
+// there whose hit is final counts for its slot: hist[slot].  hist[slots] counts the sampled pre-tokens (of any length, matches excepted).
+// The host reads the histogram at the batch's synchronisation and trusts none of it (capi/tables.cpp hot_census_read).
+// A workgroup takes a QUARTER of a tile (4 KB: 64 mask words, four lanes a word) and aggregates in LDS -- an open-addressing table of
+// HC_LDS entries keyed by the slot; a quarter starts at most 4,096 pre-tokens, so the table cannot overflow and every probe loop ends
+// within HC_LDS steps -- then adds each distinct slot ONCE: no address receives more than one global atomic per workgroup (a frequent
+// word is a twentieth of the sample, and same-address atomics resolve one at a time).  Nothing waits for another workgroup.
+// =================================================================================================
+constexpr int HC_TILES = 64;                             // tiles sampled per census (1 MiB of a batch that has as much)
+constexpr int HC_QUARTERS = 4;                           // workgroups per tile
+constexpr int HC_NT = 256;                               // four lanes per mask word of a quarter
+constexpr int HC_WORDS = LU_TILE_WORDS / HC_QUARTERS;    // mask words per workgroup (64)
+constexpr int HC_LDS = 4096;                             // >= the pre-tokens a quarter can start (one per byte)
+static_assert(HC_NT == 4 * HC_WORDS, "four lanes per mask word");
+static_assert(HC_LDS >= HC_WORDS * 64 && (HC_LDS & (HC_LDS - 1)) == 0, "one entry per byte of the quarter, a power of two");
+
+struct CensusArgs {
+    const uint8_t* text;
+    int64_t n_bytes_host;            // (readable to n_bytes_host + TEXT_PAD)
+    const int64_t* len_dev;
+    const unsigned long long* startmask;
+    const unsigned long long* endmask;
+    const unsigned long long* matchmask;
+    const uint4* shortw;
+    const uint16_t* shortw_disp;
+    uint32_t shortw_mask, shortw_bmask, word_seed, any_hit_final;
+    uint32_t* hist;                  // [shortw_mask + 1] counts by slot, then [1]: the sampled pre-tokens
+};
+
+// tile of the sample's i-th place: n_sample places strided evenly over n_tiles (tests recount with the same rule)
+__host__ __device__ inline int64_t hot_census_tile(int64_t i, int64_t n_sample, int64_t n_tiles) { return i * n_tiles / n_sample; }
+
+template <bool HAS_END>
+__global__ __launch_bounds__(HC_NT) void k_hot_census(CensusArgs a) {
+    __shared__ uint32_t s_key[HC_LDS], s_cnt[HC_LDS];
+    __shared__ uint32_t s_total;
+    const int tid = (int)threadIdx.x;
+    for (int i = tid; i < HC_LDS; i += HC_NT) { s_key[i] = 0xFFFFFFFFu; s_cnt[i] = 0u; }
+    if (tid == 0) s_total = 0u;
+    __syncthreads();
+    int64_t n_bytes = a.len_dev ? *a.len_dev : a.n_bytes_host;
+    n_bytes = max((int64_t)0, min(n_bytes, a.n_bytes_host));
+    const int64_t total_words = (n_bytes + 63) >> 6;             // start bits exist only below n_bytes
+    const int64_t end_words = (n_bytes >> 6) + 1;                // an end bit can sit at byte n_bytes
+    const int64_t n_tiles = (total_words + LU_TILE_WORDS - 1) / LU_TILE_WORDS;
+    const int64_t n_sample = min((int64_t)HC_TILES, n_tiles);
+    const int64_t place = (int64_t)(blockIdx.x / HC_QUARTERS);
+    uint32_t mine = 0u;
+    if (place < n_sample) {
+        const int64_t w = hot_census_tile(place, n_sample, n_tiles) * LU_TILE_WORDS + (int64_t)(blockIdx.x % HC_QUARTERS) * HC_WORDS + (tid >> 2);
+        if (w < total_words) {
+            // the mask that ENDS a pre-token, over bytes 64 w .. 64 w + 127: the next start, or the end bit; the end of the text ends one too
+            const unsigned long long ms = a.startmask[w];
+            const unsigned long long* const em = HAS_END ? a.endmask : a.startmask;
+            const int64_t em_words = HAS_END ? end_words : total_words;
+            unsigned long long e_lo = HAS_END ? em[w] : ms, e_hi = (w + 1 < em_words) ? em[w + 1] : 0ull;
+            if ((n_bytes >> 6) == w) e_lo |= 1ull << (n_bytes & 63);
+            if ((n_bytes >> 6) == w + 1) e_hi |= 1ull << (n_bytes & 63);
+            const unsigned long long mm = a.matchmask ? a.matchmask[w] : 0ull;
+            const int b0 = (tid & 3) * 16;
+            for (uint32_t m = (uint32_t)(ms >> b0) & 0xFFFFu; m; m &= m - 1u) {
+                const int b = b0 + (__ffs(m) - 1);
+                if ((mm >> b) & 1ull) continue;                   // an added-token match: its id is patched in, the tables never see it
+                ++mine;
+                // ends at bytes b + 1 .. b + 12 of this word's window
+                const unsigned long long after = b == 63 ? e_hi : ((e_lo >> (b + 1)) | (e_hi << (63 - b)));
+                const uint32_t near = (uint32_t)after & ((1u << HOT_MAX_KEY) - 1u);
+                if (!near) continue;                              // longer than 12 bytes
+                const uint32_t len = (uint32_t)__ffs(near);
+                uint64_t lo, hi;
+                load_key16(a.text, (uint32_t)((w << 6) + b), len, &lo, &hi);
+                const uint32_t k0 = (uint32_t)lo, k1 = (uint32_t)(lo >> 32), k2 = (uint32_t)hi;
+                const uint32_t h1 = word_hash1_from_hot(hot_hash(k0, k1, k2, len, a.word_seed), 0u);
+                const uint32_t slot = shortw_slot(h1, shortw_kmix(k0, k1, k2, 0u), (uint32_t)a.shortw_disp[h1 & a.shortw_bmask], a.shortw_mask);
+                const uint4 s = a.shortw[slot];
+                const bool found = ((s.x ^ k0) | (s.y ^ k1) | (s.z ^ k2) | (((s.w >> SHORTW_LEN_SHIFT) & SHORTW_LEN_MASK) ^ len)) == 0u;
+                if (!found || !(a.any_hit_final || (s.w & SHORTW_DIRECT))) continue;
+                uint32_t e = (slot * 0x9E3779B1u) >> 20;          // (12 bits: HC_LDS entries)
+                static_assert(HC_LDS == 1 << 12, "the entry hash keeps 12 bits");
+                for (int tries = 0; tries < HC_LDS; ++tries, e = (e + 1u) & (uint32_t)(HC_LDS - 1)) {
+                    const uint32_t old = atomicCAS(&s_key[e], 0xFFFFFFFFu, slot);
+                    if (old == 0xFFFFFFFFu || old == slot) { atomicAdd(&s_cnt[e], 1u); break; }
+                }
+            }
+        }
+    }
+    if (mine) atomicAdd(&s_total, mine);
+    __syncthreads();
+    for (int i = tid; i < HC_LDS; i += HC_NT)
+        if (s_key[i] != 0xFFFFFFFFu) atomicAdd(a.hist + s_key[i], s_cnt[i]);          // (s_key[i] is a slot this workgroup computed: <= shortw_mask)
+    if (tid == 0 && s_total) atomicAdd(a.hist + (size_t)a.shortw_mask + 1u, s_total);
+}

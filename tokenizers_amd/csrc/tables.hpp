@@ -131,7 +131,8 @@ TK_HD uint32_t shortw_slot(uint32_t h1, uint32_t kmix, uint32_t d, uint32_t mask
     return (base + d * step) & mask;
 }
 
-// ---- hot-word table: the lowest-id settled words of <= 12 bytes, copied into LDS by the lookup kernel ----
+// ---- hot-word table: settled words of <= 12 bytes, copied into LDS by the lookup kernel -- the lowest ids at load, then the words that stand
+// as whole pre-tokens in the handle's own text (hot_table_core.hpp builds it, kernels/lookup.hip k_hot_census counts) ----
 // slot = {k0, k1, k2, id | len << 24} (key bytes zero padded; len 0 = empty slot).  Hash-and-displace like the tables in HBM, so the
 // table holds exactly the words it is meant to hold: bucket = hot_hash & (slots / 4 - 1) selects a 16-bit displacement (the array
 // follows the slots, in the same buffer), the word lives in slot (hot_hash >> 12) + d.  (Round 3's table was direct mapped: of the

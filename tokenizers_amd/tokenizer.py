@@ -733,7 +733,7 @@ class Tokenizer:
         self._no_post_processor = re.search(r'"post_processor"\s*:\s*null', json_str) is not None or '"post_processor"' not in json_str
         info = _lib.Info()
         _lib.check(lib.tkamd_tokenizer_info(self._h, C.byref(info)))
-        self.info = {f: getattr(info, f) for f, _ in _lib.Info._fields_}
+        self._info = {f: getattr(info, f) for f, _ in _lib.Info._fields_}
         pre, suf = (C.c_uint32 * 16)(), (C.c_uint32 * 16)()
         npre, nsuf = C.c_int32(0), C.c_int32(0)
         rc = lib.tkamd_tokenizer_specials(self._h, pre, C.byref(npre), suf, C.byref(nsuf), 16)
@@ -1515,6 +1515,45 @@ class Tokenizer:
                                                    "char" if "offset_mapping" in tensors else "none", "word_ids" in tensors,
                                                    torch.cuda.current_stream(dev).cuda_stream)
         return TensorBatch(tensors, batch, keep + (text, off))
+
+    @property
+    def info(self) -> dict:
+        """What the handle was loaded as (``tkamd_tokenizer_info``), and the state of its hot-word table (:meth:`hot_table`)."""
+        return {**self._info, **self.hot_table()}
+
+    def hot_adapt(self, enable: bool = True) -> None:
+        """The hot-word table of the lookup learns which words stand as whole pre-tokens in this handle's text: a census on the first
+        batch of 8 MiB or more and on every 1024th after it, read -- and the table rebuilt if that pays -- when that batch is
+        synchronised (``tkamd_hot_adapt``).  On by default (``TKAMD_HOT_ADAPT=0`` in the environment: off from the start); ``False``
+        stops the censuses and keeps the table in use.  Results never change."""
+        _lib.check(self._lib.tkamd_hot_adapt(self._h, 1 if enable else 0))
+
+    def hot_table(self, words: bool = False) -> dict:
+        """The hot-word table: ``hot_generation`` (rebuilds so far), ``n_hot`` (words in it), and of the last census ``hot_census_sample``
+        (pre-tokens it sampled) and the shares of them the table then in use / the table its counts selected settle (``hot_rate_in_use``,
+        ``hot_rate_selected``).  ``words=True`` adds the table itself (``blob``), the ids of every word that may stand in it
+        (``eligible_ids``) and the tables' hash seed (``word_seed``)."""
+        st = (C.c_uint32 * 8)()
+        n = C.c_int64(0)
+        size = self._lib.tkamd_hot_table_read(self._h, None, 0, None, 0, C.byref(n), st)
+        out = {"hot_generation": st[0], "n_hot": st[1], "hot_census_sample": st[2], "hot_rate_in_use": st[3] / 10000.0, "hot_rate_selected": st[4] / 10000.0,
+               "hot_adapt": bool(st[6])}
+        if words:
+            blob = (C.c_uint8 * max(size, 1))()
+            ids = (C.c_uint32 * max(n.value, 1))()
+            self._lib.tkamd_hot_table_read(self._h, blob, size, ids, n.value, None, None)
+            out.update(blob=bytes(blob)[:size], eligible_ids=list(ids)[:n.value], word_seed=st[5], slots=st[7])
+        return out
+
+    def hot_census_counts(self) -> dict[int, int]:
+        """What the last census counted: token id of an eligible word -> sampled pre-tokens that were that word (the words it met only)."""
+        n = self._lib.tkamd_hot_census_counts(self._h, None, 0)
+        if n <= 0:
+            return {}
+        cnt = (C.c_uint32 * n)()
+        self._lib.tkamd_hot_census_counts(self._h, cnt, n)
+        ids = self.hot_table(words=True)["eligible_ids"]
+        return {i: c for i, c in zip(ids, cnt) if c}
 
     def word_cache(self, enable: bool = True, clear: bool = False) -> None:
         """The device-side counterpart of the reference's per-thread BPE word cache (models/bpe/model.rs:573-586): words of <= 16
